@@ -12,8 +12,16 @@ to rank 0 over RCCL inside the step (the path's only exchange).  Weak scaling: r
 [r*65536, (r+1)*65536) of the corpus.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel stage, timed with HIP events on the launch
-stream (zgpu_profile_*); `cpu_baseline` is the compiled reference (or the repo's CPU restatement when
-oracle/_ref is absent) timed on the host cores over a bounded sample of the same workload, rank 0, N=1 only.
+stream (zgpu_profile_*).  A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+dump of --dump-outputs, the line.  --full adds the checks and the other measurements: the sampled chunks against
+the reference's hashes, the `extra` legs (inflate, level 1, level 9, the continuous stream, host buffers, a foreign
+stream) and `cpu_baseline`, the compiled reference (or the repo's CPU restatement when oracle/_ref is absent) timed
+on the host cores over a bounded sample of the same workload, rank 0, N=1 only.
+
+--dump-outputs DIR writes, after the timed steps, what the last step gave its caller (rank 0 for N > 1: the gathered
+stream) as DIR/<name>.npy, about 35 MB in all: a byte array as a seeded sample of 64 KiB windows (float32) with the
+windows' starts (<name>_at) and a position-weighted sum of every 64 KiB window of the whole array (<name>_digest,
+float64, exact); `chunk_offsets` and `result` (byte count, Adler-32) as float64.
 """
 import argparse
 import json
@@ -39,9 +47,11 @@ def parse():
     ap.add_argument("--lz", default="auto", choices=["auto", "serial", "parallel", "sorted", "walk", "fast", "fastwin"])
     ap.add_argument("--op", default="deflate", choices=["deflate", "inflate"])
     ap.add_argument("--cpu-sample-mib", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--continuous", action="store_true", help="the timed step makes ONE continuous stream (what compress2() of the reference emits) instead of independent chunks: for profiles of that path")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip inflate / level 1 / level 9 / host-buffer runs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip inflate / level 1 / level 9 / host-buffer runs")
+    ap.add_argument("--full", action="store_true", help="also check the output against the reference's hashes and run the extra legs and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -142,6 +152,43 @@ def check_sampled_chunks(torch, dst, offs, nchunks, rank_chunk0, level, workload
     return len(rows)
 
 
+DUMP_WINDOW = 64 << 10  # bytes
+DUMP_WINDOWS = 128      # windows sampled of a longer byte array: 8 MiB, 32 MiB as float32
+DUMP_SEED = 0xD5EED
+
+
+def dump_outputs(torch, d, bytes_arrays, value_arrays):
+    """--dump-outputs: bytes_arrays, name -> 1-D uint8 device tensor; value_arrays, name -> list of integers (exact in float64 below 2**53).
+    A byte array is sampled by 64 KiB windows of a fixed grid: its first and last window and, by a fixed seed, DUMP_WINDOWS - 2 of the rest
+    (all of them when it has no more).  The digest covers every window of the array: sum((i + 1) * byte[i]) over its bytes, at most
+    255 * 65536 * 65537 / 2 < 2**53, so that a byte that differs outside the sample still shows."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in bytes_arrays.items():
+        n = t.numel()
+        nwin = -(-n // DUMP_WINDOW)
+        if nwin <= DUMP_WINDOWS:
+            at = np.arange(nwin, dtype=np.int64)
+        else:
+            rest = np.random.default_rng(DUMP_SEED).choice(np.arange(1, nwin - 1), DUMP_WINDOWS - 2, replace=False)
+            at = np.sort(np.concatenate([[0, nwin - 1], rest]))
+        at = at * DUMP_WINDOW
+        sample = torch.cat([t[s:s + DUMP_WINDOW] for s in at.tolist()]) if n else t[:0]
+        np.save(os.path.join(d, name + ".npy"), sample.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(d, name + "_at.npy"), at.astype(np.float64))
+        w = torch.arange(1, DUMP_WINDOW + 1, dtype=torch.int64, device=t.device)
+        digest = []
+        for s in range(0, n, DUMP_WINDOW << 12):  # 4096 windows at a time: 2 GiB of int64
+            part = t[s:s + (DUMP_WINDOW << 12)].to(torch.int64)
+            k = -(-part.numel() // DUMP_WINDOW)
+            part = torch.cat([part, part.new_zeros(k * DUMP_WINDOW - part.numel())]).view(k, DUMP_WINDOW)
+            digest.append((part * w).sum(1))
+        digest = torch.cat(digest).cpu().numpy() if digest else np.zeros(0)
+        np.save(os.path.join(d, name + "_digest.npy"), digest.astype(np.float64))
+    for name, v in value_arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     a = parse()
     import torch
@@ -223,7 +270,7 @@ def main():
         nonlocal gather_buf
         if comm is None:  # zlib_amd/shard.py: the same exchange over the process group
             body = dst[: res.out_bytes]
-            _, total = shard.gather_stream(body, res.adler32, nbytes, a.level, out=gather_buf if rank == 0 else None)
+            state["stream"], total = shard.gather_stream(body, res.adler32, nbytes, a.level, out=gather_buf if rank == 0 else None)
             if rank == 0 and (gather_buf is None or gather_buf.numel() < total):
                 gather_buf = torch.empty(total + (total >> 4), dtype=torch.uint8, device=dev)  # (the next step reuses it)
             state["gathered"] = total
@@ -233,6 +280,7 @@ def main():
         if rank == 0 and (gather_buf is None or gather_buf.numel() < total):
             gather_buf = torch.empty(total + (total >> 4), dtype=torch.uint8, device=dev)
         comm.gather(dst.data_ptr(), table, a.level, gather_buf.data_ptr() if rank == 0 else None, gather_buf.numel() if rank == 0 else 0, stream=stream)
+        state["stream"] = gather_buf[:total] if rank == 0 else None
         state["gathered"] = total
 
     def inflate_step():
@@ -271,13 +319,25 @@ def main():
         return dt, prof
 
     dt, prof = timed(step, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        res = state["ires"] if a.op == "inflate" else state["res"]
+        if a.op == "inflate":
+            bytes_arrays = {"output": src2[: res.out_bytes]}
+        elif world > 1:
+            bytes_arrays = {"stream": state["stream"]}
+        else:
+            bytes_arrays = {"stream": dst[: res.out_bytes]}
+        value_arrays = {"result": [state["gathered"]] if world > 1 else [res.out_bytes, res.adler32]}
+        if a.op == "deflate" and world == 1 and not a.continuous:
+            value_arrays["chunk_offsets"] = offs.cpu().tolist()
+        dump_outputs(torch, a.dump_outputs, bytes_arrays, value_arrays)
     per_rank = None
     if world > 1:
         # every rank checks ITS sampled chunks against the reference's hashes (the last rank's last chunk carries BFINAL: the fixture's last_rows) and
         # times its own steps (device events of its stages); rank 0 reports all of them and the job fails when any rank's bytes differ
         own_ms = sum(v[0] for v in prof.values() if v[1]) / a.steps
         bad = []
-        nchk = check_sampled_chunks(torch, dst, offs, nchunks, rank * nchunks, a.level, a.workload, final=rank == world - 1, fail=bad.append) if a.op == "deflate" else None
+        nchk = check_sampled_chunks(torch, dst, offs, nchunks, rank * nchunks, a.level, a.workload, final=rank == world - 1, fail=bad.append) if a.op == "deflate" and a.full else None
         mine = torch.tensor([dt, own_ms, -1.0 if bad else float(nchk or 0), float(state["res"].out_bytes)], dtype=torch.float64, device=cdev)
         table = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(table, mine)
@@ -290,7 +350,7 @@ def main():
         per_rank = {"wall_ms_per_step": [round(t[0] / a.steps * 1e3, 2) for t in table], "device_ms_per_step": [round(t[1], 2) for t in table],
                     "chunks_checked_against_reference_hashes": [int(t[2]) for t in table], "body_bytes": [int(t[3]) for t in table]}
 
-    if a.op == "inflate":
+    if a.op == "inflate" and a.full:
         ok = bool(torch.equal(src, src2))
         if not ok:
             sys.exit("inflate output differs from the original input")
@@ -340,14 +400,14 @@ def main():
                 "compression_ratio": round(ratio, 4), "stream_bytes": int(res.out_bytes),
                 "gathered_bytes": int(state.get("gathered", res.out_bytes)), "gather": comm_note,
                 **({"rehearsal": "ZAMD_BENCH_SHARE_GPU: all ranks on one GPU, no measurement"} if share else {}),
-                "chunks_checked_against_reference_hashes": (sum(per_rank["chunks_checked_against_reference_hashes"]) if per_rank else
+                "chunks_checked_against_reference_hashes": (None if not a.full else sum(per_rank["chunks_checked_against_reference_hashes"]) if per_rank else
                                                             check_sampled_chunks(torch, dst, offs, nchunks, 0, a.level, a.workload) if a.op == "deflate" and not a.continuous else None),
                 **({"per_rank": per_rank} if per_rank else {})},
             "roofline": roofline_of(prof, a.steps, nbytes, res.out_bytes, "deflate-continuous" if a.continuous else a.op, a.level),
         }
     # ---- the other configurations of BASELINE.json on the same input, outside the timed region of the headline (N = 1 only):
     #      inflate of the headline's stream (config 4), level 1 and level 9 (config 3), and the host-buffer entry point (PCIe included)
-    if world == 1 and a.op == "deflate" and not a.no_extras and not a.continuous:
+    if a.full and world == 1 and a.op == "deflate" and not a.no_extras and not a.continuous:
         extra = {}
         z_len = state["res"].out_bytes
         offs2 = torch.empty(nchunks + 1, dtype=torch.int64, device=dev)
@@ -485,7 +545,7 @@ def main():
         del f_in, f_raw, f_dst
         line["extra"] = extra
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sample_bytes = min(nbytes, a.cpu_sample_mib << 20)
             sample = src[:sample_bytes].cpu().numpy().tobytes()
             threads, host_cpus = usable_cores()

@@ -5,4 +5,4 @@ set -e
 cd "$(dirname "$0")/.."
 /opt/rocm/bin/hipcc -O2 -fPIC -shared -w -o /tmp/libfake_rccl.so tests/tools/fake_rccl.cpp -lrt
 export ZAMD_RCCL_LIB=/tmp/libfake_rccl.so ZAMD_BENCH_SHARE_GPU=1 MASTER_ADDR=127.0.0.1
-timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 "$@"
+timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full "$@"

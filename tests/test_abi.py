@@ -68,28 +68,17 @@ def test_host_library_exports_and_fails_loudly_without_gpu():
         assert rc == Z.Z_MEM_ERROR
 
 
-def test_client_compiled_against_reference_header_links_with_host_library(tmp_path):
-    """Drop-in check: a C client built with the REFERENCE's zlib.h (when the mount is present) runs against libzamd_z.so."""
+def test_client_compiled_against_reference_header_links_with_host_library():
+    """Drop-in check: a C client built with the REFERENCE's zlib.h (oracle/abi_client.c, compiled by oracle/Makefile when the reference was there
+    at build time) runs against libzamd_z.so."""
     import subprocess
     import pytest
-    ref_h = "/root/reference/h/zlib.h"
-    if not os.path.exists(ref_h):
-        pytest.skip("reference header not mounted here")
-    src = tmp_path / "client.c"
-    src.write_text('''#include "zlib.h"
-#include <stdio.h>
-int main(void) {
-    z_stream s; s.zalloc = 0; s.zfree = 0; s.opaque = 0;
-    printf("%s %d %lu ", zlibVersion(), (int)sizeof(z_stream), compressBound(65536));
-    int rc = deflateInit(&s, 6);
-    printf("%d %s\\n", rc, rc == Z_OK ? "ok" : (s.msg ? s.msg : zError(rc)));
-    if (rc == Z_OK) deflateEnd(&s);
-    return 0; }''')
-    exe = tmp_path / "client"
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libzref.so")):
+        pytest.skip("oracle/_ref was not built (no reference mount at build time)")
+    exe = os.path.join(ROOT, "oracle", "_ref", "client_zamd")
+    assert os.path.exists(exe), "oracle/Makefile built the reference but could not link client_zamd with the product"
     libdir = os.path.join(ROOT, "zlib_amd")
-    subprocess.check_call(["gcc", "-std=gnu89", "-w", "-I/root/reference/h", str(src), "-o", str(exe), "-L" + libdir, "-lzamd_z", "-lzamd_gpu",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"])
-    out = subprocess.check_output([str(exe)], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib")).decode()
+    out = subprocess.check_output([exe], env=dict(os.environ, LD_LIBRARY_PATH=libdir + ":/opt/rocm/lib")).decode()
     assert out.startswith("1.2.3 112 "), out
 
 
@@ -116,18 +105,19 @@ def test_host_library_exports_the_whole_api_of_the_reference():
         assert ref - have <= internals, sorted(ref - have - internals)
 
 
-def test_reference_example_links_with_host_library(tmp_path):
-    """The judge's link line: the reference's own example.c, unmodified, against libzamd_z.so + libzamd_gpu.so."""
+def test_reference_example_links_with_host_library():
+    """The judge's link line: the reference's own example.c, unmodified, against libzamd_z.so + libzamd_gpu.so (oracle/Makefile links it as
+    oracle/_ref/example_zamd when the reference was there at build time)."""
     import subprocess
     import pytest
-    ex = "/root/reference/qcsrc/example.c"
-    if not os.path.exists(ex):
-        pytest.skip("reference not mounted here")
-    libdir = os.path.join(ROOT, "zlib_amd")
-    exe = tmp_path / "example"
-    subprocess.check_call(["gcc", "-std=gnu89", "-w", "-I/root/reference/h", ex, "-o", str(exe), "-L" + libdir, "-lzamd_z", "-lzamd_gpu",
-                           "-Wl,-rpath," + libdir])
-    assert exe.exists()
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libzref.so")):
+        pytest.skip("oracle/_ref was not built (no reference mount at build time)")
+    exe = os.path.join(ROOT, "oracle", "_ref", "example_zamd")
+    assert os.path.exists(exe), "oracle/Makefile built the reference but could not link example_zamd with the product"
+    dyn = subprocess.check_output(["readelf", "-d", exe]).decode()
+    needed = re.findall(r"\(NEEDED\)\s+Shared library: \[([^\]]+)\]", dyn)
+    assert "libzamd_z.so" in needed, needed
+    assert "libz.so.1" not in needed, needed
 
 
 def test_host_library_exports_the_zip_entry_points():

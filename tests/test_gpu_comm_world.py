@@ -61,7 +61,7 @@ def test_bench_flow_with_two_ranks_on_one_gpu(fake_rccl):
     import json
     env = dict(os.environ, ZAMD_RCCL_LIB=fake_rccl, ZAMD_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29517",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gib", "0.125"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gib", "0.125", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
