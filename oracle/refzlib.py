@@ -311,3 +311,24 @@ def deflate_calls(data: bytes, level: int, calls=(), wbits: int = -15, strategy:
     n = s.total_out
     L.deflateEnd(C.byref(s))
     return out.raw[:n]
+
+
+def inflate_raw_dict(data: bytes, outcap: int, dictionary: bytes = b""):
+    """Raw inflate (windowBits=-15) of a whole buffer behind a preset dictionary (inflateSetDictionary before the first call; a raw
+    stream takes one at any time, inflate.c:1200-1236); returns (rc, bytes, consumed, msg)."""
+    L = lib()
+    L.inflateSetDictionary.argtypes = [C.POINTER(ZStream), C.c_char_p, C.c_uint]
+    s = ZStream()
+    rc = L.inflateInit2_(C.byref(s), -15, b"1.2.3", C.sizeof(ZStream))
+    assert rc == Z_OK
+    if dictionary:
+        rc = L.inflateSetDictionary(C.byref(s), dictionary, len(dictionary))
+        assert rc == Z_OK, rc
+    out = C.create_string_buffer(max(outcap, 1))
+    inb = C.create_string_buffer(data, max(len(data), 1))
+    s.next_in = C.addressof(inb); s.avail_in = len(data)
+    s.next_out = C.addressof(out); s.avail_out = outcap
+    rc = L.inflate(C.byref(s), Z_FINISH)
+    res = (rc, out.raw[:s.total_out], s.total_in, s.msg.decode() if s.msg else None)
+    L.inflateEnd(C.byref(s))
+    return res

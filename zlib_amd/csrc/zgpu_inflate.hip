@@ -475,6 +475,8 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
     const uint32_t role = uni(threadIdx.x >> 6); // 0 reader, 1 writer
     if (c >= nchunks) return;
     const uint64_t gc = chunk0 + c;
+    const uint32_t start_bits = stream_mode >> 8; // (a whole-stream call: the stream begins at that bit of its first byte)
+    stream_mode &= 255u;
     uint64_t seg_lo = offsets[gc], seg_hi = offsets[gc + 1];
     uint32_t bit_lead = 0, stop_bits = 0xFFFFFFFFu; // SPEC: bits of the first byte in front of the start; where the next segment starts, in bits from seg_lo
     bool bad_table;
@@ -491,6 +493,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
         // the table may arrive next to the data from anywhere: an entry that does not lie inside the input, runs backwards or is longer than
         // a 32-bit bit count can express is an error of that segment, decoded as an empty one (nothing outside the input is ever read)
         bad_table = seg_lo > seg_hi || seg_hi > in_bytes || seg_hi - seg_lo >= (1ull << 29);
+        bit_lead = start_bits;
     }
     if (bad_table) { seg_lo = 0; seg_hi = 0; }
     const bool must_be_final = !SPEC && gc == last_chunk;
@@ -562,7 +565,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
         prime(b, L.stage);
         refill(b, L.stage); refill(b, L.stage);
         drop(b, lead * 8);
-        if (SPEC) drop(b, bit_lead);
+        drop(b, bit_lead);
         auto reposition = [&](uint32_t pos) { // the scalar reader at bit `pos` of the staged dwords
             b.rd = pos >> 5; b.hold = 0; b.bits = 0;
             prime(b, L.stage); refill(b, L.stage); refill(b, L.stage);
@@ -1102,6 +1105,10 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
                 uint8_t *d_out, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode, const uint64_t *h_offsets, bool open_end,
                 uint8_t *h_dst, uint64_t h_cap)
 {
+    // stream_mode bits 8-10: the one segment of a whole-stream call begins at that bit of its first byte (inflate_stream_host's decoder of a stream
+    // taken up at a bit offset); only the decoding kernels see them
+    const uint32_t kern_mode = chunk_size == kWholeStream ? stream_mode : (stream_mode & 255u);
+    stream_mode &= 255u;
     const uint64_t host_cap = h_dst ? (h_cap < out_cap ? h_cap : out_cap) : 0;
     const uint64_t last_chunk = open_end ? ~0ull : nchunks - 1;
     if (!e || !res || !d_in || !d_out || !d_offsets || nchunks == 0 || (chunk_size > kChunkMax && !(chunk_size == kWholeStream && nchunks == 1)) ||
@@ -1152,13 +1159,13 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
         const uint32_t nb = (uint32_t)(nchunks - c0 < batch ? nchunks - c0 : batch);
         if (ring_here == 8)
             hipLaunchKernelGGL((inflate_kernel_t<false, 8192>), dim3(nb), dim3(128), sizeof(InflateLdsT<uint8_t, 8192>), st, d_in, in_bytes, d_offsets, c0, nb, last_chunk, chunk_size,
-                               d_out, out_cap, status, nullptr, engine_inflate_dict(e), 0u, stream_mode, SpecArgs{});
+                               d_out, out_cap, status, nullptr, engine_inflate_dict(e), 0u, kern_mode, SpecArgs{});
         else if (ring_here == 16)
             hipLaunchKernelGGL((inflate_kernel_t<false, 16384>), dim3(nb), dim3(128), sizeof(InflateLdsT<uint8_t, 16384>), st, d_in, in_bytes, d_offsets, c0, nb, last_chunk, chunk_size,
-                               d_out, out_cap, status, nullptr, engine_inflate_dict(e), 0u, stream_mode, SpecArgs{});
+                               d_out, out_cap, status, nullptr, engine_inflate_dict(e), 0u, kern_mode, SpecArgs{});
         else
         hipLaunchKernelGGL(inflate_kernel_t<false>, dim3(nb), dim3(128), sizeof(InflateLds), st, d_in, in_bytes, d_offsets, c0, nb, last_chunk, chunk_size,
-                           compact ? slots : d_out, out_cap, status, compact ? meta : nullptr, engine_inflate_dict(e), engine_inflate_dict_len(e), stream_mode, SpecArgs{});
+                           compact ? slots : d_out, out_cap, status, compact ? meta : nullptr, engine_inflate_dict(e), engine_inflate_dict_len(e), kern_mode, SpecArgs{});
         hipLaunchKernelGGL(inflate_reduce_kernel, dim3(1), dim3(1024), 0, st, status, nb, c0, chunk_size, acc, stream_mode, last_chunk, compact ? meta : nullptr, (uint32_t)kMsgTruncated);
         if (compact) {
             launch_scan(meta, nb, c0, oscr, engine_run_state(e), out_cap, st); // out_bytes -> byte offsets, continuing across batches
@@ -1835,7 +1842,7 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
     hipStream_t st = engine_stream(e);
     const uint32_t stream_mode = (flags & ZGPU_INF_STREAM) ? 1u : 0u;
     if (start_bit) { // the stream goes on inside its first byte (behind the last whole piece of an earlier call): the pieces are the decoder that starts at a bit
-        int rc0 = engine_ensure_stage(e, in_bytes + 256, out_cap ? out_cap : 1);
+        int rc0 = engine_ensure_stage(e, in_bytes + 256, out_cap ? out_cap : 1); // (the input, then the offsets of the fallback below)
         if (rc0) return rc0;
         uint8_t *d_in0 = engine_stage_in(e);
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_in0, in, in_bytes, hipMemcpyHostToDevice, st));
@@ -1843,20 +1850,21 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
         const int src = getenv("ZGPU_SPEC_DECLINE_AT_BIT") ? 1 : inflate_spec_run(e, d_in0, static_cast<const uint8_t *>(in), in_bytes, engine_stage_out(e), out_cap, res, st, stream_mode, start_bit, true);
         if (src == ZGPU_OK) { if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, engine_stage_out(e), res->out_bytes, hipMemcpyDeviceToHost)); return ZGPU_OK; }
         if (src != 1) return src;
-        // the pieces do not chain: damage, most likely.  The verdict is the one-workgroup decoder's, on a copy of the stream that starts at bit 0
-        std::vector<uint8_t> sh(in_bytes);
-        const uint8_t *p0 = static_cast<const uint8_t *>(in);
-        for (uint64_t i = 0; i < in_bytes; i++) sh[i] = (uint8_t)((p0[i] >> start_bit) | ((i + 1 < in_bytes ? p0[i + 1] : 0) << (8 - start_bit)));
-        zgpu_inflate_result r2;
-        t_end_bits = 0;
-        const int rc2 = inflate_stream_host(e, sh.data(), in_bytes, flags, out, out_cap, &r2, nullptr, 0);
-        if (rc2 != ZGPU_OK) { *res = r2; return rc2; }
-        if (r2.incomplete && !r2.out_bytes) { *res = r2; res->in_used = 0; res->in_used_bits = start_bit; return ZGPU_OK; } // (not all there yet: nothing taken)
-        // The shifted copy decoded (the pieces had said "not this way" for a harmless reason: no scratch room, too many repairs of the chain -- stored blocks
-        // full of what reads as headers --, a flag of the resolve pass): its result stands, with the positions mapped back to the caller's bytes
-        *res = r2;
-        if (r2.stream_end) { const uint64_t bits = (r2.in_used ? (r2.in_used - 1) * 8 + (t_end_bits ? t_end_bits : 8u) : 0) + start_bit; res->in_used = (bits + 7) >> 3; res->in_used_bits = 0; }
-        else { const uint64_t bits = r2.in_used * 8 + r2.in_used_bits + start_bit; res->in_used = bits >> 3; res->in_used_bits = (uint32_t)(bits & 7u); }
+        // The pieces do not chain: damage, most likely, or a harmless reason (no scratch room, too many repairs of the chain -- stored blocks full of
+        // what reads as headers --, a flag of the resolve pass).  The verdict is the one-workgroup decoder's, started at the same bit of the same bytes.
+        // (Not on a copy shifted to bit 0: a stored block aligns to the bytes of the stream, and in the shifted copy it read its LEN from the wrong bits.)
+        if (in_bytes >= (1ull << 29)) return engine_fail(e, ZGPU_DATA_ERROR, "stream too long for the one-workgroup decoder");
+        const uint64_t h_offs[2] = {0, in_bytes};
+        uint64_t *d_offs0 = reinterpret_cast<uint64_t *>(d_in0 + ((in_bytes + 127) & ~63ull));
+        ZGPU_HIP_CHECK(hipMemcpyAsync(d_offs0, h_offs, sizeof h_offs, hipMemcpyHostToDevice, st));
+        g_whole_done++;
+        const int rc2 = inflate_run(e, d_in0, in_bytes, d_offs0, 1, kWholeStream, engine_stage_out(e), out_cap, res, st, stream_mode | (start_bit << 8), h_offs);
+        // stream mode: input that stops inside a block is not an error, nothing of it is taken (the stream still goes on at start_bit)
+        if (stream_mode && ((rc2 == ZGPU_DATA_ERROR && res->error_msg == kMsgTruncated) || (rc2 == ZGPU_OK && res->incomplete))) {
+            res->incomplete = 1; res->in_used = 0; res->in_used_bits = start_bit; res->out_bytes = 0; res->stream_end = 0; return ZGPU_OK;
+        }
+        if (rc2 != ZGPU_OK) return rc2;
+        if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, engine_stage_out(e), res->out_bytes, hipMemcpyDeviceToHost));
         return ZGPU_OK;
     }
     const uint64_t max_cand = in_bytes / 5 + 2;
