@@ -1,0 +1,33 @@
+/* zamd_batch.h -- many small independent streams in one call, zlib style (libzamd_z.so).
+ *
+ * Item k is source[k] (sourceLen[k] bytes) into dest[k] (room destLen[k]); every item is a stream of its own and gets its own verdict in
+ * status[k], the code compress2() / uncompress() of this library return for that item alone.  The return value is Z_OK when every item
+ * succeeded, else the code of the first item that did not (Z_STREAM_ERROR for bad arguments: then no item was touched).
+ */
+#ifndef ZAMD_BATCH_H
+#define ZAMD_BATCH_H
+#include <stddef.h>
+#include "zamd_zlib.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* windowBits 15: each item becomes what compress2(item, level) gives; 31: a gzip member as deflateInit2(level, Z_DEFLATED, 31, 8,
+ * Z_DEFAULT_STRATEGY) + deflate(Z_FINISH) gives it; -15: raw deflate the same way.  status[k]: Z_OK (destLen[k] = the stream's length) or
+ * Z_BUF_ERROR when destLen[k] is too small (destLen[k] unchanged).  Items of at most 64 KiB at levels 1-9 are compressed together in one
+ * launch of the engine (zgpu_deflate_segments_host); level 0 and larger items are served one by one through compress2() / deflateInit2(),
+ * which handle any size. */
+int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int level,
+                         int windowBits, int *status);
+
+/* windowBits 15 zlib, 31 gzip, 47 either (by the magic), -15 raw deflate.  status[k] as uncompress() (qcsrc/uncompr.c:50-56) gives it:
+ * Z_OK (destLen[k] = the decoded size), Z_BUF_ERROR when destLen[k] is too small, Z_DATA_ERROR for a damaged or truncated stream and for one
+ * that needs a preset dictionary.  Items of 512 MiB of input or more are served one by one. */
+int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits,
+                          int *status);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

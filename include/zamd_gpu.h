@@ -198,13 +198,19 @@ int zgpu_deflate_cont_host(zgpu_engine *e, const void *hist, uint64_t hist_bytes
 /* Batch of independent small buffers: segment k = in[seg_offsets[k] .. seg_offsets[k+1]), each at most
  * 65536 bytes, becomes one chunk.  With ZGPU_F_FINAL every segment is a complete raw-deflate stream of its
  * own (Z_FINISH); without it every segment ends with the full-flush marker.  ZGPU_F_POS0_ALL applies to all
- * segments; ZGPU_F_ZLIB_WRAP is not allowed.  out_offsets (optional) receives nseg+1 output offsets. */
+ * segments.  With ZGPU_F_FINAL, ZGPU_F_ZLIB_WRAP or ZGPU_F_GZIP_WRAP makes every segment one complete zlib stream (what
+ * compress2() of the segment emits) or one gzip member (the header deflate() writes, qcsrc/deflate.c:578-596, and its own
+ * CRC-32 / ISIZE); out_offsets then marks where each stream begins.  out_offsets (optional) receives nseg+1 output offsets. */
 int zgpu_deflate_segments_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets,
                                  uint64_t nseg, const zgpu_deflate_params *p, void *d_out, uint64_t out_cap,
                                  uint64_t *d_out_offsets, zgpu_deflate_result *res, void *hip_stream);
 int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *seg_offsets, uint64_t nseg,
                                const zgpu_deflate_params *p, void *out, uint64_t out_cap, uint64_t *out_offsets,
                                zgpu_deflate_result *res);
+
+/* Output capacity that is enough for zgpu_deflate_segments_* of nseg segments holding in_bytes in all (flags: the wrapper asked for), on an
+ * engine with the default geometry (windowBits 15, memLevel 8; zgpu_deflate_set_geometry); the host entry sizes its own staging in any case. */
+uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t flags);
 
 /* One chunk with a preset dictionary (deflateSetDictionary, qcsrc/deflate.c:315-354).  `window` holds the dictionary bytes the
  * reference copies into its window -- the last min(length, 32506) bytes of the dictionary, at least 3 -- followed by the data;
@@ -277,6 +283,40 @@ int zgpu_inflate_set_dictionary(zgpu_engine *e, const void *dict, uint32_t len);
 #define ZGPU_CHECK_ADLER32 1u
 #define ZGPU_CHECK_CRC32 2u
 int zgpu_inflate_set_checks(zgpu_engine *e, uint32_t mask);
+
+/* ---- batch inflate: many independent streams in one call ----
+ * Item k is the stream d_in[d_in_offsets[k] .. d_in_offsets[k+1]), decoded to d_out[d_out_offsets[k] .. d_out_offsets[k+1]); every item is a
+ * stream of its own and gets its own record in d_items[k].  wrap says what the items carry, as inflateInit2's windowBits does
+ * (qcsrc/inflate.c:589-760): ZGPU_WRAP_RAW -15, ZGPU_WRAP_ZLIB 15, ZGPU_WRAP_GZIP 31, ZGPU_WRAP_AUTO 47 (zlib or gzip by the magic).  An item must
+ * reach its final block; what follows its trailer (or, raw, its final block) is left alone.  Limits per item: < 512 MiB compressed, < 4 GiB
+ * decoded (an item past them gets ZGPU_DATA_ERROR with "segment table out of range" / "segment decodes to more than chunk_size bytes").  No preset dictionary (zgpu_inflate_set_dictionary does not apply); multi-member gzip items decode their first member.
+ * Record of item k:
+ *   code       ZGPU_OK, ZGPU_DATA_ERROR, ZGPU_BUF_ERROR (out_bytes = the size that would have been needed) or 2 (Z_NEED_DICT: FDICT set)
+ *   msg        index for zgpu_inflate_message() (the reference's text for a header or trailer failure)
+ *   out_bytes  decoded size
+ *   in_used    input bytes up to the end of the trailer (raw: of the final block)
+ *   adler32 / crc32  of the decoded bytes: checks takes ZGPU_CHECK_* bits; the check the wrapper needs is always computed (AUTO: both); a check
+ *              that is not computed reads adler32 = 1 / crc32 = 0.
+ * The call fails only for bad arguments (offsets that run backwards or leave their buffer), allocation or HIP errors; *nfailed (optional)
+ * receives the number of items whose code is not ZGPU_OK.  The device entry blocks until the records are in d_items. */
+#define ZGPU_WRAP_RAW 0
+#define ZGPU_WRAP_ZLIB 1
+#define ZGPU_WRAP_GZIP 2
+#define ZGPU_WRAP_AUTO 3
+typedef struct {
+    int32_t code;
+    uint32_t msg;
+    uint64_t out_bytes;
+    uint64_t in_used;
+    uint32_t adler32, crc32;
+} zgpu_inflate_item;
+int zgpu_inflate_batch_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                              uint32_t checks, void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_inflate_item *d_items,
+                              uint64_t *nfailed, void *hip_stream);
+/* The same with host arrays.  Only the decoded bytes of the items that succeed are written to out. */
+int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,
+                            uint32_t checks, void *out, uint64_t out_cap, const uint64_t *out_offsets, zgpu_inflate_item *items,
+                            uint64_t *nfailed);
 
 /* ---- checksums (qcsrc/adler32.c:57-149) ---- */
 int zgpu_adler32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *adler_out, void *hip_stream);

@@ -41,6 +41,29 @@ inline LevelCfg level_cfg(int level)
 }
 
 // Per-chunk record passed between the LZ77 stage, the Huffman stage and the stitcher.
+// inflate verdicts: index into zgpu_inflate_message() (zgpu_inflate.hip, kInfMessages); the wrapper messages of the batch decoder are the reference's
+// (qcsrc/inflate.c:610-730, 1092, 1105)
+enum InfMsg : uint32_t {
+    kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLens, kMsgRepeat, kMsgLitLens, kMsgDists, kMsgLitCode, kMsgDistCode,
+    kMsgTooFar, kMsgTruncated, kMsgOutput, kMsgTrailing, kMsgShort, kMsgTable,
+    kMsgHeaderCheck, kMsgMethod, kMsgWindow, kMsgHeaderFlags, kMsgHeaderCrc, kMsgDataCheck, kMsgLengthCheck, kMsgCount
+};
+
+// Batch inflate (zgpu_inflate_batch_*): item k = an independent stream in[in_lo, in_hi) decoded to out[out_lo, out_hi).  The header kernel fills
+// in what the wrapper says, the decoder's verdict is merged in behind it, the checks of the decoded bytes come from 64 KiB pieces of the output.
+constexpr uint32_t kWrapRaw = 0, kWrapZlib = 1, kWrapGzip = 2, kWrapAuto = 3;
+struct BatchItemState {
+    uint64_t in_lo, in_hi, body_lo, out_lo;
+    uint64_t piece0;             // first of the item's pieces in the piece list (exclusive scan of npieces)
+    uint32_t kind;               // kWrapRaw / kWrapZlib / kWrapGzip (AUTO resolved by the magic)
+    int32_t code;                // header verdict first, then the decoder's
+    uint32_t msg, used;          // used: body bytes up to the end of the final block
+    uint32_t out_bytes, npieces;
+};
+
+// the header every segment of a wrapped segment call starts with (zgpu_stitch.hip, frame_kernel)
+struct FrameHead { uint8_t b[10]; uint8_t n, gzip; };
+
 struct ChunkMeta {
     uint32_t ntok;        // tokens produced by the LZ77 stage
     uint32_t nostore;     // bit b set: block b may not be emitted stored (reference: buf == NULL after the slide); kFullFinalBlock: see there

@@ -20,6 +20,8 @@ void launch_huffman(const ChunkGeom &g, const uint32_t *tokens, ChunkMeta *meta,
 void launch_adler(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
 void launch_crc(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
 void launch_scan(const ChunkMeta *meta, uint32_t nchunks, uint64_t chunk0, uint64_t *offsets, void *run, uint64_t out_cap, hipStream_t st, bool with_crc = false);
+void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets, const uint64_t *seg_off, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
+                  uint64_t out_cap, uint32_t slot_stride, void *run, bool with_crc, const FrameHead &h, hipStream_t st);
 void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
                    uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
 void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st);
@@ -303,7 +305,8 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     if (geo) impl = ZGPU_LZ_SERIAL;
     const bool serial = impl == ZGPU_LZ_SERIAL;
     hand_on = hand_on && serial && !geo && p->lz_impl == ZGPU_LZ_AUTO;
-    if (d_seg && ((p->flags & (ZGPU_F_ZLIB_WRAP | ZGPU_F_GZIP_WRAP)) || nseg == 0)) return fail(e, ZGPU_STREAM_ERROR, "segment mode: no zlib wrapper, nseg >= 1");
+    if (d_seg && (nseg == 0 || ((p->flags & (ZGPU_F_ZLIB_WRAP | ZGPU_F_GZIP_WRAP)) && (!(p->flags & ZGPU_F_FINAL) || ((p->flags & ZGPU_F_ZLIB_WRAP) && (p->flags & ZGPU_F_GZIP_WRAP))))))
+        return fail(e, ZGPU_STREAM_ERROR, "segment mode: nseg >= 1, a wrapper needs FINAL (one of zlib / gzip)");
     const uint64_t nchunks = d_seg ? nseg : (in_bytes ? (in_bytes + chunk_size - 1) / chunk_size : 1);
     // One batch = one launch of every stage.  The lane-per-chunk stages (serial LZ77, parse) need tens of thousands of
     // chunks in flight to fill 256 CUs, so batches are as large as device memory allows (~1 MiB of workspace per chunk).
@@ -342,7 +345,16 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
         }
     }
     const bool wrap = p->flags & ZGPU_F_ZLIB_WRAP, gz = p->flags & ZGPU_F_GZIP_WRAP;
-    const uint32_t head_bytes = wrap ? 2 : gz ? 10 : 0, tail_bytes = wrap ? 4 : gz ? 8 : 0;
+    // segments with a wrapper: every segment is a stream of its own, framed by launch_frame; the call itself has no header or trailer
+    const bool seg_wrap = d_seg && (wrap || gz);
+    const uint32_t head_bytes = seg_wrap ? 0 : wrap ? 2 : gz ? 10 : 0, tail_bytes = seg_wrap ? 0 : wrap ? 4 : gz ? 8 : 0;
+    FrameHead fh{};
+    if (wrap) { zlib_header(p->level, p->strategy, fh.b); fh.n = 2; }
+    if (gz) { // the header deflate() writes when no gz_header was set (qcsrc/deflate.c:578-596); OS_CODE 3 as the reference builds here
+        const uint8_t hdr[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)(p->level == 9 ? 2 : (p->strategy >= 2 || p->level < 2) ? 4 : 0), 3};
+        for (int i = 0; i < 10; i++) fh.b[i] = hdr[i];
+        fh.n = 10; fh.gzip = 1;
+    }
     ChunkGeom g{};
     g.in = d_in; g.in_bytes = in_bytes; g.seg_off = d_seg; g.chunk_size = chunk_size;
     g.final_chunk = (!d_seg && (p->flags & ZGPU_F_FINAL)) ? nchunks - 1 : ~0ull;
@@ -361,11 +373,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     const bool check_sort = (impl == ZGPU_LZ_SORTED || impl == ZGPU_LZ_WALK || impl == ZGPU_LZ_FAST || impl == ZGPU_LZ_FASTWIN || hand_on) && !e->exact_sort;
     uint32_t sort_fault = 0;
     if (check_sort) ZGPU_HIP_CHECK(hipMemsetAsync(lz_sorted_fault_word(e->par_ws), 0, 4, st));
-    if (wrap && out_cap >= 2) { uint8_t hdr[2]; zlib_header(p->level, p->strategy, hdr); ZGPU_HIP_CHECK(hipMemcpyAsync(d_out, hdr, 2, hipMemcpyHostToDevice, st)); }
-    if (gz && out_cap >= 10) { // the header deflate() writes when no gz_header was set (qcsrc/deflate.c:578-596); OS_CODE 3 as the reference builds here
-        const uint8_t hdr[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)(p->level == 9 ? 2 : (p->strategy >= 2 || p->level < 2) ? 4 : 0), 3};
-        ZGPU_HIP_CHECK(hipMemcpyAsync(d_out, hdr, 10, hipMemcpyHostToDevice, st));
-    }
+    if (!seg_wrap && head_bytes && out_cap >= head_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(d_out, fh.b, head_bytes, hipMemcpyHostToDevice, st));
 
     // h_dst: what the batches so far have produced goes to the caller's buffer while the next ones are compressed.  Copies to pageable memory
     // hold the calling thread, so they are a second thread's: it waits for batch k's event, reads the stream length behind it (pinned)
@@ -454,8 +462,11 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
             StageTimer t(e, st, ZGPU_STAGE_STITCH);
             if (!adler_done) launch_adler(g, e->meta, st); // (the sort of the default path has computed it on the way)
             if (gz || (p->flags & ZGPU_F_CRC32)) launch_crc(g, e->meta, st);
-            launch_scan(e->meta, nb, c0, e->offsets, e->run, body_cap, st, gz || (p->flags & ZGPU_F_CRC32));
-            launch_stitch(slots, e->meta, e->offsets, c0, nb, d_out, body_cap, g.slot_stride, st);
+            if (seg_wrap) launch_frame(slots, e->meta, e->offsets, d_seg, c0, nb, d_out, body_cap, g.slot_stride, e->run, gz || (p->flags & ZGPU_F_CRC32), fh, st);
+            else {
+                launch_scan(e->meta, nb, c0, e->offsets, e->run, body_cap, st, gz || (p->flags & ZGPU_F_CRC32));
+                launch_stitch(slots, e->meta, e->offsets, c0, nb, d_out, body_cap, g.slot_stride, st);
+            }
         }
         if (home) {
             hipError_t he = hipMemcpyAsync(&e->pin_tot[nbatch], e->run, sizeof(uint64_t), hipMemcpyDeviceToHost, st); // RunState::out_total
@@ -479,13 +490,13 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     }
     if (rs.overflow || (tail_bytes && out_cap < rs.out_total + tail_bytes)) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
     const uint32_t adler = rs.adler_a | (rs.adler_b << 16);
-    if (wrap) {
+    if (wrap && !seg_wrap) {
         uint8_t tr[4] = {(uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler};
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + rs.out_total, tr, 4, hipMemcpyHostToDevice, st));
         ZGPU_HIP_CHECK(hipStreamSynchronize(st));
         rs.out_total += 4;
     }
-    if (gz) { // CRC-32 and the input length mod 2^32, both little-endian (qcsrc/deflate.c:833-843)
+    if (gz && !seg_wrap) { // CRC-32 and the input length mod 2^32, both little-endian (qcsrc/deflate.c:833-843)
         const uint32_t isz = (uint32_t)in_bytes;
         uint8_t tr[8] = {(uint8_t)rs.crc, (uint8_t)(rs.crc >> 8), (uint8_t)(rs.crc >> 16), (uint8_t)(rs.crc >> 24),
                          (uint8_t)isz, (uint8_t)(isz >> 8), (uint8_t)(isz >> 16), (uint8_t)(isz >> 24)};
@@ -1145,6 +1156,12 @@ int zgpu_deflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const z
     return ZGPU_OK;
 }
 
+uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t flags)
+{
+    // raw: what zgpu_deflate_segments_host stages for the default geometry; a wrapper adds its header and trailer to every segment
+    return in_bytes + nseg * (40 + (uint64_t)((flags & ZGPU_F_GZIP_WRAP) ? 18 : (flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0)) + 16;
+}
+
 int zgpu_deflate_segments_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets, uint64_t nseg,
                                  const zgpu_deflate_params *p, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
                                  zgpu_deflate_result *res, void *hip_stream)
@@ -1166,12 +1183,13 @@ int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *s
     // (every segment may be a chunk of its own: with a non-default geometry each gets the allowance of a full chunk)
     const uint64_t bound = (e->geo_w != 15 || e->geo_m != 8) ? in_bytes + zgpu_deflate_bound_geometry(nseg * (uint64_t)kChunkMax, kChunkMax, e->geo_w, e->geo_m) - nseg * (uint64_t)kChunkMax + ((nseg * (uint64_t)kChunkMax) >> 3)
                                                              : in_bytes + nseg * 40 + 16;
-    int rc = ensure_stage(e, in_bytes + (nseg + 1) * sizeof(uint64_t) + 64, bound);
+    const uint64_t framed = bound + nseg * (uint64_t)((p->flags & ZGPU_F_GZIP_WRAP) ? 18 : (p->flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0);
+    int rc = ensure_stage(e, in_bytes + (nseg + 1) * sizeof(uint64_t) + 64, framed);
     if (rc) return rc;
     const uint64_t tab_off = (in_bytes + 63) & ~63ull; // segment table staged behind the data
     if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in, in, in_bytes, hipMemcpyHostToDevice, e->stream));
     ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in + tab_off, seg_offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-    rc = deflate_device(e, e->stage_in, in_bytes, reinterpret_cast<const uint64_t *>(e->stage_in + tab_off), nseg, p, e->stage_out, bound,
+    rc = deflate_device(e, e->stage_in, in_bytes, reinterpret_cast<const uint64_t *>(e->stage_in + tab_off), nseg, p, e->stage_out, framed,
                         nullptr, res, e->stream);
     if (rc) return rc;
     if (res->out_bytes > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");

@@ -18,6 +18,7 @@
 #include "../../include/zamd_gpu.h"
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 struct zgpu_engine;
 
@@ -35,15 +36,13 @@ void launch_scan(const ChunkMeta *meta, uint32_t nchunks, uint64_t chunk0, uint6
 void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
                    uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
 
-enum InfMsg : uint32_t {
-    kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLens, kMsgRepeat, kMsgLitLens, kMsgDists, kMsgLitCode, kMsgDistCode,
-    kMsgTooFar, kMsgTruncated, kMsgOutput, kMsgTrailing, kMsgShort, kMsgTable, kMsgCount
-};
 static const char *const kInfMessages[kMsgCount] = {
     "", "invalid block type", "invalid stored block lengths", "too many length or distance symbols", "invalid code lengths set",
     "invalid bit length repeat", "invalid literal/lengths set", "invalid distances set", "invalid literal/length code", "invalid distance code",
     "invalid distance too far back", "segment ends inside a block", "segment decodes to more than chunk_size bytes",
-    "segment holds data after its last block", "segment decodes to fewer than chunk_size bytes", "segment table out of range"};
+    "segment holds data after its last block", "segment decodes to fewer than chunk_size bytes", "segment table out of range",
+    "incorrect header check", "unknown compression method", "invalid window size", "unknown header flags set", "header crc mismatch",
+    "incorrect data check", "incorrect length check"};
 
 // bits of the last byte that belong to a stream whose final block the last decode reached (0: all eight): inflate_stream_host's fallback for a stream taken up at a bit offset maps the end back with it
 static thread_local uint32_t t_end_bits = 0;
@@ -458,7 +457,9 @@ struct SpecArgs {
 // (chunks placed directly at their offset of the destination only) lets more segments share a CU; a match that reaches farther back than RING reads its
 // source from the destination itself, where every byte older than the ring has been flushed: the lanes that hold such matches ask for their first 32 bytes
 // when their half of the token ring is handed over, all at once, and the copy takes them from registers when its turn comes.
-template <bool SPEC, uint32_t RING = ZGPU_INF_RING>
+// BATCH (zgpu_inflate_batch_*): segment gc is one independent stream, offsets[4 gc ..] = {body start, input end, output start, output end}; it must
+// reach its final block, whatever follows is its trailer (stream_mode), and it goes straight to its own range of the destination with no dictionary.
+template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false>
 __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_kernel_t(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ offsets,
                                                         uint64_t chunk0, uint32_t nchunks, uint64_t last_chunk, uint32_t chunk_size_arg,
                                                         uint8_t *__restrict__ out, uint64_t out_cap, InfStatus *status, ChunkMeta *meta,
@@ -477,7 +478,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
     const uint64_t gc = chunk0 + c;
     const uint32_t start_bits = stream_mode >> 8; // (a whole-stream call: the stream begins at that bit of its first byte)
     stream_mode &= 255u;
-    uint64_t seg_lo = offsets[gc], seg_hi = offsets[gc + 1];
+    uint64_t seg_lo = BATCH ? offsets[4 * gc] : offsets[gc], seg_hi = BATCH ? offsets[4 * gc + 1] : offsets[gc + 1];
     uint32_t bit_lead = 0, stop_bits = 0xFFFFFFFFu; // SPEC: bits of the first byte in front of the start; where the next segment starts, in bits from seg_lo
     bool bad_table;
     bool at_len = false; // SPEC: the piece starts at the LEN field of a stored block (its header bits lie in front, the piece before checks them)
@@ -496,18 +497,18 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
         bit_lead = start_bits;
     }
     if (bad_table) { seg_lo = 0; seg_hi = 0; }
-    const bool must_be_final = !SPEC && gc == last_chunk;
+    const bool must_be_final = !SPEC && (BATCH || gc == last_chunk);
     // chunk_size_arg == 0: "compact" mode, segments of any size up to 64 KiB are decoded into per-chunk slots and
     // concatenated afterwards (used for streams whose chunks are not all full, e.g. flushed mid-chunk)
     const bool compact = chunk_size_arg == 0;
     // chunk_size_arg == kWholeStream: one segment of any size (a stream that was not produced in chunks): decoded from end to
     // end by this one workgroup straight into the destination, limited only by the destination's capacity (a destination
     // that is too small still gets the size that would have been needed)
-    const bool whole = SPEC || chunk_size_arg == kWholeStream;
+    const bool whole = SPEC || BATCH || chunk_size_arg == kWholeStream;
     const uint32_t chunk_size = compact ? kChunkMax : whole ? 0xFFFF0000u : chunk_size_arg;
     // a preset dictionary (inflateSetDictionary, inflate.c:1200-1236) is what the window holds before the first byte: in the ring it
     // sits right below position 0, and the first segment may reach that much farther back
-    const uint32_t reach = (gc == 0) ? dict_len : SPEC ? kOutRing : 0u;
+    const uint32_t reach = BATCH ? 0u : (gc == 0) ? dict_len : SPEC ? kOutRing : 0u;
     if (threadIdx.x == 0) { L.abort_flag = 0; L.end_bits = 0; L.end_final = 0; }
     INF_T0();
 
@@ -772,8 +773,8 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
     for (uint32_t i = lane; i < reach; i += 64) L.out[(kOutRing - reach + i) & (kOutRing - 1)] = dict[i];
     uint32_t flushed = 0; // bytes already copied from the LDS ring to the destination (a multiple of kOutHalf until the end)
     bool nofit = false;   // direct placement: the destination ended before the chunk did
-    uint8_t *dst = compact ? out + (uint64_t)c * kChunkMax : whole ? out : out + gc * (uint64_t)chunk_size;
-    const uint64_t dst_room = SPEC ? ~0ull : compact ? kChunkMax : whole ? out_cap : (out_cap > gc * (uint64_t)chunk_size ? out_cap - gc * (uint64_t)chunk_size : 0);
+    uint8_t *dst = BATCH ? out + offsets[4 * gc + 2] : compact ? out + (uint64_t)c * kChunkMax : whole ? out : out + gc * (uint64_t)chunk_size;
+    const uint64_t dst_room = BATCH ? offsets[4 * gc + 3] - offsets[4 * gc + 2] : SPEC ? ~0ull : compact ? kChunkMax : whole ? out_cap : (out_cap > gc * (uint64_t)chunk_size ? out_cap - gc * (uint64_t)chunk_size : 0);
     // copy a match of `len` bytes at distance `dist` to output position `at`; a distance shorter than the length repeats its
     // pattern (byte-sequential semantics of inffast.c:246-259).  The ring holds the last 32 KiB: a read at the full distance
     // 32768 hits the slot its own lane is about to write.
@@ -1206,6 +1207,200 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
         ZGPU_HIP_CHECK(hipMemcpyAsync(h_dst, d_out, h[0], hipMemcpyDeviceToHost, st));
         ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     }
+    return ZGPU_OK;
+}
+} // namespace zgpu
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Batch of independent streams (zgpu_inflate_batch_*): item k = in[in_off[k], in_off[k+1]) -> out[out_off[k], out_off[k+1]), every item a stream of
+// its own with its own verdict.  The header kernel reads each item's wrapper (qcsrc/inflate.c:589-760), the decoder runs in BATCH mode (one
+// workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and the finish
+// kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.
+namespace zgpu {
+void launch_batch_finish(const BatchItemState *items, uint64_t n, const ChunkMeta *meta, const uint8_t *in, uint32_t do_adler, uint32_t do_crc,
+                         zgpu_inflate_item *out_items, unsigned long long *nfailed, hipStream_t st);
+
+__device__ inline uint32_t crc_bytes(uint32_t c, const uint8_t *p, uint64_t n) // crc32() of the reference (crc32.c:219), bit by bit: headers are short
+{
+    c = ~c;
+    for (uint64_t i = 0; i < n; i++) {
+        c ^= p[i];
+#pragma unroll
+        for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xedb88320u : c >> 1;
+    }
+    return ~c;
+}
+
+// one lane per item: the wrapper in front of the deflate data (HEAD .. HCRC / DICTID of inflate(), inflate.c:589-760, windowBits -15 / 15 / 31 / 47).
+// bad[0] |= 1: an offsets table that runs backwards or leaves its buffer (a bad argument of the call; such an item is made empty here).
+__global__ void __launch_bounds__(256) batch_header_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ in_off, uint64_t n,
+                                                           uint32_t wrap, uint64_t out_cap, const uint64_t *__restrict__ out_off, uint64_t *seg,
+                                                           BatchItemState *items, uint32_t *bad)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    uint64_t lo = in_off[k], hi = in_off[k + 1], ol = out_off[k], oh = out_off[k + 1];
+    if (lo > hi || hi > in_bytes || ol > oh || oh > out_cap) { atomicOr(bad, 1u); lo = hi = 0; ol = oh = 0; }
+    const uint8_t *p = in + lo;
+    const uint64_t len = hi - lo;
+    uint32_t kind = wrap, msg = kMsgNone;
+    int32_t code = ZGPU_OK;
+    uint64_t pos = 0;
+    if (wrap == kWrapAuto) kind = (len >= 2 && p[0] == 0x1f && p[1] == 0x8b) ? kWrapGzip : kWrapZlib;
+    auto fail = [&](uint32_t m) { if (code == ZGPU_OK) { code = ZGPU_DATA_ERROR; msg = m; } };
+    if (kind == kWrapZlib) {
+        if (len < 2) fail(kMsgTruncated);
+        else if (((uint32_t)p[0] << 8 | p[1]) % 31) fail(kMsgHeaderCheck);
+        else if ((p[0] & 15u) != 8) fail(kMsgMethod);
+        else if ((p[0] >> 4) + 8 > 15) fail(kMsgWindow);
+        else if (p[1] & 0x20) { if (len < 6) fail(kMsgTruncated); else code = 2; } // FDICT: the dictionary's Adler-32 follows, inflate() returns Z_NEED_DICT
+        pos = 2;
+    } else if (kind == kWrapGzip) {
+        if (len < 2) fail(kMsgTruncated);
+        else if (p[0] != 0x1f || p[1] != 0x8b) fail(kMsgHeaderCheck);
+        else if (len < 10) fail(kMsgTruncated);
+        else if (p[2] != 8) fail(kMsgMethod);
+        else if (p[3] & 0xe0) fail(kMsgHeaderFlags);
+        else {
+            const uint32_t flg = p[3];
+            pos = 10;
+            if (flg & 4) { // FEXTRA
+                if (pos + 2 > len) fail(kMsgTruncated);
+                else { pos += 2 + (p[pos] | (uint32_t)p[pos + 1] << 8); if (pos > len) fail(kMsgTruncated); }
+            }
+            for (uint32_t f = 8; f <= 16 && code == ZGPU_OK; f <<= 1) // FNAME, FCOMMENT: zero-terminated
+                if (flg & f) { while (pos < len && p[pos]) pos++; if (pos >= len) fail(kMsgTruncated); else pos++; }
+            if ((flg & 2) && code == ZGPU_OK) { // FHCRC: the low 16 bits of the CRC-32 of the header in front of it
+                if (pos + 2 > len) fail(kMsgTruncated);
+                else if ((crc_bytes(0, p, pos) & 0xffffu) != (p[pos] | (uint32_t)p[pos + 1] << 8)) fail(kMsgHeaderCrc);
+                pos += 2;
+            }
+        }
+    }
+    if (code != ZGPU_OK) pos = 0;
+    const uint64_t body = code == ZGPU_OK ? lo + pos : 0, end = code == ZGPU_OK ? hi : 0; // (an item whose header failed decodes as an empty segment)
+    seg[4 * k] = body; seg[4 * k + 1] = end; seg[4 * k + 2] = ol; seg[4 * k + 3] = oh;
+    BatchItemState s{};
+    s.in_lo = lo; s.in_hi = hi; s.body_lo = lo + pos; s.out_lo = ol; s.kind = kind; s.code = code; s.msg = msg;
+    items[k] = s;
+}
+
+// the decoder's verdict behind the header's; how many 64 KiB pieces of output the item's checks read
+__global__ void __launch_bounds__(256) batch_merge_kernel(const InfStatus *__restrict__ status, uint64_t n, uint32_t any_check, BatchItemState *items)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    BatchItemState s = items[k];
+    if (s.code == ZGPU_OK) {
+        const InfStatus t = status[k];
+        s.code = t.code; s.msg = t.code == ZGPU_DATA_ERROR ? t.msg : 0u; s.out_bytes = t.out_bytes; s.used = t.used & 0x7fffffffu;
+    }
+    s.npieces = (s.code == ZGPU_OK && any_check) ? (uint32_t)(((uint64_t)s.out_bytes + kChunkMax - 1) / kChunkMax) : 0u;
+    items[k].code = s.code; items[k].msg = s.msg; items[k].out_bytes = s.out_bytes; items[k].used = s.used; items[k].npieces = s.npieces;
+}
+
+// one workgroup: piece0 = exclusive scan of npieces; total[0] = all pieces
+__global__ void __launch_bounds__(1024) batch_piece_scan_kernel(BatchItemState *items, uint64_t n, unsigned long long *total)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (n + 1023) / 1024, a = tid * per < n ? tid * per : n, z = (tid + 1) * per < n ? (tid + 1) * per : n;
+    unsigned long long sum = 0;
+    for (uint64_t i = a; i < z; i++) sum += items[i].npieces;
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const unsigned long long add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    unsigned long long o = part[tid] - sum;
+    for (uint64_t i = a; i < z; i++) { items[i].piece0 = o; o += items[i].npieces; }
+    if (tid == 1023) total[0] = part[1023];
+}
+
+// the piece table: item k owns boundaries [piece0 + k, piece0 + k + npieces] (its pieces, then the gap up to the next item's range, which no
+// launch reads); map lists the pieces themselves, in item order
+__global__ void __launch_bounds__(256) batch_piece_fill_kernel(const BatchItemState *__restrict__ items, uint64_t n, uint64_t *tab, uint32_t *map)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const BatchItemState s = items[k];
+    const uint64_t base = s.piece0 + k;
+    for (uint32_t i = 0; i < s.npieces; i++) { tab[base + i] = s.out_lo + (uint64_t)i * kChunkMax; map[s.piece0 + i] = (uint32_t)(base + i); }
+    tab[base + s.npieces] = s.out_lo + s.out_bytes;
+}
+
+int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks,
+                      uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (checks & ~3u) || (n && (!d_in_off || !d_out_off || !d_items)) || (n && in_bytes && !d_in) || (n && out_cap && !d_out) ||
+        n >= (1ull << 32))
+        return engine_fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(engine_device(e)));
+    // the check each item's wrapper needs is always computed (AUTO: both), the others when asked for
+    const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
+    const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    const uint64_t max_pieces = (out_cap >> 16) + n;
+    // one scratch: segment table, item states, decoder status, the counters, the piece boundaries, the piece list, the pieces' checksums
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_seg = 0, o_items = o_seg + al(n * 32), o_status = o_items + al(n * sizeof(BatchItemState)), o_cnt = o_status + al(n * sizeof(InfStatus)),
+                 o_tab = o_cnt + 256, o_map = o_tab + al((max_pieces + n + 1) * 8), o_meta = o_map + al(max_pieces * 4), total = o_meta + al(max_pieces * sizeof(ChunkMeta));
+    uint8_t *scr = static_cast<uint8_t *>(engine_scratch(e, total));
+    if (!scr) return engine_fail(e, ZGPU_MEM_ERROR, "inflate batch scratch");
+    uint64_t *seg = reinterpret_cast<uint64_t *>(scr + o_seg);
+    BatchItemState *items = reinterpret_cast<BatchItemState *>(scr + o_items);
+    InfStatus *status = reinterpret_cast<InfStatus *>(scr + o_status);
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(scr + o_cnt); // [0] pieces, [1] failed items, [2] bad offsets
+    uint64_t *tab = reinterpret_cast<uint64_t *>(scr + o_tab);
+    uint32_t *map = reinterpret_cast<uint32_t *>(scr + o_map);
+    ChunkMeta *meta = reinterpret_cast<ChunkMeta *>(scr + o_meta);
+    ZGPU_HIP_CHECK(hipMemsetAsync(cnt, 0, 256, st));
+    const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, n, (uint32_t)wrap, out_cap, d_out_off, seg, items,
+                       reinterpret_cast<uint32_t *>(cnt + 2));
+    int ring_kb = ZGPU_INF_RING_DEFAULT_KB; // (items go straight to their place: the small rings serve them as they serve chunks)
+    if (const char *v = getenv("ZGPU_INF_RING_KB")) ring_kb = atoi(v);
+    if (ring_kb != 8 && ring_kb != 16) ring_kb = 32;
+    hipEvent_t ev{};
+    prof_span_begin(e, st, &ev);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        if (ring_kb == 8)
+            hipLaunchKernelGGL((inflate_kernel_t<false, 8192, true>), dim3(nb), dim3(128), sizeof(InflateLdsT<uint8_t, 8192>), st, d_in, in_bytes, seg, c0, nb, ~0ull,
+                               kWholeStream, d_out, out_cap, status + c0, nullptr, nullptr, 0u, 1u, SpecArgs{});
+        else if (ring_kb == 16)
+            hipLaunchKernelGGL((inflate_kernel_t<false, 16384, true>), dim3(nb), dim3(128), sizeof(InflateLdsT<uint8_t, 16384>), st, d_in, in_bytes, seg, c0, nb, ~0ull,
+                               kWholeStream, d_out, out_cap, status + c0, nullptr, nullptr, 0u, 1u, SpecArgs{});
+        else
+            hipLaunchKernelGGL((inflate_kernel_t<false, ZGPU_INF_RING, true>), dim3(nb), dim3(128), sizeof(InflateLds), st, d_in, in_bytes, seg, c0, nb, ~0ull,
+                               kWholeStream, d_out, out_cap, status + c0, nullptr, nullptr, 0u, 1u, SpecArgs{});
+    }
+    prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+    hipLaunchKernelGGL(batch_merge_kernel, dim3(ngrid), dim3(256), 0, st, status, n, do_adler | do_crc, items);
+    hipLaunchKernelGGL(batch_piece_scan_kernel, dim3(1), dim3(1024), 0, st, items, n, cnt);
+    hipLaunchKernelGGL(batch_piece_fill_kernel, dim3(ngrid), dim3(256), 0, st, items, n, tab, map);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[2]) { engine_collect(e); return engine_fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range"); }
+    if (h[0]) {
+        ChunkGeom g{}; g.in = d_out; g.in_bytes = out_cap; g.seg_off = tab; g.chunk0 = 0; g.final_chunk = ~0ull; g.chunk_size = kChunkMax;
+        g.nchunks = (uint32_t)h[0]; g.chunk_map = map;
+        if (do_adler) launch_adler(g, meta, st);
+        if (do_crc) launch_crc(g, meta, st);
+    }
+    launch_batch_finish(items, n, meta, d_in, do_adler, do_crc, d_items, cnt + 1, st);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    engine_collect(e);
+    if (nfailed) *nfailed = h[1];
     return ZGPU_OK;
 }
 } // namespace zgpu
@@ -1991,4 +2186,60 @@ int zgpu_inflate_stream_host3(zgpu_engine *e, const void *in, uint64_t in_bytes,
     return inflate_stream_host(e, in, in_bytes, flags, out, out_cap, res, nullptr, start_bit);
 }
 #pragma GCC visibility pop
+}
+
+extern "C" {
+__attribute__((visibility("default")))
+int zgpu_inflate_batch_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks,
+                              void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : engine_stream(e);
+    return inflate_batch_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, checks, static_cast<uint8_t *>(d_out), out_cap,
+                             d_out_offsets, d_items, nfailed, st);
+}
+
+// host arrays: input, both offset tables and the records staged in the engine's buffers; the decoded range comes back in one copy and each item
+// that succeeded is placed from there (the bytes of the others -- and any room an item did not fill -- stay as the caller left them)
+__attribute__((visibility("default")))
+int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, uint32_t checks,
+                            void *out, uint64_t out_cap, const uint64_t *out_offsets, zgpu_inflate_item *items, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (n && (!in_offsets || !out_offsets || !items || (in_bytes && !in) || (out_cap && !out))) return engine_fail(e, ZGPU_STREAM_ERROR, "null argument");
+    if (n == 0) return ZGPU_OK;
+    for (uint64_t k = 0; k < n; k++)
+        if (in_offsets[k] > in_offsets[k + 1] || in_offsets[k + 1] > in_bytes || out_offsets[k] > out_offsets[k + 1] || out_offsets[k + 1] > out_cap)
+            return engine_fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    ZGPU_HIP_CHECK(hipSetDevice(engine_device(e)));
+    const uint64_t o_tab = (in_bytes + 255) & ~255ull, tab_bytes = (n + 1) * sizeof(uint64_t);
+    const uint64_t o_items = o_tab + 2 * ((tab_bytes + 255) & ~255ull);
+    const uint64_t lo = out_offsets[0], hi = out_offsets[n];
+    int rc = engine_ensure_stage(e, o_items + n * sizeof(zgpu_inflate_item), hi);
+    if (rc) return rc;
+    uint8_t *sin = engine_stage_in(e), *sout = engine_stage_out(e);
+    hipStream_t st = engine_stream(e);
+    uint64_t *d_in_off = reinterpret_cast<uint64_t *>(sin + o_tab), *d_out_off = reinterpret_cast<uint64_t *>(sin + o_tab + ((tab_bytes + 255) & ~255ull));
+    zgpu_inflate_item *d_items = reinterpret_cast<zgpu_inflate_item *>(sin + o_items);
+    if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(sin, in, in_bytes, hipMemcpyHostToDevice, st));
+    ZGPU_HIP_CHECK(hipMemcpyAsync(d_in_off, in_offsets, tab_bytes, hipMemcpyHostToDevice, st));
+    ZGPU_HIP_CHECK(hipMemcpyAsync(d_out_off, out_offsets, tab_bytes, hipMemcpyHostToDevice, st));
+    rc = inflate_batch_run(e, sin, in_bytes, d_in_off, n, wrap, checks, sout, hi, d_out_off, d_items, nfailed, st);
+    if (rc) return rc;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    uint8_t *o = static_cast<uint8_t *>(out);
+    bool all = true; // every item succeeded and filled its room exactly: the range goes straight to the caller
+    for (uint64_t k = 0; k < n && all; k++) all = items[k].code == ZGPU_OK && items[k].out_bytes == out_offsets[k + 1] - out_offsets[k];
+    if (all) {
+        if (hi > lo) ZGPU_HIP_CHECK(hipMemcpy(o + lo, sout + lo, hi - lo, hipMemcpyDeviceToHost));
+        return ZGPU_OK;
+    }
+    std::vector<uint8_t> tmp(hi - lo);
+    if (hi > lo) ZGPU_HIP_CHECK(hipMemcpy(tmp.data(), sout + lo, hi - lo, hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < n; k++)
+        if (items[k].code == ZGPU_OK && items[k].out_bytes) memcpy(o + out_offsets[k], tmp.data() + (out_offsets[k] - lo), items[k].out_bytes);
+    return ZGPU_OK;
+}
 }

@@ -5,6 +5,7 @@
 // stitching is a byte copy, never a bit shift.  Also hosts the corpus generator kernel used by bench.py.
 #include "zgpu_common.h"
 #include "corpus.h"
+#include "../../include/zamd_gpu.h"
 
 namespace zgpu {
 
@@ -164,9 +165,10 @@ __device__ inline void adler_join(uint32_t &ax, uint32_t &bx, uint32_t ay, uint3
     ax = (uint32_t)a; bx = (uint32_t)b;
 }
 
-// One workgroup: exclusive scan of out_bytes over the batch (continuing RunState), ordered Adler combination.
+// One workgroup: exclusive scan of out_bytes over the batch (continuing RunState), ordered Adler combination.  frame: bytes of wrapper
+// around every chunk (segments that are streams of their own: header + trailer), counted into the offsets.
 __global__ void __launch_bounds__(1024) scan_kernel(const ChunkMeta *__restrict__ meta, uint32_t nchunks, uint64_t chunk0, uint64_t *offsets,
-                                                    RunState *run, uint64_t out_cap, uint32_t with_crc)
+                                                    RunState *run, uint64_t out_cap, uint32_t with_crc, uint32_t frame)
 {
     __shared__ uint64_t part[1024];
     __shared__ uint32_t pa[1024], pb[1024];
@@ -177,7 +179,7 @@ __global__ void __launch_bounds__(1024) scan_kernel(const ChunkMeta *__restrict_
     uint64_t sum = 0, len = 0, ntok = 0; uint32_t xa = 1, xb = 0, xc = 0;
     uint32_t op_len = ~0u, op = 0; // the append operator of the last chunk length seen (chunks are the same size but for the last)
     for (uint32_t i = a; i < z; i++) {
-        sum += meta[i].out_bytes; ntok += meta[i].ntok;
+        sum += meta[i].out_bytes + frame; ntok += meta[i].ntok;
         adler_join(xa, xb, meta[i].adler_a, meta[i].adler_b, meta[i].in_bytes); len += meta[i].in_bytes;
         if (with_crc) {
             if (meta[i].in_bytes != op_len) { op_len = meta[i].in_bytes; op = crc_xpow8n(op_len); }
@@ -225,19 +227,19 @@ __global__ void __launch_bounds__(1024) scan_kernel(const ChunkMeta *__restrict_
         offsets[chunk0 + nchunks] = acc;
     }
     uint64_t o = base + incl - sum;
-    for (uint32_t i = a; i < z; i++) { offsets[chunk0 + i] = o; o += meta[i].out_bytes; }
+    for (uint32_t i = a; i < z; i++) { offsets[chunk0 + i] = o; o += meta[i].out_bytes + frame; }
 }
 
-// copy slot c to out + offsets[chunk0 + c]; 4-byte destination-aligned stores
+// copy slot c to out + offsets[chunk0 + c] + lead (frame: lead + trailer bytes the chunk's place holds as well); 4-byte destination-aligned stores
 __global__ void __launch_bounds__(256) stitch_kernel(const uint8_t *__restrict__ slots, const ChunkMeta *__restrict__ meta,
                                                      const uint64_t *__restrict__ offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
-                                                     uint64_t out_cap, uint32_t slot_stride)
+                                                     uint64_t out_cap, uint32_t slot_stride, uint32_t lead, uint32_t frame)
 {
     const uint32_t c = blockIdx.x, tid = threadIdx.x;
     if (c >= nchunks) return;
     const uint32_t n = meta[c].out_bytes;
-    const uint64_t off = offsets[chunk0 + c];
-    if (off + n > out_cap) return; // reported through RunState.overflow
+    const uint64_t off = offsets[chunk0 + c] + lead;
+    if (off - lead + frame + n > out_cap) return; // reported through RunState.overflow
     const uint8_t *src = slots + (size_t)c * slot_stride;
     uint8_t *dst = out + off;
     uint32_t head = (uint32_t)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3);
@@ -259,6 +261,51 @@ __global__ void __launch_bounds__(64) corpus_kernel(uint32_t kind, uint64_t seed
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nchunks) zc_fill_chunk(kind, seed, first_chunk + i, out + i * ZC_CHUNK);
+}
+
+// ---- batch inflate: one lane per item joins the Adler-32 / CRC-32 of its 64 KiB pieces (in order, as scan_kernel does) and checks the trailer
+// (qcsrc/inflate.c:1078-1112): zlib the big-endian Adler-32, gzip the CRC-32 and ISIZE little-endian ----
+__global__ void __launch_bounds__(256) batch_finish_kernel(const BatchItemState *__restrict__ items, uint64_t n, const ChunkMeta *__restrict__ meta,
+                                                           const uint8_t *__restrict__ in, uint32_t do_adler, uint32_t do_crc, zgpu_inflate_item *out,
+                                                           unsigned long long *nfailed)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const BatchItemState s = items[k];
+    uint32_t a = 1, b = 0, crc = 0;
+    const uint32_t op_full = do_crc && s.npieces > 1 ? crc_xpow8n(kChunkMax) : 0u;
+    for (uint32_t i = 0; i < s.npieces; i++) {
+        const ChunkMeta &m = meta[s.piece0 + i];
+        const uint32_t len = i + 1 < s.npieces ? kChunkMax : s.out_bytes - i * kChunkMax;
+        if (do_adler) adler_join(a, b, m.adler_a, m.adler_b, len);
+        if (do_crc) crc = crc_join(crc, m.crc, len == kChunkMax ? op_full : crc_xpow8n(len));
+    }
+    zgpu_inflate_item r{};
+    r.code = s.code; r.msg = s.msg; r.out_bytes = s.out_bytes;
+    r.adler32 = do_adler ? (a | (b << 16)) : 1u; r.crc32 = do_crc ? crc : 0u;
+    if (s.code == ZGPU_OK) {
+        const uint64_t end = s.body_lo + s.used, tl = s.kind == kWrapZlib ? 4 : s.kind == kWrapGzip ? 8 : 0;
+        const uint8_t *t = in + end;
+        if (end + tl > s.in_hi) { r.code = ZGPU_DATA_ERROR; r.msg = kMsgTruncated; }
+        else if (s.kind == kWrapZlib) {
+            const uint32_t want = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | t[3];
+            if (want != r.adler32) { r.code = ZGPU_DATA_ERROR; r.msg = kMsgDataCheck; }
+        } else if (s.kind == kWrapGzip) {
+            const uint32_t want = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            const uint32_t isz = t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+            if (want != r.crc32) { r.code = ZGPU_DATA_ERROR; r.msg = kMsgDataCheck; }
+            else if (isz != s.out_bytes) { r.code = ZGPU_DATA_ERROR; r.msg = kMsgLengthCheck; }
+        }
+        if (r.code == ZGPU_OK) r.in_used = end + tl - s.in_lo;
+        else r.out_bytes = 0;
+    }
+    out[k] = r;
+    if (r.code != ZGPU_OK) atomicAdd(nfailed, 1ull);
+}
+void launch_batch_finish(const BatchItemState *items, uint64_t n, const ChunkMeta *meta, const uint8_t *in, uint32_t do_adler, uint32_t do_crc,
+                         zgpu_inflate_item *out_items, unsigned long long *nfailed, hipStream_t st)
+{
+    hipLaunchKernelGGL(batch_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, items, n, meta, in, do_adler, do_crc, out_items, nfailed);
 }
 
 void launch_crc(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st)
@@ -284,12 +331,43 @@ void launch_adler(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st)
 }
 void launch_scan(const ChunkMeta *meta, uint32_t nchunks, uint64_t chunk0, uint64_t *offsets, void *run, uint64_t out_cap, hipStream_t st, bool with_crc)
 {
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, meta, nchunks, chunk0, offsets, static_cast<RunState *>(run), out_cap, with_crc ? 1u : 0u);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, meta, nchunks, chunk0, offsets, static_cast<RunState *>(run), out_cap, with_crc ? 1u : 0u, 0u);
 }
 void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
                    uint64_t out_cap, uint32_t slot_stride, hipStream_t st)
 {
-    hipLaunchKernelGGL(stitch_kernel, dim3(nchunks), dim3(256), 0, st, slots, meta, offsets, chunk0, nchunks, out, out_cap, slot_stride);
+    hipLaunchKernelGGL(stitch_kernel, dim3(nchunks), dim3(256), 0, st, slots, meta, offsets, chunk0, nchunks, out, out_cap, slot_stride, 0u, 0u);
+}
+
+// ---- segments that are streams of their own (zgpu_deflate_segments_* with a wrapper): the scan leaves room for a header and a trailer around
+// every body, the stitch places the body behind its header, and one lane per segment writes both: the zlib header and the big-endian Adler-32, or
+// the gzip header and CRC-32 / ISIZE little-endian (qcsrc/deflate.c:578-596, 625-641, 833-843) ----
+__global__ void __launch_bounds__(256) frame_kernel(const ChunkMeta *__restrict__ meta, const uint64_t *__restrict__ offsets, const uint64_t *__restrict__ seg_off,
+                                                    uint64_t chunk0, uint32_t nchunks, uint8_t *out, uint64_t out_cap, FrameHead h)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= nchunks) return;
+    const uint64_t gc = chunk0 + c, off = offsets[gc];
+    const uint32_t n = meta[c].out_bytes, tail = h.gzip ? 8u : 4u;
+    if (off + h.n + n + tail > out_cap) return; // reported through RunState.overflow
+    uint8_t *d = out + off;
+    for (uint32_t i = 0; i < h.n; i++) d[i] = h.b[i];
+    uint8_t *t = d + h.n + n;
+    if (h.gzip) {
+        const uint32_t crc = meta[c].crc, isz = (uint32_t)(seg_off[gc + 1] - seg_off[gc]);
+        for (int i = 0; i < 4; i++) { t[i] = (uint8_t)(crc >> (8 * i)); t[4 + i] = (uint8_t)(isz >> (8 * i)); }
+    } else {
+        const uint32_t adler = meta[c].adler_a | (meta[c].adler_b << 16);
+        for (int i = 0; i < 4; i++) t[i] = (uint8_t)(adler >> (24 - 8 * i));
+    }
+}
+void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets, const uint64_t *seg_off, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
+                  uint64_t out_cap, uint32_t slot_stride, void *run, bool with_crc, const FrameHead &h, hipStream_t st)
+{
+    const uint32_t frame = h.n + (h.gzip ? 8u : 4u);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, meta, nchunks, chunk0, offsets, static_cast<RunState *>(run), out_cap, with_crc ? 1u : 0u, frame);
+    hipLaunchKernelGGL(stitch_kernel, dim3(nchunks), dim3(256), 0, st, slots, meta, offsets, chunk0, nchunks, out, out_cap, slot_stride, (uint32_t)h.n, frame);
+    hipLaunchKernelGGL(frame_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, st, meta, offsets, seg_off, chunk0, nchunks, out, out_cap, h);
 }
 void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st)
 {

@@ -10,6 +10,8 @@ CONT_MORE, CONT_FLUSH, CONT_FINISH = 0, 1, 2  # zgpu_deflate_cont_host modes
 WHOLE_STREAM = 0xFFFFFFFF  # inflate chunk_size: the one segment is a complete stream of any size
 LZ_AUTO, LZ_SERIAL, LZ_PARALLEL, LZ_SORTED, LZ_WALK, LZ_FAST, LZ_FASTWIN = 0, 1, 2, 3, 4, 5, 6
 CHECK_ADLER32, CHECK_CRC32 = 1, 2  # zgpu_inflate_set_checks
+WRAP_RAW, WRAP_ZLIB, WRAP_GZIP, WRAP_AUTO = 0, 1, 2, 3  # zgpu_inflate_batch_*
+_WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP, "auto": WRAP_AUTO}
 STAGES = ["chain", "match", "parse", "lz_serial", "huffman", "stitch", "inflate"]
 CHUNK = 65536
 
@@ -40,6 +42,11 @@ class InflateResult(C.Structure):
     _fields_ = [("out_bytes", C.c_uint64), ("adler32", C.c_uint32), ("first_bad_chunk", C.c_int32),
                 ("error_code", C.c_int32), ("error_msg", C.c_uint32), ("crc32", C.c_uint32), ("in_used_bits", C.c_uint32),
                 ("in_used", C.c_uint64), ("stream_end", C.c_uint32), ("incomplete", C.c_uint32)]
+
+
+class InflateItem(C.Structure):
+    """zgpu_inflate_item: the verdict of one item of a batch inflate."""
+    _fields_ = [("code", C.c_int32), ("msg", C.c_uint32), ("out_bytes", C.c_uint64), ("in_used", C.c_uint64), ("adler32", C.c_uint32), ("crc32", C.c_uint32)]
 
 
 def library_path():
@@ -85,6 +92,10 @@ def load_library():
     L.zgpu_deflate_segments_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp]
     L.zgpu_inflate_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, C.POINTER(InflateResult), vp]
     L.zgpu_inflate_host.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, C.POINTER(InflateResult)]
+    L.zgpu_deflate_segments_bound.argtypes = [u64, u64, u32]
+    L.zgpu_deflate_segments_bound.restype = u64
+    L.zgpu_inflate_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, C.POINTER(u64), vp]
+    L.zgpu_inflate_batch_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, C.POINTER(u64)]
     L.zgpu_inflate_find_chunks_host.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64)]
     L.zgpu_inflate_stream_host2.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(InflateResult)]
     L.zgpu_inflate_stream_host3.argtypes = [vp, vp, u64, u32, u32, vp, u64, C.POINTER(InflateResult)]
@@ -235,6 +246,58 @@ class Engine:
         self.last = res
         raw = out[: res.out_bytes].tobytes()
         return [raw[int(ooffs[i]): int(ooffs[i + 1])] for i in range(len(buffers))]
+
+    def deflate_batch_host(self, buffers, level, wrap="zlib", strategy=0):
+        """Batch of independent buffers (each <= 65536 bytes) -> one complete stream per buffer, one launch: wrap "zlib" (what compress2()
+        of the buffer emits), "gzip" (a gzip member as deflate() with windowBits 31 writes it) or "raw" (windowBits -15)."""
+        import numpy as np
+        flags = F_FINAL | {"raw": 0, "zlib": F_ZLIB_WRAP, "gzip": F_GZIP_WRAP}[wrap]
+        sizes = [len(b) for b in buffers]
+        offs = np.zeros(len(buffers) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum(sizes)
+        blob = np.frombuffer(b"".join(bytes(b) for b in buffers) + b"\0", dtype=np.uint8)
+        cap = int(self.L.zgpu_deflate_segments_bound(len(buffers), int(offs[-1]), flags))
+        out = np.empty(cap, dtype=np.uint8)
+        ooffs = np.zeros(len(buffers) + 1, dtype=np.uint64)
+        p = _Params(level, 0, flags, LZ_AUTO, strategy, 0)
+        res = DeflateResult()
+        self._check(self.L.zgpu_deflate_segments_host(self.h, blob.ctypes.data, offs.ctypes.data, len(buffers), C.byref(p),
+                                                      out.ctypes.data, cap, ooffs.ctypes.data, C.byref(res)))
+        self.last = res
+        raw = out[: res.out_bytes].tobytes()
+        return [raw[int(ooffs[i]): int(ooffs[i + 1])] for i in range(len(buffers))]
+
+    def inflate_batch_host(self, streams, out_caps, wrap="zlib", checks=0):
+        """Batch of independent streams, one call (zgpu_inflate_batch_host).  out_caps: the room of each item (an int: the same for all).
+        Returns one (code, msg, data, in_used, adler32, crc32) per item; data is the decoded bytes (b"" unless code is 0)."""
+        import numpy as np
+        n = len(streams)
+        caps = [int(out_caps)] * n if isinstance(out_caps, int) else [int(c) for c in out_caps]
+        ioffs = np.zeros(n + 1, dtype=np.uint64)
+        ioffs[1:] = np.cumsum([len(s) for s in streams])
+        ooffs = np.zeros(n + 1, dtype=np.uint64)
+        ooffs[1:] = np.cumsum(caps)
+        blob = np.frombuffer(b"".join(bytes(s) for s in streams) + b"\0", dtype=np.uint8)
+        out = np.zeros(int(ooffs[-1]) + 1, dtype=np.uint8)
+        items = (InflateItem * max(n, 1))()
+        failed = C.c_uint64(0)
+        self._check(self.L.zgpu_inflate_batch_host(self.h, blob.ctypes.data, int(ioffs[-1]), ioffs.ctypes.data, n, _WRAPS[wrap], checks,
+                                                   out.ctypes.data, int(ooffs[-1]), ooffs.ctypes.data, items, C.byref(failed)))
+        self.last_failed = failed.value
+        res = []
+        for k in range(n):
+            it = items[k]
+            data = out[int(ooffs[k]): int(ooffs[k]) + it.out_bytes].tobytes() if it.code == 0 else b""
+            res.append((it.code, self.L.zgpu_inflate_message(it.msg).decode(), data, it.in_used, it.adler32, it.crc32))
+        return res
+
+    def inflate_batch_device(self, d_in, in_bytes, d_in_offsets, n, d_out, out_cap, d_out_offsets, d_items, wrap="zlib", checks=0, stream=None):
+        """Device pointers as ints (e.g. torch.Tensor.data_ptr()): in_offsets / out_offsets hold n + 1 uint64 each, d_items n records of 32 bytes
+        (zgpu_inflate_item).  Blocks until the records are written; returns the number of items that failed."""
+        failed = C.c_uint64(0)
+        self._check(self.L.zgpu_inflate_batch_device(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks,
+                                                     d_out, out_cap, d_out_offsets, d_items, C.byref(failed), stream))
+        return failed.value
 
     def deflate_device(self, d_in, n, level, d_out, out_cap, flags=F_FINAL | F_ZLIB_WRAP, chunk_size=CHUNK, lz_impl=LZ_AUTO,
                        d_offsets=None, stream=None):

@@ -1,0 +1,191 @@
+/* zamd_batch.c -- zamd_compress2_batch / zamd_uncompress_batch (include/zamd_batch.h): many small independent streams in one engine call,
+ * each with the verdict compress2() / uncompress() (qcsrc/compress.c:22-58, qcsrc/uncompr.c:26-61) give it alone.
+ *
+ * Compress: the items of at most 64 KiB at levels 1-9 go to zgpu_deflate_segments_host with ZGPU_F_FINAL and the wrapper (every segment one
+ * complete stream, byte for byte what compress2() of it emits); level 0 and larger items take the one-item path.  Uncompress: every item of
+ * less than 512 MiB of input goes to zgpu_inflate_batch_host, the per-item codes are mapped the way uncompress() maps inflate()'s.
+ * The batch calls use an engine of their own (created on first use, on the device ZAMD_DEVICE names, like the stream API's). */
+#include "../../include/zamd_batch.h"
+#include "../../include/zamd_gpu.h"
+#include <pthread.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#define EXPORT __attribute__((visibility("default")))
+#define SEG_MAX 65536u
+#define BATCH_IN_MAX (1ull << 29) /* the decoder's limit of compressed bytes per item */
+
+static pthread_mutex_t g_batch_lock = PTHREAD_MUTEX_INITIALIZER; /* one call at a time on the engine (one stream, one workspace) */
+static zgpu_engine *g_batch_engine;
+
+static zgpu_engine *batch_engine_lock(void)
+{
+    pthread_mutex_lock(&g_batch_lock);
+    if (!g_batch_engine) {
+        const char *dev = getenv("ZAMD_DEVICE");
+        if (zgpu_engine_create(dev ? atoi(dev) : 0, &g_batch_engine) != ZGPU_OK) g_batch_engine = NULL;
+    }
+    if (!g_batch_engine) pthread_mutex_unlock(&g_batch_lock);
+    return g_batch_engine;
+}
+static void batch_engine_unlock(void) { pthread_mutex_unlock(&g_batch_lock); }
+
+static int first_failure(const int *status, size_t n)
+{
+    for (size_t k = 0; k < n; k++)
+        if (status[k] != Z_OK) return status[k];
+    return Z_OK;
+}
+
+/* one item the way compress2() (windowBits 15) or deflateInit2() + deflate(Z_FINISH) serve it */
+static int compress_one(Bytef *dest, uLongf *destLen, const Bytef *src, uLong len, int level, int wbits)
+{
+    if (wbits == 15) return compress2(dest, destLen, src, len, level);
+    if (len > 0xFFFFFFFFul) return Z_STREAM_ERROR;
+    z_stream st;
+    memset(&st, 0, sizeof st);
+    int err = deflateInit2_(&st, level, Z_DEFLATED, wbits, 8, Z_DEFAULT_STRATEGY, ZLIB_VERSION, (int)sizeof st);
+    if (err != Z_OK) return err;
+    st.next_in = (Bytef *)src; st.avail_in = (uInt)len;
+    st.next_out = dest; st.avail_out = *destLen > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uInt)*destLen;
+    err = deflate(&st, Z_FINISH);
+    if (err != Z_STREAM_END) { deflateEnd(&st); return err == Z_OK ? Z_BUF_ERROR : err; }
+    *destLen = st.total_out;
+    return deflateEnd(&st);
+}
+
+/* one item the way uncompress() serves it (windowBits 15), or inflateInit2() + inflate(Z_FINISH) with uncompress()'s mapping of the codes */
+static int uncompress_one(Bytef *dest, uLongf *destLen, const Bytef *src, uLong len, int wbits)
+{
+    if (wbits == 15) return uncompress(dest, destLen, src, len);
+    if (len > 0xFFFFFFFFul || *destLen > 0xFFFFFFFFul) return Z_BUF_ERROR; /* uncompr.c:36-38 */
+    z_stream st;
+    memset(&st, 0, sizeof st);
+    st.next_in = (Bytef *)src; st.avail_in = (uInt)len;
+    st.next_out = dest; st.avail_out = (uInt)*destLen;
+    int err = inflateInit2_(&st, wbits, ZLIB_VERSION, (int)sizeof st);
+    if (err != Z_OK) return err;
+    err = inflate(&st, Z_FINISH);
+    if (err != Z_STREAM_END) {
+        const int full = st.avail_out == 0; /* (this inflate() takes all input: what ran out is the room, or the stream) */
+        inflateEnd(&st);
+        if (err == Z_NEED_DICT || (err == Z_BUF_ERROR && !full)) return Z_DATA_ERROR;
+        return err == Z_OK ? Z_BUF_ERROR : err;
+    }
+    *destLen = st.total_out;
+    return inflateEnd(&st);
+}
+
+static int engine_code(int rc) { return rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : rc == ZGPU_STREAM_ERROR ? Z_STREAM_ERROR : Z_ERRNO; }
+
+EXPORT int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int level,
+                                int windowBits, int *status)
+{
+    if (n && (!dest || !destLen || !source || !sourceLen || !status)) return Z_STREAM_ERROR;
+    if (level == Z_DEFAULT_COMPRESSION) level = 6;
+    if (level < 0 || level > 9 || (windowBits != 15 && windowBits != 31 && windowBits != -15)) return Z_STREAM_ERROR;
+    for (size_t k = 0; k < n; k++)
+        if ((!source[k] && sourceLen[k]) || !dest[k]) return Z_STREAM_ERROR;
+    uint64_t nb = 0, in_total = 0;
+    for (size_t k = 0; k < n; k++)
+        if (level > 0 && sourceLen[k] <= SEG_MAX) { nb++; in_total += sourceLen[k]; }
+    if (nb) {
+        const uint32_t flags = ZGPU_F_FINAL | (windowBits == 15 ? ZGPU_F_ZLIB_WRAP : windowBits == 31 ? ZGPU_F_GZIP_WRAP : 0u);
+        const uint64_t cap = zgpu_deflate_segments_bound(nb, in_total, flags);
+        uint8_t *in = malloc(in_total + 1), *out = malloc(cap);
+        uint64_t *seg = malloc((nb + 1) * sizeof *seg), *ooff = malloc((nb + 1) * sizeof *ooff);
+        size_t *idx = malloc(nb * sizeof *idx);
+        int rc = in && out && seg && ooff && idx ? ZGPU_OK : ZGPU_MEM_ERROR;
+        if (rc == ZGPU_OK) {
+            uint64_t j = 0, at = 0;
+            for (size_t k = 0; k < n; k++)
+                if (level > 0 && sourceLen[k] <= SEG_MAX) {
+                    seg[j] = at; idx[j++] = k;
+                    if (sourceLen[k]) memcpy(in + at, source[k], sourceLen[k]);
+                    at += sourceLen[k];
+                }
+            seg[nb] = at;
+            zgpu_deflate_params p;
+            memset(&p, 0, sizeof p);
+            p.level = level; p.flags = flags; p.lz_impl = ZGPU_LZ_AUTO;
+            zgpu_deflate_result res;
+            memset(&res, 0, sizeof res);
+            zgpu_engine *e = batch_engine_lock();
+            if (!e) rc = ZGPU_ERRNO;
+            else {
+                rc = zgpu_deflate_segments_host(e, in, seg, nb, &p, out, cap, ooff, &res);
+                batch_engine_unlock();
+            }
+            for (uint64_t i = 0; i < nb; i++) {
+                const size_t k = idx[i];
+                if (rc != ZGPU_OK) { status[k] = engine_code(rc); continue; }
+                const uint64_t len = ooff[i + 1] - ooff[i];
+                if (len > destLen[k]) { status[k] = Z_BUF_ERROR; continue; }
+                memcpy(dest[k], out + ooff[i], len);
+                destLen[k] = len;
+                status[k] = Z_OK;
+            }
+        } else {
+            for (size_t k = 0; k < n; k++)
+                if (level > 0 && sourceLen[k] <= SEG_MAX) status[k] = Z_MEM_ERROR;
+        }
+        free(in); free(out); free(seg); free(ooff); free(idx);
+    }
+    for (size_t k = 0; k < n; k++)
+        if (!(level > 0 && sourceLen[k] <= SEG_MAX)) status[k] = compress_one(dest[k], &destLen[k], source[k], sourceLen[k], level, windowBits);
+    return first_failure(status, n);
+}
+
+EXPORT int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits,
+                                 int *status)
+{
+    if (n && (!dest || !destLen || !source || !sourceLen || !status)) return Z_STREAM_ERROR;
+    const int wrap = windowBits == 15 ? ZGPU_WRAP_ZLIB : windowBits == 31 ? ZGPU_WRAP_GZIP : windowBits == 47 ? ZGPU_WRAP_AUTO : windowBits == -15 ? ZGPU_WRAP_RAW : -1;
+    if (wrap < 0) return Z_STREAM_ERROR;
+    for (size_t k = 0; k < n; k++)
+        if ((!source[k] && sourceLen[k]) || (!dest[k] && destLen[k])) return Z_STREAM_ERROR;
+    uint64_t nb = 0, in_total = 0, out_total = 0;
+    for (size_t k = 0; k < n; k++)
+        if (sourceLen[k] < BATCH_IN_MAX) { nb++; in_total += sourceLen[k]; out_total += destLen[k]; }
+    if (nb) {
+        uint8_t *in = malloc(in_total + 1), *out = malloc(out_total + 1);
+        uint64_t *ioff = malloc((nb + 1) * sizeof *ioff), *ooff = malloc((nb + 1) * sizeof *ooff);
+        zgpu_inflate_item *items = malloc(nb * sizeof *items);
+        size_t *idx = malloc(nb * sizeof *idx);
+        int rc = in && out && ioff && ooff && items && idx ? ZGPU_OK : ZGPU_MEM_ERROR;
+        if (rc == ZGPU_OK) {
+            uint64_t j = 0, ai = 0, ao = 0;
+            for (size_t k = 0; k < n; k++)
+                if (sourceLen[k] < BATCH_IN_MAX) {
+                    ioff[j] = ai; ooff[j] = ao; idx[j++] = k;
+                    if (sourceLen[k]) memcpy(in + ai, source[k], sourceLen[k]);
+                    ai += sourceLen[k]; ao += destLen[k];
+                }
+            ioff[nb] = ai; ooff[nb] = ao;
+            zgpu_engine *e = batch_engine_lock();
+            if (!e) rc = ZGPU_ERRNO;
+            else {
+                rc = zgpu_inflate_batch_host(e, in, in_total, ioff, nb, wrap, 0, out, out_total, ooff, items, NULL);
+                batch_engine_unlock();
+            }
+            for (uint64_t i = 0; i < nb; i++) {
+                const size_t k = idx[i];
+                if (rc != ZGPU_OK) { status[k] = engine_code(rc); continue; }
+                const zgpu_inflate_item *it = &items[i];
+                if (it->code == ZGPU_OK) {
+                    if (it->out_bytes) memcpy(dest[k], out + ooff[i], it->out_bytes);
+                    destLen[k] = it->out_bytes;
+                    status[k] = Z_OK;
+                } else status[k] = it->code == ZGPU_BUF_ERROR ? Z_BUF_ERROR : Z_DATA_ERROR; /* Z_NEED_DICT, truncation: uncompr.c:50-56 */
+            }
+        } else {
+            for (size_t k = 0; k < n; k++)
+                if (sourceLen[k] < BATCH_IN_MAX) status[k] = Z_MEM_ERROR;
+        }
+        free(in); free(out); free(ioff); free(ooff); free(items); free(idx);
+    }
+    for (size_t k = 0; k < n; k++)
+        if (sourceLen[k] >= BATCH_IN_MAX) status[k] = uncompress_one(dest[k], &destLen[k], source[k], sourceLen[k], windowBits);
+    return first_failure(status, n);
+}
