@@ -132,10 +132,18 @@ static void sift_down(enc *e, const htree *t, int k)
     e->heap[k] = v;
 }
 
+/* ---- test-only counters (oracle.h: ora_tree_counter): what the tree code went through since the last reset.  They are written, never read, by the
+ * compress path, so no output depends on them.  Plain statics: one thread at a time. ---- */
+static uint32_t g_count[ORA_TC_COUNT];
+static void count_max(int which, uint32_t v) { if (g_count[which] < v) g_count[which] = v; }
+uint32_t ora_tree_counter(int which) { return which >= 0 && which < ORA_TC_COUNT ? g_count[which] : 0; }
+void ora_tree_counters_reset(void) { memset(g_count, 0, sizeof g_count); }
+
 /* gen_bitlen trees.c:490-567 */
 static void assign_lengths(enc *e, htree *t, int elems_max_code, const uint8_t *sllen, const uint8_t *extra, int xbase, int max_length)
 {
     int h, n, m, bits, xbits, overflow = 0; (void)elems_max_code;
+    const int kind = t == &e->lt ? 0 : t == &e->dt ? 1 : 2;
     for (bits = 0; bits <= MAXBITS; bits++) e->bl_count[bits] = 0;
     t->len[e->heap[e->heap_max]] = 0;
     for (h = e->heap_max + 1; h < NHEAP; h++) {
@@ -144,11 +152,13 @@ static void assign_lengths(enc *e, htree *t, int elems_max_code, const uint8_t *
         t->len[n] = (uint16_t)bits;
         if (n > t->max_code) continue;
         e->bl_count[bits]++; xbits = 0;
+        count_max(ORA_TC_LONGEST + kind, (uint32_t)bits);
         if (n >= xbase) xbits = extra[n - xbase];
         e->opt_len += (uint64_t)t->freq[n] * (unsigned)(bits + xbits);
         if (sllen) e->static_len += (uint64_t)t->freq[n] * (unsigned)(sllen[n] + xbits);
     }
     if (overflow == 0) return;
+    g_count[ORA_TC_REPAIRS + kind]++; count_max(ORA_TC_OVERFLOW + kind, (uint32_t)overflow);
     do {
         bits = max_length - 1;
         while (e->bl_count[bits] == 0) bits--;
@@ -274,7 +284,9 @@ static void close_block(enc *e, uint32_t p_end, int eof)
         for (max_blindex = NBL - 1; max_blindex >= 3; max_blindex--) if (e->bt.len[BLORDER[max_blindex]] != 0) break;
         e->opt_len += 3 * (uint64_t)(max_blindex + 1) + 5 + 5 + 4;
         opt_lenb = (e->opt_len + 3 + 7) >> 3; static_lenb = (e->static_len + 3 + 7) >> 3;
+        if (static_lenb == opt_lenb) g_count[ORA_TC_TIE_STATIC]++;
         if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
+        if ((uint64_t)stored_len + 4 == opt_lenb && bs_w >= 0) g_count[ORA_TC_TIE_STORED]++;
     } else opt_lenb = static_lenb = (uint64_t)stored_len + 5;
 
     if ((uint64_t)stored_len + 4 <= opt_lenb && bs_w >= 0) { stored_block(e, e->in + e->block_start, stored_len, eof); btype = 0; e->last_eob = 8; }
@@ -289,6 +301,7 @@ static void close_block(enc *e, uint32_t p_end, int eof)
         walk_lengths(e, &e->lt, e->lt.max_code, 1); walk_lengths(e, &e->dt, e->dt.max_code, 1);
         emit_tokens(e, e->lt.code, e->lt.len, NULL, e->dt.code, e->dt.len, 0); btype = 2; e->last_eob = e->lt.len[EOB];
     }
+    g_count[ORA_TC_BLOCKS + btype]++;
     if (e->info && e->nblocks < 8) e->info->btype[e->nblocks] = (uint32_t)btype;
     e->nblocks++;
     new_block(e);

@@ -78,6 +78,22 @@ size_t ora_deflate_cont(const uint8_t *in, size_t n, size_t dict_len, int level,
 size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
                           const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap);
 
+/* Test-only counters of what the tree code (build_tree / gen_bitlen, trees.c:490-567, and the block choice of _tr_flush_block, :921-1016) went through
+ * since the last reset, over every ora_deflate_* call of the process.  They show that an input reaches the branch it is named for
+ * (oracle/treecases.py, tests/test_trees_cpu.py); no output depends on them.  Not thread-safe.
+ * kind: 0 literal/length tree, 1 distance tree, 2 bit-length tree. */
+enum {
+    ORA_TC_REPAIRS = 0,    /* + kind: blocks whose tree overflowed max_length and went through the repair behind `if (overflow == 0) return;` */
+    ORA_TC_OVERFLOW = 3,   /* + kind: the largest `overflow` any of those blocks entered the repair loop with */
+    ORA_TC_LONGEST = 6,    /* + kind: the longest code length the first pass gave a symbol (clamped at max_length) */
+    ORA_TC_BLOCKS = 9,     /* + 0 stored / 1 static / 2 dynamic: blocks written */
+    ORA_TC_TIE_STATIC = 12, /* blocks (level > 0) with static_lenb == opt_lenb before the smaller one is taken (trees.c:967) */
+    ORA_TC_TIE_STORED = 13, /* blocks (level > 0) with stored_len + 4 == opt_lenb and a buffer to copy from (trees.c:978) */
+    ORA_TC_COUNT = 14
+};
+uint32_t ora_tree_counter(int which);
+void ora_tree_counters_reset(void);
+
 /* adler32.c:57-125 and :128-149 */
 uint32_t ora_adler32(uint32_t adler, const uint8_t *buf, size_t len);
 uint32_t ora_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2);

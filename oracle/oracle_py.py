@@ -59,8 +59,24 @@ def lib():
             f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                           C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
             f.restype = C.c_int
+        L.ora_tree_counter.argtypes = [C.c_int]
+        L.ora_tree_counter.restype = C.c_uint32
+        L.ora_tree_counters_reset.argtypes = []
+        L.ora_tree_counters_reset.restype = None
         _lib = L
     return _lib
+
+
+def tree_counters_reset():
+    lib().ora_tree_counters_reset()
+
+
+def tree_counters() -> dict:
+    """The test-only counters of oracle.h (ORA_TC_*), summed over every deflate call since tree_counters_reset(): per tree kind (literal, distance,
+    bit-length) the blocks that went through gen_bitlen's overflow repair, the largest overflow and the longest first-pass code length; the blocks
+    written per type (stored, static, dynamic); the blocks that sat on one of the two equalities of the block choice."""
+    c = [lib().ora_tree_counter(k) for k in range(14)]
+    return dict(repairs=c[0:3], overflow=c[3:6], longest=c[6:9], blocks=c[9:12], tie_static=c[12], tie_stored=c[13])
 
 
 def deflate_chunk(chunk: bytes, level: int, is_last: bool, pos0_matchable: bool = False, want_tokens=False, strategy: int = 0):
