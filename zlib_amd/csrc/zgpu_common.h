@@ -201,6 +201,17 @@ struct ContState {
     uint32_t entry_k;     // entry of the next batch's first tile relative to its h0 (the chain's hand-over)
 };
 
+// running totals carried across batches of one call (device memory; the host writes its start values and reads the result back as this same struct)
+struct RunState {
+    uint64_t out_total; // bytes placed so far (starts at 2 when a zlib header is prepended)
+    uint64_t in_total;
+    uint64_t ntokens;
+    uint32_t adler_a, adler_b; // Adler-32 halves of all input so far (a starts at 1, b at 0)
+    uint32_t data_type;
+    uint32_t overflow;         // set when the output capacity was exceeded
+    uint32_t crc, pad;         // CRC-32 of all input so far (meaningful when the chunks' crc fields were filled)
+};
+
 // token: bits 0..7 = literal byte or (match length - 3); bits 8..23 = match distance (0 for a literal)
 __host__ __device__ inline uint32_t tok_lit(uint32_t c) { return c; }
 __host__ __device__ inline uint32_t tok_match(uint32_t dist, uint32_t lenm3) { return lenm3 | (dist << 8); }

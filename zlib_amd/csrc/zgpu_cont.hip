@@ -18,6 +18,7 @@
 //              a slot of its own; cont_stitch_kernel shifts it into place (stored blocks: straight from the input).
 //   chain 4  from one batch of tiles to the next, and from one feed of a stream to the next: ContState + the tokens of the block that is still filling.
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #include "../../include/zamd_gpu.h"
 
 namespace zgpu {

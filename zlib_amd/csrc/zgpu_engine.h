@@ -1,0 +1,186 @@
+// zgpu_engine.h -- internal (not installed): what the translation units of the engine share on the HOST side.  The engine struct and its owned
+// device buffers, and one prototype for every function that is defined in one .hip file and called from another.  Every file that defines one of
+// them includes this header too, so a signature that drifts is a compile error.  Default arguments live here only.
+#pragma once
+#include "zgpu_common.h"
+#include "../../include/zamd_gpu.h"
+#include <vector>
+
+namespace zgpu {
+
+int fail_hip(zgpu_engine *e, hipError_t err, const char *what, const char *file, int line); // sets the engine's error text; ZGPU_MEM_ERROR for hipErrorOutOfMemory, else ZGPU_ERRNO
+int fail(zgpu_engine *e, int code, const char *msg);                                       // sets the engine's error text, returns code
+
+// A device buffer the engine owns: typed, grow-only, freed with the engine.  Growth frees first and then allocates exactly the requested count --
+// no doubling, no copy of the old contents; the slack some callers want is in what they ask for.  Reads as the pointer it holds.
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0; // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    // n <= cap: nothing.  A failed allocation leaves the buffer empty (cap 0) and is reported through fail_hip (e == nullptr: the code only, no error
+    // text -- for a caller that can do without the buffer).  *grew: the buffer is a new one
+    int reserve(zgpu_engine *e, size_t n, bool *grew = nullptr)
+    {
+        if (grew) *grew = false;
+        if (n <= cap) return ZGPU_OK;
+        release();
+        const hipError_t err = hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T));
+        if (err != hipSuccess) { p = nullptr; return fail_hip(e, err, "hipMalloc of an engine buffer", __FILE__, __LINE__); }
+        cap = n;
+        if (grew) *grew = true;
+        return ZGPU_OK;
+    }
+};
+
+} // namespace zgpu
+
+struct StageSpan { int stage; hipEvent_t a, b; };
+
+struct zgpu_engine {
+    template <typename T> using DevBuf = zgpu::DevBuf<T>;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t copy_stream = nullptr; // H2D of the *_host entry points: the next batch's input moves while this batch's kernels run
+    std::vector<hipEvent_t> copy_ev;
+    hipStream_t d2h_stream = nullptr;  // D2H of zgpu_deflate_host: finished batches' bytes go home while later batches are compressed (a second host thread)
+    std::vector<hipEvent_t> done_ev;
+    uint64_t *pin_tot = nullptr;       // pinned: out_total behind every batch
+    char err[512] = {0};
+    // deflate workspace: tokens, meta and slots are one group, sized for batch_cap() chunks
+    DevBuf<uint32_t> tokens;
+    DevBuf<zgpu::ChunkMeta> meta;
+    DevBuf<uint8_t> slots;
+    uint32_t batch_cap() const { return (uint32_t)meta.cap; }
+    DevBuf<uint4> tables;        // serial LZ only: zeroed when allocated, after that `serial_tag` tells one launch's buckets from another's (SerialLzT::insert)
+    uint32_t serial_tag = 0;
+    DevBuf<uint8_t> par_ws;      // parallel LZ only (bytes): the larger of the two implementations' workspaces for par_cap chunks
+    uint32_t par_cap = 0;
+    int tuned = 0; uint32_t tune[4] = {0, 0, 0, 0}; // zgpu_deflate_set_tuning: good, lazy, nice, chain instead of the level's
+    uint64_t handed_on = 0; // (diagnostic: chunks handed on since the engine was made)
+    DevBuf<uint32_t> hand_list; // chunks the lane-per-chunk loop handed on: [0] their number, [1..] their indices in the batch
+    int geo_w = 15, geo_m = 8;   // zgpu_deflate_set_geometry: deflateInit2's windowBits and memLevel
+    DevBuf<uint8_t> geo_slots; DevBuf<uint4> geo_tables; DevBuf<uint32_t> geo_nostore; // the workspace of a non-default geometry (one group)
+    int exact_sort = 0;          // sticky: the fast sort's self-check failed once on this engine (zgpu_lz_sorted.hip, pass V)
+    DevBuf<uint64_t> offsets;    // nchunks+1 segment offsets of the current call
+    DevBuf<zgpu::RunState> run;  // one
+    // staging for the *_host entry points (bytes)
+    DevBuf<uint8_t> stage_in, stage_out;
+    // inflate scratch (status and slots: bytes)
+    DevBuf<uint8_t> inf_status;
+    DevBuf<zgpu::ChunkMeta> inf_meta;
+    DevBuf<uint64_t> inf_offs;
+    DevBuf<uint8_t> inf_slots;
+    DevBuf<uint8_t> inf_dict; uint32_t inf_dict_len = 0; // preset dictionary of the next inflate calls (zgpu_inflate_set_dictionary)
+    uint32_t inf_checks = 3;                             // checks of the decoded bytes (zgpu_inflate_set_checks)
+    // continuous stream (deflate_cont): per batch of tiles (one group, for ct_tiles() tiles) / per feed (ct_entry)
+    DevBuf<uint16_t> ct_exits, ct_entry, ct_comp, ct_gentry;
+    DevBuf<uint32_t> ct_tokoff, ct_T, ct_carry, ct_carry_in;
+    DevBuf<zgpu::ContBlk> ct_blk; DevBuf<uint64_t> ct_pos; DevBuf<uint8_t> ct_slots; DevBuf<zgpu::ContState> ct_st;
+    uint32_t ct_tiles() const { return ct_tokoff.cap ? (uint32_t)(ct_tokoff.cap - 1) : 0; } // (ct_tokoff: a word per tile and one more)
+    DevBuf<zgpu::ChunkMeta> ct_ckmeta;
+    DevBuf<uint64_t> ct_excl;
+    // ... levels 1-3: the rounds of fastwin_tile_kernel (the per-batch ones are one group)
+    DevBuf<uint16_t> cf_exit_a, cf_exit_b; DevBuf<uint32_t> cf_ins0, cf_ins1, cf_prev, cf_prev2, cf_hist, cf_count;
+    DevBuf<uint8_t> cf_cur, cf_act_a, cf_act_b, cf_changed, cf_kept; DevBuf<uint32_t> cf_list_a, cf_list_b, cf_used; DevBuf<uint16_t> cf_entry_used;
+    DevBuf<uint32_t> cf_dbg, cf_dstat; // (ZGPU_FAST_TRACE only)
+    hipStream_t ct_stream = nullptr; hipEvent_t ct_ev_a[2] = {nullptr, nullptr}, ct_ev_b[2] = {nullptr, nullptr}; // levels 4-9: a batch's blocks are made on a second stream under the next batch's walkers
+    uint64_t cf_rounds = 0, cf_tile_parses = 0; // (diagnostic: rounds and tile parses since the engine was made)
+    // profiling
+    bool prof = false;
+    double ms[ZGPU_STAGE_COUNT] = {0};
+    uint64_t launches[ZGPU_STAGE_COUNT] = {0};
+    std::vector<hipEvent_t> ev_pool;
+    size_t ev_used = 0;
+    std::vector<StageSpan> spans;
+
+    zgpu_engine() = default;
+    zgpu_engine(const zgpu_engine &) = delete;
+    zgpu_engine &operator=(const zgpu_engine &) = delete;
+    ~zgpu_engine(); // waits for the main stream, destroys events and streams; the buffers free themselves
+};
+
+namespace zgpu {
+
+// ---- zgpu_engine.hip ----
+void collect_spans(zgpu_engine *e);
+int ensure_stage(zgpu_engine *e, uint64_t in_bytes, uint64_t out_bytes);
+hipEvent_t engine_copy_event(zgpu_engine *e, size_t i);
+// stage timing of the other files' launches with the engine's event pool
+void prof_span_begin(zgpu_engine *e, hipStream_t st, hipEvent_t *a);
+void prof_span_end(zgpu_engine *e, hipStream_t st, int stage, hipEvent_t a);
+// Adler-32 (mask bit 0) and CRC-32 (bit 1) of d_bytes[0, nbytes) from 64 KiB pieces, at most batch_cap of them a launch, their records in `meta`
+int checksum_pass(zgpu_engine *e, const uint8_t *d_bytes, uint64_t nbytes, uint32_t mask, uint32_t batch_cap, DevBuf<ChunkMeta> &meta, hipStream_t st, uint32_t *adler, uint32_t *crc);
+
+// ---- zgpu_lz_serial.hip ----
+void launch_lz_serial(const ChunkGeom &g, LevelCfg cfg, uint4 *tables, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, uint32_t *nostore_bits, bool hand_on, uint32_t tag);
+
+// ---- zgpu_huffman.hip ----
+void launch_huffman(const ChunkGeom &g, const uint32_t *tokens, ChunkMeta *meta, uint8_t *slots, hipStream_t st, bool fixed_trees);
+void launch_huffman_cont(const ChunkGeom &g, const uint32_t *compact_tokens, uint32_t nblk, ContBlk *blk, ContState *cst, uint8_t *slots, hipStream_t st, bool fixed_trees);
+
+// ---- zgpu_stitch.hip ----
+void launch_collect_handed_on(const ChunkMeta *meta, uint32_t n, uint32_t *list, uint32_t *count, hipStream_t st);
+void launch_adler(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
+void launch_crc(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
+void launch_scan(const ChunkMeta *meta, uint32_t nchunks, uint64_t chunk0, uint64_t *offsets, void *run, uint64_t out_cap, hipStream_t st, bool with_crc = false);
+void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets, const uint64_t *seg_off, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
+                  uint64_t out_cap, uint32_t slot_stride, void *run, bool with_crc, const FrameHead &h, hipStream_t st);
+void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
+                   uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
+void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st);
+void launch_batch_finish(const BatchItemState *items, uint64_t n, const ChunkMeta *meta, const uint8_t *in, uint32_t do_adler, uint32_t do_crc,
+                         zgpu_inflate_item *out_items, unsigned long long *nfailed, hipStream_t st);
+
+// ---- zgpu_lz_parallel.hip ----
+bool lz_parallel_available();
+size_t lz_parallel_workspace_bytes(uint32_t batch_chunks);
+void launch_lz_parallel(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof);
+void launch_parse(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
+
+// ---- zgpu_lz_parse.hip ----
+void launch_parse2(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
+void launch_parse_lite(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
+void launch_parse_tile(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, const TileGeom &tg, hipStream_t st);
+
+// ---- zgpu_lz_sorted.hip ----
+size_t lz_sorted_workspace_bytes(uint32_t batch_chunks);
+uint32_t *lz_sorted_fault_word(void *workspace);
+bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, int walk);
+// continuous stream
+void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st,
+                     zgpu_engine *prof, int exact_sort);
+void launch_lz_tiles_parse(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof);
+void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out);
+
+// ---- zgpu_lz_fastwin.hip ----
+bool lz_fastwin_serves(const LevelCfg &cfg);
+void launch_lz_fastwin(const ChunkGeom &g, LevelCfg cfg, const uint16_t *S, const uint32_t *ir, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
+void launch_lz_fastwin_tiles(const ChunkGeom &g, const TileGeom &tg, const FastTiles &ft, LevelCfg cfg, const uint16_t *S, const uint32_t *ir, uint32_t *tokens, ChunkMeta *meta, uint32_t ngrid,
+                             hipStream_t st);
+void launch_fast_init(uint8_t *cur, uint8_t *active, uint16_t *exit_cur, uint32_t n, hipStream_t st);
+void launch_fast_flip_list(uint8_t *cur, uint16_t *exit_cur, const uint16_t *exit_new, const uint32_t *list, uint32_t n, hipStream_t st);
+void launch_fast_flip(uint8_t *cur, const uint8_t *active, uint8_t *active_next, const uint8_t *changed, uint16_t *exit_cur, const uint16_t *exit_new, uint32_t n, uint32_t round,
+                      uint32_t *count, uint32_t *list, const uint8_t *kept, hipStream_t st);
+void launch_fast_finish(const uint8_t *cur, const uint16_t *exit_cur, const uint32_t *ins0, const uint32_t *ins1, uint32_t n, uint16_t *entry_after, uint32_t *prev_ins, uint32_t *prev_prev_ins,
+                        const uint32_t *low, hipStream_t st);
+void launch_fast_hist(const uint32_t *before, const uint32_t *last, uint32_t x0, uint32_t count, uint32_t *out, hipStream_t st);
+
+// ---- zgpu_cont.hip ----
+uint32_t chain_groups(uint32_t ntiles);
+uint64_t cont_special_pos(uint64_t n);
+void launch_chain(const uint16_t *exits, uint32_t ntiles, uint16_t *comp, uint16_t *gentry, uint16_t *entry, hipStream_t st);
+void launch_cont_tokens(const ChunkGeom &g, const TileGeom &tg, const uint32_t *tokens, const ChunkMeta *tmeta, ContState *st, uint32_t *tokoff, const uint32_t *carry, uint32_t *T,
+                        ContBlk *blk, uint64_t seg_end, bool final_block, uint64_t sp, uint32_t nblk_cap, bool slow, hipStream_t s);
+void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const uint8_t *slots, uint32_t slot_stride, const uint8_t *in, uint64_t abs0, uint8_t *out, uint64_t out_cap,
+                        uint32_t nblk_cap, const uint32_t *T, uint32_t *carry, uint64_t seg_end, hipStream_t s);
+
+// ---- zgpu_inflate.hip ----
+int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t nchunks, uint32_t chunk_size, uint8_t *d_out, uint64_t out_cap,
+                zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode = 0, const uint64_t *h_offsets = nullptr, bool open_end = false, uint8_t *h_dst = nullptr, uint64_t h_cap = 0);
+
+} // namespace zgpu

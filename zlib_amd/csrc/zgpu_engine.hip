@@ -1,125 +1,12 @@
 // zgpu_engine.hip -- host side of the C ABI in include/zamd_gpu.h: workspace ownership, batching, kernel
 // sequencing on one HIP stream, per-stage HIP-event timing.  No torch, no C++ types cross the boundary.
-#include "zgpu_common.h"
-#include "../../include/zamd_gpu.h"
+#include "zgpu_engine.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <atomic>
 #include <thread>
-#include <vector>
-
-namespace zgpu {
-
-struct RunStateHost { uint64_t out_total, in_total, ntokens; uint32_t adler_a, adler_b, data_type, overflow, crc, pad; };
-
-// kernels (other translation units)
-void launch_lz_serial(const ChunkGeom &g, LevelCfg cfg, uint4 *tables, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, uint32_t *nostore_bits, bool hand_on, uint32_t tag);
-void launch_collect_handed_on(const ChunkMeta *meta, uint32_t n, uint32_t *list, uint32_t *count, hipStream_t st);
-void launch_huffman(const ChunkGeom &g, const uint32_t *tokens, ChunkMeta *meta, uint8_t *slots, hipStream_t st, bool fixed_trees);
-void launch_adler(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
-void launch_crc(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
-void launch_scan(const ChunkMeta *meta, uint32_t nchunks, uint64_t chunk0, uint64_t *offsets, void *run, uint64_t out_cap, hipStream_t st, bool with_crc = false);
-void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets, const uint64_t *seg_off, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
-                  uint64_t out_cap, uint32_t slot_stride, void *run, bool with_crc, const FrameHead &h, hipStream_t st);
-void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
-                   uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
-void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st);
-bool lz_parallel_available();
-size_t lz_parallel_workspace_bytes(uint32_t batch_chunks);
-void launch_lz_parallel(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, void *prof);
-size_t lz_sorted_workspace_bytes(uint32_t batch_chunks);
-bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, void *prof, int exact_sort, int walk);
-bool lz_fastwin_serves(const LevelCfg &cfg);
-uint32_t *lz_sorted_fault_word(void *workspace);
-// continuous stream (zgpu_cont.hip, zgpu_lz_sorted.hip)
-void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st,
-                     void *prof, int exact_sort);
-uint32_t chain_groups(uint32_t ntiles);
-void launch_lz_tiles_parse(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, void *prof);
-void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, void *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out);
-void launch_lz_fastwin_tiles(const ChunkGeom &g, const TileGeom &tg, const FastTiles &ft, LevelCfg cfg, const uint16_t *S, const uint32_t *ir, uint32_t *tokens, ChunkMeta *meta, uint32_t ngrid,
-                             hipStream_t st);
-void launch_fast_init(uint8_t *cur, uint8_t *active, uint16_t *exit_cur, uint32_t n, hipStream_t st);
-void launch_fast_flip_list(uint8_t *cur, uint16_t *exit_cur, const uint16_t *exit_new, const uint32_t *list, uint32_t n, hipStream_t st);
-void launch_fast_flip(uint8_t *cur, const uint8_t *active, uint8_t *active_next, const uint8_t *changed, uint16_t *exit_cur, const uint16_t *exit_new, uint32_t n, uint32_t round,
-                      uint32_t *count, uint32_t *list, const uint8_t *kept, hipStream_t st);
-void launch_fast_finish(const uint8_t *cur, const uint16_t *exit_cur, const uint32_t *ins0, const uint32_t *ins1, uint32_t n, uint16_t *entry_after, uint32_t *prev_ins, uint32_t *prev_prev_ins,
-                        const uint32_t *low, hipStream_t st);
-void launch_fast_hist(const uint32_t *before, const uint32_t *last, uint32_t x0, uint32_t count, uint32_t *out, hipStream_t st);
-void launch_cont_tokens(const ChunkGeom &g, const TileGeom &tg, const uint32_t *tokens, const ChunkMeta *tmeta, ContState *st, uint32_t *tokoff, const uint32_t *carry, uint32_t *T,
-                        ContBlk *blk, uint64_t seg_end, bool final_block, uint64_t sp, uint32_t nblk_cap, bool slow, hipStream_t s);
-void launch_huffman_cont(const ChunkGeom &g, const uint32_t *compact_tokens, uint32_t nblk, ContBlk *blk, ContState *cst, uint8_t *slots, hipStream_t st, bool fixed_trees);
-void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const uint8_t *slots, uint32_t slot_stride, const uint8_t *in, uint64_t abs0, uint8_t *out, uint64_t out_cap,
-                        uint32_t nblk_cap, const uint32_t *T, uint32_t *carry, uint64_t seg_end, hipStream_t s);
-uint64_t cont_special_pos(uint64_t n);
-int inflate_run(struct ::zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t nchunks,
-                uint32_t chunk_size, uint8_t *d_out, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode = 0,
-                const uint64_t *h_offsets = nullptr, bool open_end = false, uint8_t *h_dst = nullptr, uint64_t h_cap = 0);
-
-} // namespace zgpu
-
-struct StageSpan { int stage; hipEvent_t a, b; };
-
-struct zgpu_engine {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr; // H2D of the *_host entry points: the next batch's input moves while this batch's kernels run
-    std::vector<hipEvent_t> copy_ev;
-    hipStream_t d2h_stream = nullptr;  // D2H of zgpu_deflate_host: finished batches' bytes go home while later batches are compressed (a second host thread)
-    std::vector<hipEvent_t> done_ev;
-    uint64_t *pin_tot = nullptr;       // pinned: out_total behind every batch
-    char err[512] = {0};
-    // deflate workspace, sized for `batch_cap` chunks
-    uint32_t batch_cap = 0;
-    uint32_t *tokens = nullptr;
-    zgpu::ChunkMeta *meta = nullptr;
-    uint8_t *slots = nullptr;
-    uint4 *tables = nullptr;     // serial LZ only: zeroed when allocated, after that `serial_tag` tells one launch's buckets from another's (SerialLzT::insert)
-    uint32_t serial_tag = 0;
-    uint32_t tables_cap = 0;
-    void *par_ws = nullptr;      // parallel LZ only
-    int tuned = 0; uint32_t tune[4] = {0, 0, 0, 0}; // zgpu_deflate_set_tuning: good, lazy, nice, chain instead of the level's
-    uint64_t handed_on = 0; // (diagnostic: chunks handed on since the engine was made)
-    uint32_t *hand_list = nullptr; uint32_t hand_cap = 0; // chunks the lane-per-chunk loop handed on: [0] their number, [1..] their indices in the batch
-    int geo_w = 15, geo_m = 8;   // zgpu_deflate_set_geometry: deflateInit2's windowBits and memLevel
-    uint8_t *geo_slots = nullptr; uint4 *geo_tables = nullptr; uint32_t *geo_nostore = nullptr; uint32_t geo_cap = 0; // the workspace of a non-default geometry
-    int exact_sort = 0;          // sticky: the fast sort's self-check failed once on this engine (zgpu_lz_sorted.hip, pass V)
-    uint32_t par_cap = 0;
-    uint64_t *offsets = nullptr; // nchunks+1 segment offsets of the current call
-    uint64_t offsets_cap = 0;
-    void *run = nullptr;         // RunState
-    // staging for the *_host entry points
-    uint8_t *stage_in = nullptr, *stage_out = nullptr;
-    uint64_t stage_in_cap = 0, stage_out_cap = 0;
-    // inflate scratch
-    void *inf_status = nullptr; uint64_t inf_status_cap = 0;
-    zgpu::ChunkMeta *inf_meta = nullptr; uint32_t inf_meta_cap = 0;
-    uint64_t *inf_offs = nullptr; uint64_t inf_offs_cap = 0;
-    void *inf_slots = nullptr; uint64_t inf_slots_cap = 0;
-    uint8_t *inf_dict = nullptr; uint32_t inf_dict_len = 0; // preset dictionary of the next inflate calls (zgpu_inflate_set_dictionary)
-    uint32_t inf_checks = 3;                                // checks of the decoded bytes (zgpu_inflate_set_checks)
-    // continuous stream (deflate_cont): per batch of tiles / per feed
-    uint32_t ct_tiles = 0, ct_nblk = 0; uint64_t ct_feed_tiles = 0;
-    uint16_t *ct_exits = nullptr, *ct_entry = nullptr, *ct_comp = nullptr, *ct_gentry = nullptr;
-    uint32_t *ct_tokoff = nullptr, *ct_T = nullptr, *ct_carry = nullptr, *ct_carry_in = nullptr;
-    zgpu::ContBlk *ct_blk = nullptr; uint64_t *ct_pos = nullptr; uint8_t *ct_slots = nullptr; zgpu::ContState *ct_st = nullptr;
-    zgpu::ChunkMeta *ct_ckmeta = nullptr; uint64_t ct_ck_cap = 0;
-    uint64_t *ct_excl = nullptr; uint32_t ct_excl_cap = 0;
-    // ... levels 1-3: the rounds of fastwin_tile_kernel
-    uint32_t cf_tiles = 0;
-    uint16_t *cf_exit_a = nullptr, *cf_exit_b = nullptr; uint32_t *cf_ins0 = nullptr, *cf_ins1 = nullptr, *cf_prev = nullptr, *cf_prev2 = nullptr, *cf_hist = nullptr, *cf_count = nullptr;
-    uint8_t *cf_cur = nullptr, *cf_act_a = nullptr, *cf_act_b = nullptr, *cf_changed = nullptr, *cf_kept = nullptr; uint32_t *cf_list_a = nullptr, *cf_list_b = nullptr, *cf_used = nullptr; uint16_t *cf_entry_used = nullptr;
-    hipStream_t ct_stream = nullptr; hipEvent_t ct_ev_a[2] = {nullptr, nullptr}, ct_ev_b[2] = {nullptr, nullptr}; // levels 4-9: a batch's blocks are made on a second stream under the next batch's walkers
-    uint64_t cf_rounds = 0, cf_tile_parses = 0; // (diagnostic: rounds and tile parses since the engine was made)
-    // profiling
-    bool prof = false;
-    double ms[ZGPU_STAGE_COUNT] = {0};
-    uint64_t launches[ZGPU_STAGE_COUNT] = {0};
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    std::vector<StageSpan> spans;
-};
 
 namespace zgpu {
 
@@ -130,7 +17,7 @@ int fail_hip(zgpu_engine *e, hipError_t err, const char *what, const char *file,
     return ZGPU_ERRNO;
 }
 
-static int fail(zgpu_engine *e, int code, const char *msg)
+int fail(zgpu_engine *e, int code, const char *msg)
 {
     if (e) snprintf(e->err, sizeof e->err, "%s", msg);
     return code;
@@ -155,16 +42,10 @@ struct StageTimer {
     }
 };
 
-static void collect_spans(zgpu_engine *e)
+void collect_spans(zgpu_engine *e)
 {
     for (auto &s : e->spans) { float ms = 0; if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { e->ms[s.stage] += ms; e->launches[s.stage]++; } }
     e->spans.clear(); e->ev_used = 0;
-}
-
-template <typename T> static int dev_alloc(zgpu_engine *e, T **p, size_t count)
-{
-    ZGPU_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
-    return ZGPU_OK;
 }
 
 static uint32_t env_u32(const char *name, uint32_t dflt)
@@ -178,41 +59,33 @@ static uint32_t env_u32(const char *name, uint32_t dflt)
 static int ensure_deflate_ws(zgpu_engine *e, uint32_t batch, bool serial, uint64_t nchunks_total, bool geo = false)
 {
     int rc;
-    if (geo && batch > e->geo_cap) { // wider slots (blocks that may not be stored grow), head[] of up to 65536 entries, a flag word array per chunk
-        hipFree(e->geo_slots); hipFree(e->geo_tables); hipFree(e->geo_nostore); e->geo_slots = nullptr; e->geo_tables = nullptr; e->geo_nostore = nullptr; e->geo_cap = 0;
-        if ((rc = dev_alloc(e, &e->geo_slots, (size_t)batch * kGeoSlotStride))) return rc;
-        if ((rc = dev_alloc(e, &e->geo_tables, (size_t)batch * kGeoTableEntries))) return rc;
-        ZGPU_HIP_CHECK(hipMemsetAsync(e->geo_tables, 0, (size_t)batch * kGeoTableEntries * sizeof(uint4), e->stream));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
-        if ((rc = dev_alloc(e, &e->geo_nostore, (size_t)batch * kGeoNostoreWords))) return rc;
-        e->geo_cap = batch;
+    bool grew;
+    if (geo) { // wider slots (blocks that may not be stored grow), head[] of up to 65536 entries, a flag word array per chunk
+        if ((rc = e->geo_slots.reserve(e, (size_t)batch * kGeoSlotStride))) return rc;
+        if ((rc = e->geo_tables.reserve(e, (size_t)batch * kGeoTableEntries, &grew))) return rc;
+        if (grew) {
+            ZGPU_HIP_CHECK(hipMemsetAsync(e->geo_tables, 0, e->geo_tables.cap * sizeof(uint4), e->stream));
+            ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
+        }
+        if ((rc = e->geo_nostore.reserve(e, (size_t)batch * kGeoNostoreWords))) return rc;
     }
-    if (batch > e->batch_cap) {
-        hipFree(e->tokens); hipFree(e->meta); hipFree(e->slots); e->tokens = nullptr; e->meta = nullptr; e->slots = nullptr; e->batch_cap = 0;
-        if ((rc = dev_alloc(e, &e->tokens, (size_t)batch * kChunkMax))) return rc;
-        if ((rc = dev_alloc(e, &e->meta, (size_t)batch))) return rc;
-        if ((rc = dev_alloc(e, &e->slots, (size_t)batch * kSlotStride))) return rc;
-        e->batch_cap = batch;
-    }
-    if (serial && !geo && batch > e->tables_cap) {
-        hipFree(e->tables); e->tables = nullptr; e->tables_cap = 0;
-        if ((rc = dev_alloc(e, &e->tables, (size_t)batch * kSerialTableEntries))) return rc;
-        ZGPU_HIP_CHECK(hipMemsetAsync(e->tables, 0, (size_t)batch * kSerialTableEntries * sizeof(uint4), e->stream));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
-        e->tables_cap = batch;
+    if ((rc = e->tokens.reserve(e, (size_t)batch * kChunkMax))) return rc;
+    if ((rc = e->meta.reserve(e, (size_t)batch))) return rc;
+    if ((rc = e->slots.reserve(e, (size_t)batch * kSlotStride))) return rc;
+    if (serial && !geo) {
+        if ((rc = e->tables.reserve(e, (size_t)batch * kSerialTableEntries, &grew))) return rc;
+        if (grew) {
+            ZGPU_HIP_CHECK(hipMemsetAsync(e->tables, 0, e->tables.cap * sizeof(uint4), e->stream));
+            ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
+        }
     }
     if (!serial && batch > e->par_cap) {
-        hipFree(e->par_ws); e->par_ws = nullptr; e->par_cap = 0;
         const size_t wa = lz_parallel_workspace_bytes(batch), wb = lz_sorted_workspace_bytes(batch);
-        ZGPU_HIP_CHECK(hipMalloc(&e->par_ws, wa > wb ? wa : wb));
+        e->par_cap = 0;
+        if ((rc = e->par_ws.reserve(e, wa > wb ? wa : wb))) return rc;
         e->par_cap = batch;
     }
-    if (nchunks_total + 1 > e->offsets_cap) {
-        hipFree(e->offsets); e->offsets = nullptr; e->offsets_cap = 0;
-        if ((rc = dev_alloc(e, &e->offsets, (size_t)nchunks_total + 1))) return rc;
-        e->offsets_cap = nchunks_total + 1;
-    }
-    return ZGPU_OK;
+    return e->offsets.reserve(e, (size_t)nchunks_total + 1);
 }
 
 static void zlib_header(int level, int strategy, uint8_t hdr[2]) // qcsrc/deflate.c:625-641
@@ -220,6 +93,45 @@ static void zlib_header(int level, int strategy, uint8_t hdr[2]) // qcsrc/deflat
     unsigned h = (8u + (7u << 4)) << 8, lf = (strategy >= 2 || level < 2) ? 0 : level < 6 ? 1 : level == 6 ? 2 : 3;
     h |= lf << 6; h += 31 - h % 31;
     hdr[0] = (uint8_t)(h >> 8); hdr[1] = (uint8_t)h;
+}
+
+// what a stream that is not part of a wrapped segment call starts with: the zlib header, or the gzip header deflate() writes when no gz_header
+// was set (qcsrc/deflate.c:578-596); OS_CODE 3 as the reference builds here
+static FrameHead frame_head(int level, int strategy, bool wrap, bool gz)
+{
+    FrameHead fh{};
+    if (wrap) { zlib_header(level, strategy, fh.b); fh.n = 2; }
+    if (gz) {
+        const uint8_t hdr[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)(level == 9 ? 2 : (strategy >= 2 || level < 2) ? 4 : 0), 3};
+        for (int i = 0; i < 10; i++) fh.b[i] = hdr[i];
+        fh.n = 10; fh.gzip = 1;
+    }
+    return fh;
+}
+
+// ... and ends with, behind d_out[*out_total]: zlib's Adler-32, big-endian; gzip's CRC-32 and the input length mod 2^32, both little-endian (qcsrc/deflate.c:833-843)
+static int write_trailer(zgpu_engine *e, bool gz, uint32_t adler, uint32_t crc, uint64_t in_bytes, uint8_t *d_out, uint64_t *out_total, hipStream_t st)
+{
+    const uint32_t isz = (uint32_t)in_bytes, n = gz ? 8 : 4;
+    const uint8_t zl[4] = {(uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler};
+    const uint8_t gt[8] = {(uint8_t)crc, (uint8_t)(crc >> 8), (uint8_t)(crc >> 16), (uint8_t)(crc >> 24), (uint8_t)isz, (uint8_t)(isz >> 8), (uint8_t)(isz >> 16), (uint8_t)(isz >> 24)};
+    ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + *out_total, gz ? gt : zl, n, hipMemcpyHostToDevice, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    *out_total += n;
+    return ZGPU_OK;
+}
+
+// the level's parameters, or deflateTune's (deflate.c:453-470): the level keeps its function, the four parameters are the caller's
+static LevelCfg level_cfg_for(const zgpu_engine *e, int level, int strategy)
+{
+    LevelCfg cfg = level_cfg(level);
+    cfg.strategy = (uint32_t)strategy;
+    if (e->tuned) {
+        // (a budget of 0 never runs out in the reference: its loop counts down past zero, deflate.c:1163 -- no chain of a chunk is longer than 65535)
+        cfg.good = e->tune[0]; cfg.lazy = e->tune[1]; cfg.nice = e->tune[2]; cfg.chain = (e->tune[3] && e->tune[3] < 0xffffu) ? e->tune[3] : 0xffffu;
+        if (cfg.nice > kMaxMatch) cfg.nice = kMaxMatch; // (no match is longer: the same searches)
+    }
+    return cfg;
 }
 
 // d_seg (optional): device table of nseg+1 offsets; then every segment is one chunk and chunk_size is ignored.
@@ -239,13 +151,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     if (p->prime && ((p->prime >> 16) > 16 || (p->flags & (ZGPU_F_ZLIB_WRAP | ZGPU_F_GZIP_WRAP)))) return fail(e, ZGPU_STREAM_ERROR, "prime: at most 16 bits, no wrapper");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     if (p->strategy < 0 || p->strategy > (int)kFixed) return fail(e, ZGPU_STREAM_ERROR, "strategy must be 0..4");
-    LevelCfg cfg = level_cfg(p->level);
-    cfg.strategy = (uint32_t)p->strategy;
-    if (e->tuned) { // deflateTune (deflate.c:453-470): the level keeps its function, the four parameters are the caller's
-        // (a budget of 0 never runs out in the reference: its loop counts down past zero, deflate.c:1163 -- no chain of a chunk is longer than 65535)
-        cfg.good = e->tune[0]; cfg.lazy = e->tune[1]; cfg.nice = e->tune[2]; cfg.chain = (e->tune[3] && e->tune[3] < 0xffffu) ? e->tune[3] : 0xffffu;
-        if (cfg.nice > kMaxMatch) cfg.nice = kMaxMatch; // (no match is longer: the same searches)
-    }
+    LevelCfg cfg = level_cfg_for(e, p->level, p->strategy);
     // the chain budget of the all-position search says it all for two strategies (deflate.c:1594-1599): no candidate at all,
     // or the nearest one only (and then only at distance 1, see match3_kernel)
     if (cfg.slow && cfg.strategy == kHuffmanOnly) cfg.chain = 0;
@@ -323,7 +229,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
         size_t free_b = 0, total_b = 0;
         const size_t per_chunk = (size_t)kChunkMax * 4 + kSlotStride + (geo ? (size_t)kGeoSlotStride + (size_t)kGeoTableEntries * sizeof(uint4) : serial ? (size_t)kSerialTableEntries * sizeof(uint4) + (hand_on ? lz_sorted_workspace_bytes(1) / 4 : 0) : lz_sorted_workspace_bytes(1));
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t held = (size_t)e->batch_cap * per_chunk; // what this engine already owns can be reused
+            const size_t held = (size_t)e->batch_cap() * per_chunk; // what this engine already owns can be reused
             const size_t budget = (free_b + held) / 10 * 6;
             size_t fit = budget / per_chunk; // chunks that fit; never below 256, whatever the device reports
             if (fit < 256) fit = 256;
@@ -338,23 +244,13 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
         hand_piece = batch / 4 < 4096 ? (batch < 4096 ? batch : 4096) : batch / 4; // the sorted buckets' workspace: for a quarter of the batch at a time
         if ((rc = ensure_deflate_ws(e, hand_piece, false, nchunks))) return rc;
         if (e->par_cap > hand_piece) hand_piece = e->par_cap < batch ? e->par_cap : batch; // (an earlier call has left more)
-        if (batch > e->hand_cap) {
-            hipFree(e->hand_list); e->hand_list = nullptr; e->hand_cap = 0;
-            if ((rc = dev_alloc(e, &e->hand_list, (size_t)batch + 1))) return rc;
-            e->hand_cap = batch;
-        }
+        if ((rc = e->hand_list.reserve(e, (size_t)batch + 1))) return rc;
     }
     const bool wrap = p->flags & ZGPU_F_ZLIB_WRAP, gz = p->flags & ZGPU_F_GZIP_WRAP;
     // segments with a wrapper: every segment is a stream of its own, framed by launch_frame; the call itself has no header or trailer
     const bool seg_wrap = d_seg && (wrap || gz);
     const uint32_t head_bytes = seg_wrap ? 0 : wrap ? 2 : gz ? 10 : 0, tail_bytes = seg_wrap ? 0 : wrap ? 4 : gz ? 8 : 0;
-    FrameHead fh{};
-    if (wrap) { zlib_header(p->level, p->strategy, fh.b); fh.n = 2; }
-    if (gz) { // the header deflate() writes when no gz_header was set (qcsrc/deflate.c:578-596); OS_CODE 3 as the reference builds here
-        const uint8_t hdr[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)(p->level == 9 ? 2 : (p->strategy >= 2 || p->level < 2) ? 4 : 0), 3};
-        for (int i = 0; i < 10; i++) fh.b[i] = hdr[i];
-        fh.n = 10; fh.gzip = 1;
-    }
+    const FrameHead fh = frame_head(p->level, p->strategy, wrap, gz);
     ChunkGeom g{};
     g.in = d_in; g.in_bytes = in_bytes; g.seg_off = d_seg; g.chunk_size = chunk_size;
     g.final_chunk = (!d_seg && (p->flags & ZGPU_F_FINAL)) ? nchunks - 1 : ~0ull;
@@ -368,7 +264,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     g.prime = (p->prime >> 16) ? ((p->prime & 0xffff0000u) | (p->prime & ((1u << (p->prime >> 16)) - 1u))) : 0u;
     const uint64_t body_cap = tail_bytes ? (out_cap >= head_bytes + tail_bytes ? out_cap - tail_bytes : 0) : out_cap;
 
-    RunStateHost rs{}; rs.out_total = head_bytes; rs.adler_a = 1; rs.adler_b = 0; rs.data_type = 2;
+    RunState rs{}; rs.out_total = head_bytes; rs.adler_a = 1; rs.adler_b = 0; rs.data_type = 2;
     ZGPU_HIP_CHECK(hipMemcpyAsync(e->run, &rs, sizeof rs, hipMemcpyHostToDevice, st));
     const bool check_sort = (impl == ZGPU_LZ_SORTED || impl == ZGPU_LZ_WALK || impl == ZGPU_LZ_FAST || impl == ZGPU_LZ_FASTWIN || hand_on) && !e->exact_sort;
     uint32_t sort_fault = 0;
@@ -432,8 +328,8 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
             StageTimer t(e, st, ZGPU_STAGE_LZ_SERIAL);
             // (a tag that these tables have not seen: 0 is what fresh tables hold; should the counter ever wrap, they are zeroed again)
             if (++e->serial_tag == 0) {
-                if (e->tables) ZGPU_HIP_CHECK(hipMemsetAsync(e->tables, 0, (size_t)e->tables_cap * kSerialTableEntries * sizeof(uint4), st));
-                if (e->geo_tables) ZGPU_HIP_CHECK(hipMemsetAsync(e->geo_tables, 0, (size_t)e->geo_cap * kGeoTableEntries * sizeof(uint4), st));
+                if (e->tables) ZGPU_HIP_CHECK(hipMemsetAsync(e->tables, 0, e->tables.cap * sizeof(uint4), st));
+                if (e->geo_tables) ZGPU_HIP_CHECK(hipMemsetAsync(e->geo_tables, 0, e->geo_tables.cap * sizeof(uint4), st));
                 e->serial_tag = 1;
             }
             if (geo) launch_lz_serial(g, cfg, e->geo_tables, e->tokens, e->meta, st, e->geo_nostore, false, e->serial_tag);
@@ -490,20 +386,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     }
     if (rs.overflow || (tail_bytes && out_cap < rs.out_total + tail_bytes)) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
     const uint32_t adler = rs.adler_a | (rs.adler_b << 16);
-    if (wrap && !seg_wrap) {
-        uint8_t tr[4] = {(uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler};
-        ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + rs.out_total, tr, 4, hipMemcpyHostToDevice, st));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-        rs.out_total += 4;
-    }
-    if (gz && !seg_wrap) { // CRC-32 and the input length mod 2^32, both little-endian (qcsrc/deflate.c:833-843)
-        const uint32_t isz = (uint32_t)in_bytes;
-        uint8_t tr[8] = {(uint8_t)rs.crc, (uint8_t)(rs.crc >> 8), (uint8_t)(rs.crc >> 16), (uint8_t)(rs.crc >> 24),
-                         (uint8_t)isz, (uint8_t)(isz >> 8), (uint8_t)(isz >> 16), (uint8_t)(isz >> 24)};
-        ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + rs.out_total, tr, 8, hipMemcpyHostToDevice, st));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-        rs.out_total += 8;
-    }
+    if ((wrap || gz) && !seg_wrap && (rc = write_trailer(e, gz, adler, rs.crc, in_bytes, d_out, &rs.out_total, st))) return rc;
     if (d_chunk_offsets) {
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_chunk_offsets, e->offsets, (nchunks + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
         ZGPU_HIP_CHECK(hipStreamSynchronize(st));
@@ -512,9 +395,6 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     res->crc32 = (gz || (p->flags & ZGPU_F_CRC32)) ? rs.crc : 0;
     return ZGPU_OK;
 }
-
-ChunkMeta *engine_meta(zgpu_engine *e, uint32_t batch);
-uint64_t *engine_offsets_scratch(zgpu_engine *e, uint64_t n);
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // One FEED of a continuous stream (zgpu_cont.hip has the plan): d_buf holds the history the parse can still reach followed by the bytes that have
@@ -525,65 +405,43 @@ constexpr uint32_t kContCarry = 16384;
 static int ensure_cont_ws(zgpu_engine *e, uint32_t batch_tiles, uint64_t feed_tiles)
 {
     int rc;
-    if (!e->ct_st) {
-        if ((rc = dev_alloc(e, &e->ct_st, 1))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_carry, kContCarry))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_carry_in, kContCarry))) return rc;
-    }
-    if (feed_tiles + 2 > e->ct_feed_tiles) {
-        hipFree(e->ct_entry); e->ct_entry = nullptr; e->ct_feed_tiles = 0;
-        if ((rc = dev_alloc(e, &e->ct_entry, feed_tiles + 2 + 1024))) return rc;
-        e->ct_feed_tiles = feed_tiles + 2 + 1024;
-    }
-    if (batch_tiles > e->ct_tiles) {
-        hipFree(e->ct_exits); hipFree(e->ct_comp); hipFree(e->ct_gentry); hipFree(e->ct_tokoff); hipFree(e->ct_T); hipFree(e->ct_blk); hipFree(e->ct_pos); hipFree(e->ct_slots);
-        e->ct_exits = e->ct_comp = e->ct_gentry = nullptr; e->ct_tokoff = e->ct_T = nullptr; e->ct_blk = nullptr; e->ct_pos = nullptr; e->ct_slots = nullptr; e->ct_tiles = 0;
-        const size_t ntok_cap = (size_t)kContCarry + kChunkMax + (size_t)batch_tiles * (kTileStride + kTileSlack); // tile 0 of a feed parses up to 65024 positions, the others 32512, + the last game's overhang
-        const uint32_t nblk_cap = (uint32_t)(ntok_cap / kBlockTokens + 2);
-        const uint32_t ngroups = chain_groups(batch_tiles);
-        if ((rc = dev_alloc(e, &e->ct_exits, (size_t)batch_tiles * kTileExitStride))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_comp, (size_t)ngroups * kTileExitStride))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_gentry, (size_t)ngroups + 1))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_tokoff, (size_t)batch_tiles + 1))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_T, ntok_cap))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_blk, (size_t)nblk_cap))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_pos, (size_t)nblk_cap + 1))) return rc;
-        if ((rc = dev_alloc(e, &e->ct_slots, (size_t)nblk_cap * kSlotStride))) return rc;
-        e->ct_tiles = batch_tiles; e->ct_nblk = nblk_cap;
-    }
-    return ZGPU_OK;
+    if ((rc = e->ct_st.reserve(e, 1))) return rc;
+    if ((rc = e->ct_carry.reserve(e, kContCarry))) return rc;
+    if ((rc = e->ct_carry_in.reserve(e, kContCarry))) return rc;
+    if (feed_tiles + 2 > e->ct_entry.cap && (rc = e->ct_entry.reserve(e, feed_tiles + 2 + 1024))) return rc;
+    const size_t ntok_cap = (size_t)kContCarry + kChunkMax + (size_t)batch_tiles * (kTileStride + kTileSlack); // tile 0 of a feed parses up to 65024 positions, the others 32512, + the last game's overhang
+    const uint32_t nblk_cap = (uint32_t)(ntok_cap / kBlockTokens + 2);
+    const uint32_t ngroups = chain_groups(batch_tiles);
+    if ((rc = e->ct_exits.reserve(e, (size_t)batch_tiles * kTileExitStride))) return rc;
+    if ((rc = e->ct_comp.reserve(e, (size_t)ngroups * kTileExitStride))) return rc;
+    if ((rc = e->ct_gentry.reserve(e, (size_t)ngroups + 1))) return rc;
+    if ((rc = e->ct_tokoff.reserve(e, (size_t)batch_tiles + 1))) return rc;
+    if ((rc = e->ct_T.reserve(e, ntok_cap))) return rc;
+    if ((rc = e->ct_blk.reserve(e, (size_t)nblk_cap))) return rc;
+    if ((rc = e->ct_pos.reserve(e, (size_t)nblk_cap + 1))) return rc;
+    return e->ct_slots.reserve(e, (size_t)nblk_cap * kSlotStride);
 }
 
 static int ensure_fast_ws(zgpu_engine *e, uint32_t batch_tiles)
 {
     int rc;
-    if (!e->cf_prev) {
-        if ((rc = dev_alloc(e, &e->cf_prev, kInsWords + 8))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_prev2, kInsWords + 8))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_hist, kInsWords + 8))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_count, 4))) return rc;
-    }
-    if (batch_tiles > e->cf_tiles) {
-        hipFree(e->cf_exit_a); hipFree(e->cf_exit_b); hipFree(e->cf_ins0); hipFree(e->cf_ins1); hipFree(e->cf_cur); hipFree(e->cf_act_a); hipFree(e->cf_act_b); hipFree(e->cf_changed);
-        hipFree(e->cf_list_a); hipFree(e->cf_list_b); e->cf_list_a = e->cf_list_b = nullptr;
-        hipFree(e->cf_kept); hipFree(e->cf_used); hipFree(e->cf_entry_used); e->cf_kept = nullptr; e->cf_used = nullptr; e->cf_entry_used = nullptr;
-        e->cf_exit_a = e->cf_exit_b = nullptr; e->cf_ins0 = e->cf_ins1 = nullptr; e->cf_cur = e->cf_act_a = e->cf_act_b = e->cf_changed = nullptr; e->cf_tiles = 0;
-        if ((rc = dev_alloc(e, &e->cf_exit_a, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_exit_b, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_ins0, (size_t)batch_tiles * kInsWords))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_ins1, (size_t)batch_tiles * kInsWords))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_cur, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_act_a, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_act_b, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_changed, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_list_a, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_list_b, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_kept, (size_t)batch_tiles))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_used, (size_t)batch_tiles * kInsWords))) return rc;
-        if ((rc = dev_alloc(e, &e->cf_entry_used, (size_t)batch_tiles))) return rc;
-        e->cf_tiles = batch_tiles;
-    }
-    return ZGPU_OK;
+    if ((rc = e->cf_prev.reserve(e, kInsWords + 8))) return rc;
+    if ((rc = e->cf_prev2.reserve(e, kInsWords + 8))) return rc;
+    if ((rc = e->cf_hist.reserve(e, kInsWords + 8))) return rc;
+    if ((rc = e->cf_count.reserve(e, 4))) return rc;
+    if ((rc = e->cf_exit_a.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_exit_b.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_ins0.reserve(e, (size_t)batch_tiles * kInsWords))) return rc;
+    if ((rc = e->cf_ins1.reserve(e, (size_t)batch_tiles * kInsWords))) return rc;
+    if ((rc = e->cf_cur.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_act_a.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_act_b.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_changed.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_list_a.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_list_b.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_kept.reserve(e, (size_t)batch_tiles))) return rc;
+    if ((rc = e->cf_used.reserve(e, (size_t)batch_tiles * kInsWords))) return rc;
+    return e->cf_entry_used.reserve(e, (size_t)batch_tiles);
 }
 // levels 1-3: the tiles of one batch by rounds (zgpu_lz_fastwin.hip, fastwin_tile_kernel): until no tile's predecessor has changed
 static int lz_tiles_fast(zgpu_engine *e, const ChunkGeom &g, const TileGeom &tg, const LevelCfg &cfg, hipStream_t st)
@@ -595,10 +453,9 @@ static int lz_tiles_fast(zgpu_engine *e, const ChunkGeom &g, const TileGeom &tg,
     launch_fast_init(e->cf_cur, e->cf_act_a, e->cf_exit_a, nb, st);
     uint8_t *act = e->cf_act_a, *act_next = e->cf_act_b;
     uint32_t *list = nullptr, *list_next = e->cf_list_a, ngrid = nb;
-    static uint32_t *dbg = nullptr, *dstat = nullptr;
     const bool trace = getenv("ZGPU_FAST_TRACE") != nullptr;
-    if (trace && !dbg) hipMalloc(reinterpret_cast<void **>(&dbg), 65536 * 32);
-    if (trace && !dstat) hipMalloc(reinterpret_cast<void **>(&dstat), 32);
+    if (trace && (e->cf_dbg.reserve(e, 65536 * 8) || e->cf_dstat.reserve(e, 8))) return ZGPU_MEM_ERROR;
+    uint32_t *const dbg = e->cf_dbg, *const dstat = e->cf_dstat;
     static int keep = -1; // ZGPU_FAST_KEEP=0: every active tile is parsed to its end (A/B runs)
     if (keep < 0) { const char *v = getenv("ZGPU_FAST_KEEP"); keep = v ? atoi(v) : 1; }
     auto fill = [&](FastTiles &ft, uint32_t round, const uint32_t *lst) {
@@ -724,7 +581,7 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             // what this engine holds already and would use again, piece by piece (the chunked path's buffers serve the tiles too): counted as free, or the batch would
             // grow from call to call as more of the same memory is held -- and a later call of a series would stop to allocate (seen in bench.py: 44 035, 64 837, 66 052 tiles)
-            const size_t held = (size_t)e->batch_cap * ((size_t)kChunkMax * 4 + kSlotStride) + (size_t)e->par_cap * lz_sorted_workspace_bytes(1) + (size_t)e->ct_tiles * ((size_t)(kTileStride + kTileSlack) * 4 + 3 * (size_t)kSlotStride);
+            const size_t held = (size_t)e->batch_cap() * ((size_t)kChunkMax * 4 + kSlotStride) + (size_t)e->par_cap * lz_sorted_workspace_bytes(1) + (size_t)e->ct_tiles() * ((size_t)(kTileStride + kTileSlack) * 4 + 3 * (size_t)kSlotStride);
             size_t fit = (free_b + held) / 10 * 6 / per_tile;
             if (fit < 64) fit = 64;
             if (fit < batch_max) batch_max = (uint32_t)fit;
@@ -754,7 +611,7 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     const uint32_t batch = (uint32_t)(ntiles < batch_max ? (ntiles ? ntiles : 1) : batch_max);
     const bool size_trace = getenv("ZGPU_FAST_TRACE") != nullptr;
     timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
-    if (size_trace) fprintf(stderr, "continuous stream: %llu tiles, memory admits %u, batches of %u (held: %u tiles, %u chunks of tokens, %u of buckets)\n", (unsigned long long)ntiles, batch_fit, batch, e->ct_tiles, e->batch_cap, e->par_cap);
+    if (size_trace) fprintf(stderr, "continuous stream: %llu tiles, memory admits %u, batches of %u (held: %u tiles, %u chunks of tokens, %u of buckets)\n", (unsigned long long)ntiles, batch_fit, batch, e->ct_tiles(), e->batch_cap(), e->par_cap);
     int rc = ensure_deflate_ws(e, pipe ? 2 * batch + 1 : batch, false, 1);
     if (rc) return rc;
     if ((rc = ensure_cont_ws(e, pipe ? 2 * batch : batch, ntiles))) return rc;
@@ -770,7 +627,7 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     const uint64_t seg_end = ends ? cs->abs0 + f.buf_bytes : ~0ull, sp = ends ? cont_special_pos(seg_end) : ~0ull;
     uint32_t nexcl_dev = 0;
     if (f.nexcl && !fast_lz) { // (levels 1-3 know which positions are in the chains bit by bit: hist bits)
-        if (f.nexcl > e->ct_excl_cap) { hipFree(e->ct_excl); e->ct_excl = nullptr; e->ct_excl_cap = 0; if ((rc = dev_alloc(e, &e->ct_excl, (size_t)f.nexcl + 64))) return rc; e->ct_excl_cap = f.nexcl + 64; }
+        if (f.nexcl > e->ct_excl.cap && (rc = e->ct_excl.reserve(e, (size_t)f.nexcl + 64))) return rc;
         std::vector<uint64_t> off(f.nexcl);
         uint32_t k = 0;
         for (uint32_t i = 0; i < f.nexcl; i++) if (f.h_excl[i] >= cs->abs0 && f.h_excl[i] - cs->abs0 < f.buf_bytes) off[k++] = f.h_excl[i] - cs->abs0; // (buffer offsets)
@@ -786,7 +643,7 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     const bool check_sort = !e->exact_sort;
     uint32_t sort_fault = 0;
     const size_t ws_half = (lz_sorted_workspace_bytes(batch) + 255) & ~(size_t)255;
-    uint8_t *const ws_set[2] = {static_cast<uint8_t *>(e->par_ws), static_cast<uint8_t *>(e->par_ws) + (pipe ? ws_half : 0)};
+    uint8_t *const ws_set[2] = {e->par_ws, e->par_ws + (pipe ? ws_half : 0)};
     if (check_sort) { ZGPU_HIP_CHECK(hipMemsetAsync(lz_sorted_fault_word(ws_set[0]), 0, 4, st)); if (pipe) ZGPU_HIP_CHECK(hipMemsetAsync(lz_sorted_fault_word(ws_set[1]), 0, 4, st)); }
 
     ChunkGeom g{};
@@ -796,6 +653,8 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     tg.abs0 = cs->abs0; tg.e0 = e0; tg.end = end; tg.nil_pos = (sp != ~0ull && sp >= cs->abs0 && sp < seg_end) ? sp - cs->abs0 : ~0ull; tg.abs0_nil = 1;
     tg.exits = e->ct_exits; tg.entry = e->ct_entry;
     const uint64_t out_cap4 = f.out_cap & ~3ull;
+    // blocks the per-batch buffers have room for (the three grow together, ensure_cont_ws; the smallest counts should a growth ever have failed half way)
+    const uint32_t nblk_cap = (uint32_t)std::min({e->ct_blk.cap, e->ct_pos.cap - 1, e->ct_slots.cap / kSlotStride});
     hipStream_t sb = pipe ? e->ct_stream : st; // where a batch's blocks are made
     if (pipe) { ZGPU_HIP_CHECK(hipEventRecord(e->ct_ev_a[0], st)); ZGPU_HIP_CHECK(hipStreamWaitEvent(sb, e->ct_ev_a[0], 0)); } // (the second stream starts behind what the caller has queued: the input, the state)
     uint64_t kbatch = 0;
@@ -815,15 +674,15 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
         const uint64_t seg_here = (ends && last_batch) ? seg_end : ~0ull;
         {
             StageTimer t(e, sb, ZGPU_STAGE_PARSE);
-            launch_cont_tokens(g, tg, tokens, tmeta, e->ct_st, e->ct_tokoff, t0 == 0 ? d_carry_in : e->ct_carry, e->ct_T, e->ct_blk, seg_here, f.mode == ZGPU_CONT_FINISH && seg_here != ~0ull, seg_here != ~0ull ? sp : ~0ull, e->ct_nblk, cfg.slow != 0, sb);
+            launch_cont_tokens(g, tg, tokens, tmeta, e->ct_st, e->ct_tokoff, t0 == 0 ? d_carry_in : e->ct_carry, e->ct_T, e->ct_blk, seg_here, f.mode == ZGPU_CONT_FINISH && seg_here != ~0ull, seg_here != ~0ull ? sp : ~0ull, nblk_cap, cfg.slow != 0, sb);
         }
         {
             StageTimer t(e, sb, ZGPU_STAGE_HUFFMAN);
-            launch_huffman_cont(g, e->ct_T, e->ct_nblk, e->ct_blk, e->ct_st, e->ct_slots, sb, cfg.strategy == kFixed);
+            launch_huffman_cont(g, e->ct_T, nblk_cap, e->ct_blk, e->ct_st, e->ct_slots, sb, cfg.strategy == kFixed);
         }
         {
             StageTimer t(e, sb, ZGPU_STAGE_STITCH);
-            launch_cont_stitch(e->ct_blk, e->ct_st, e->ct_pos, e->ct_slots, kSlotStride, f.d_buf, cs->abs0, f.d_out, out_cap4, e->ct_nblk, e->ct_T, e->ct_carry, seg_here, sb);
+            launch_cont_stitch(e->ct_blk, e->ct_st, e->ct_pos, e->ct_slots, kSlotStride, f.d_buf, cs->abs0, f.d_out, out_cap4, nblk_cap, e->ct_T, e->ct_carry, seg_here, sb);
         }
         if (pipe) ZGPU_HIP_CHECK(hipEventRecord(e->ct_ev_b[set], sb));
         const hipError_t he = hipGetLastError();
@@ -834,25 +693,8 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     // checksums of the bytes this feed brought
     uint32_t adler = 1, crc = 0;
     if (f.check_from < f.buf_bytes) {
-        const uint64_t nbytes = f.buf_bytes - f.check_from, nck = (nbytes + kChunkMax - 1) / kChunkMax;
-        const uint32_t cb = (uint32_t)(nck < 65536 ? nck : 65536);
-        if (cb > e->ct_ck_cap) { hipFree(e->ct_ckmeta); e->ct_ckmeta = nullptr; e->ct_ck_cap = 0; if ((rc = dev_alloc(e, &e->ct_ckmeta, (size_t)cb))) return rc; e->ct_ck_cap = cb; }
-        uint64_t *offs = engine_offsets_scratch(e, nck + 1);
-        if (!offs) return fail(e, ZGPU_MEM_ERROR, "checksum scratch");
         StageTimer t(e, st, ZGPU_STAGE_STITCH);
-        RunStateHost rs{}; rs.adler_a = 1;
-        ZGPU_HIP_CHECK(hipMemcpyAsync(e->run, &rs, sizeof rs, hipMemcpyHostToDevice, st));
-        for (uint64_t c0 = 0; c0 < nck; c0 += cb) {
-            const uint32_t nbk = (uint32_t)(nck - c0 < cb ? nck - c0 : cb);
-            ZGPU_HIP_CHECK(hipMemsetAsync(e->ct_ckmeta, 0, (size_t)nbk * sizeof(ChunkMeta), st));
-            ChunkGeom g2{}; g2.in = f.d_buf + f.check_from; g2.in_bytes = nbytes; g2.chunk_size = kChunkMax; g2.chunk0 = c0; g2.nchunks = nbk; g2.final_chunk = ~0ull;
-            launch_adler(g2, e->ct_ckmeta, st);
-            if (f.want_crc) launch_crc(g2, e->ct_ckmeta, st);
-            launch_scan(e->ct_ckmeta, nbk, c0, offs, e->run, ~0ull, st, f.want_crc);
-        }
-        ZGPU_HIP_CHECK(hipMemcpyAsync(&rs, e->run, sizeof rs, hipMemcpyDeviceToHost, st));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-        adler = rs.adler_a | (rs.adler_b << 16); crc = rs.crc;
+        if ((rc = checksum_pass(e, f.d_buf + f.check_from, f.buf_bytes - f.check_from, f.want_crc ? 3u : 1u, 65536, e->ct_ckmeta, st, &adler, &crc))) return rc;
     }
     uint16_t k_next = 0;
     ZGPU_HIP_CHECK(hipMemcpyAsync(&hs, e->ct_st, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -897,22 +739,55 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     return ZGPU_OK;
 }
 
-static int ensure_stage(zgpu_engine *e, uint64_t in_bytes, uint64_t out_bytes)
+int ensure_stage(zgpu_engine *e, uint64_t in_bytes, uint64_t out_bytes)
 {
-    if (in_bytes > e->stage_in_cap) {
-        hipFree(e->stage_in); e->stage_in = nullptr; e->stage_in_cap = 0;
-        uint64_t cap = in_bytes + (in_bytes >> 3) + 4096;
-        ZGPU_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&e->stage_in), cap)); e->stage_in_cap = cap;
+    int rc;
+    if (in_bytes > e->stage_in.cap && (rc = e->stage_in.reserve(e, in_bytes + (in_bytes >> 3) + 4096))) return rc;
+    if (out_bytes > e->stage_out.cap && (rc = e->stage_out.reserve(e, out_bytes + (out_bytes >> 3) + 4096))) return rc;
+    return ZGPU_OK;
+}
+
+// Adler-32 / CRC-32 over 64 KiB pieces (the kernels of the compress side): zero the pieces' records, launch_adler / launch_crc, launch_scan joins them in the run state
+int checksum_pass(zgpu_engine *e, const uint8_t *d_bytes, uint64_t nbytes, uint32_t mask, uint32_t batch_cap, DevBuf<ChunkMeta> &meta, hipStream_t st, uint32_t *adler, uint32_t *crc)
+{
+    const uint64_t npieces = nbytes ? (nbytes + kChunkMax - 1) / kChunkMax : 1;
+    const uint32_t batch = (uint32_t)(npieces < batch_cap ? npieces : batch_cap);
+    // (the engine's grow-only scratch: checksum-only users call this per buffer)
+    if (meta.reserve(e, batch) || e->inf_offs.reserve(e, npieces + 1)) return ZGPU_MEM_ERROR;
+    RunState rs{}; rs.adler_a = 1;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(e->run, &rs, sizeof rs, hipMemcpyHostToDevice, st));
+    for (uint64_t c0 = 0; c0 < npieces; c0 += batch) {
+        const uint32_t nb = (uint32_t)(npieces - c0 < batch ? npieces - c0 : batch);
+        ZGPU_HIP_CHECK(hipMemsetAsync(meta, 0, (size_t)nb * sizeof(ChunkMeta), st));
+        ChunkGeom g{}; g.in = d_bytes; g.in_bytes = nbytes; g.chunk_size = kChunkMax; g.chunk0 = c0; g.nchunks = nb; g.final_chunk = ~0ull;
+        if (mask & 1u) launch_adler(g, meta, st); // (not computed: the pieces read a = 0, b = 0; the result is not reported)
+        if (mask & 2u) launch_crc(g, meta, st);
+        launch_scan(meta, nb, c0, e->inf_offs, e->run, ~0ull, st, (mask & 2u) != 0);
     }
-    if (out_bytes > e->stage_out_cap) {
-        hipFree(e->stage_out); e->stage_out = nullptr; e->stage_out_cap = 0;
-        uint64_t cap = out_bytes + (out_bytes >> 3) + 4096;
-        ZGPU_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&e->stage_out), cap)); e->stage_out_cap = cap;
-    }
+    ZGPU_HIP_CHECK(hipMemcpyAsync(&rs, e->run, sizeof rs, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    *adler = (mask & 1u) ? rs.adler_a | (rs.adler_b << 16) : 1u;
+    *crc = (mask & 2u) ? rs.crc : 0u;
     return ZGPU_OK;
 }
 
 } // namespace zgpu
+
+zgpu_engine::~zgpu_engine()
+{
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    for (auto ev : ev_pool) hipEventDestroy(ev);
+    for (auto ev : copy_ev) hipEventDestroy(ev);
+    for (auto ev : done_ev) hipEventDestroy(ev);
+    if (ct_stream) hipStreamDestroy(ct_stream);
+    for (int i = 0; i < 2; i++) { if (ct_ev_a[i]) hipEventDestroy(ct_ev_a[i]); if (ct_ev_b[i]) hipEventDestroy(ct_ev_b[i]); }
+    if (d2h_stream) hipStreamDestroy(d2h_stream);
+    if (pin_tot) hipHostFree(pin_tot);
+    if (copy_stream) hipStreamDestroy(copy_stream);
+    if (stream) hipStreamDestroy(stream);
+    // (the device buffers free themselves, behind this, with the engine's device still set)
+}
 
 using namespace zgpu;
 
@@ -937,7 +812,7 @@ int zgpu_engine_create(int device, zgpu_engine **out)
     zgpu_engine *e = new zgpu_engine();
     e->device = device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&e->run, 256) != hipSuccess) {
+        e->run.reserve(e, 1) != ZGPU_OK) {
         delete e;
         return ZGPU_ERRNO;
     }
@@ -947,25 +822,7 @@ int zgpu_engine_create(int device, zgpu_engine **out)
 
 void zgpu_engine_destroy(zgpu_engine *e)
 {
-    if (!e) return;
-    hipSetDevice(e->device);
-    hipStreamSynchronize(e->stream);
-    hipFree(e->hand_list); hipFree(e->tokens); hipFree(e->meta); hipFree(e->slots); hipFree(e->tables); hipFree(e->geo_slots); hipFree(e->geo_tables); hipFree(e->geo_nostore); hipFree(e->par_ws); hipFree(e->offsets); hipFree(e->run);
-    hipFree(e->ct_exits); hipFree(e->ct_entry); hipFree(e->ct_comp); hipFree(e->ct_gentry); hipFree(e->ct_tokoff); hipFree(e->ct_T); hipFree(e->ct_carry); hipFree(e->ct_carry_in); hipFree(e->ct_blk);
-    hipFree(e->ct_pos); hipFree(e->ct_slots); hipFree(e->ct_st); hipFree(e->ct_ckmeta); hipFree(e->ct_excl);
-    hipFree(e->cf_exit_a); hipFree(e->cf_exit_b); hipFree(e->cf_ins0); hipFree(e->cf_ins1); hipFree(e->cf_prev); hipFree(e->cf_prev2); hipFree(e->cf_hist); hipFree(e->cf_count);
-    hipFree(e->cf_cur); hipFree(e->cf_act_a); hipFree(e->cf_act_b); hipFree(e->cf_changed); hipFree(e->cf_list_a); hipFree(e->cf_list_b); hipFree(e->cf_kept); hipFree(e->cf_used); hipFree(e->cf_entry_used);
-    hipFree(e->stage_in); hipFree(e->stage_out); hipFree(e->inf_status); hipFree(e->inf_meta); hipFree(e->inf_offs); hipFree(e->inf_slots); hipFree(e->inf_dict);
-    for (auto ev : e->ev_pool) hipEventDestroy(ev);
-    for (auto ev : e->copy_ev) hipEventDestroy(ev);
-    for (auto ev : e->done_ev) hipEventDestroy(ev);
-    if (e->ct_stream) hipStreamDestroy(e->ct_stream);
-    for (int i = 0; i < 2; i++) { if (e->ct_ev_a[i]) hipEventDestroy(e->ct_ev_a[i]); if (e->ct_ev_b[i]) hipEventDestroy(e->ct_ev_b[i]); }
-    if (e->d2h_stream) hipStreamDestroy(e->d2h_stream);
-    if (e->pin_tot) hipHostFree(e->pin_tot);
-    hipStreamDestroy(e->copy_stream);
-    hipStreamDestroy(e->stream);
-    delete e;
+    if (e) delete e;
 }
 
 const char *zgpu_engine_error(const zgpu_engine *e) { return e ? e->err : "no engine"; }
@@ -1011,16 +868,14 @@ static int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in
     if (p->level < 1 || p->level > 9 || p->strategy < 0 || p->strategy > (int)kFixed) return fail(e, ZGPU_STREAM_ERROR, "level 1..9, strategy 0..4");
     if (p->prime || (p->flags & (ZGPU_F_POS0 | ZGPU_F_POS0_ALL)) || !(p->flags & ZGPU_F_FINAL) || e->geo_w != 15 || e->geo_m != 8) return fail(e, ZGPU_STREAM_ERROR, "continuous stream: FINAL, no prime, the default geometry");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
-    LevelCfg cfg = level_cfg(p->level);
-    cfg.strategy = (uint32_t)p->strategy;
-    if (e->tuned) { cfg.good = e->tune[0]; cfg.lazy = e->tune[1]; cfg.nice = e->tune[2]; cfg.chain = (e->tune[3] && e->tune[3] < 0xffffu) ? e->tune[3] : 0xffffu; if (cfg.nice > kMaxMatch) cfg.nice = kMaxMatch; }
+    const LevelCfg cfg = level_cfg_for(e, p->level, p->strategy);
     const bool wrap = p->flags & ZGPU_F_ZLIB_WRAP, gz = p->flags & ZGPU_F_GZIP_WRAP;
     if (wrap && gz) return fail(e, ZGPU_STREAM_ERROR, "one wrapper at a time");
     const uint32_t head_bytes = wrap ? 2 : gz ? 10 : 0, tail_bytes = wrap ? 4 : gz ? 8 : 0;
     if (out_cap < head_bytes + tail_bytes + 8) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    const FrameHead fh = frame_head(p->level, p->strategy, wrap, gz);
     uint8_t hdr[12] = {0};
-    if (wrap) zlib_header(p->level, p->strategy, hdr);
-    if (gz) { const uint8_t h[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)(p->level == 9 ? 2 : (p->strategy >= 2 || p->level < 2) ? 4 : 0), 3}; memcpy(hdr, h, 10); }
+    memcpy(hdr, fh.b, fh.n);
     ZGPU_HIP_CHECK(hipMemcpyAsync(d_out, hdr, (head_bytes + 4) & ~3u, hipMemcpyHostToDevice, st)); // (zero-filled to a whole word: the first block's bits are ORed in behind the header)
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     zgpu_cont_state cs{}; cs.data_type = 2; cs.first_block = 1; cs.last_eob = 8;
@@ -1032,20 +887,7 @@ static int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in
     if (rc) return rc;
     rc = deflate_cont(e, f, cfg, &cs, e->ct_carry_in, res, st);
     if (rc) return rc;
-    if (wrap) {
-        const uint32_t a = res->adler32;
-        uint8_t tr[4] = {(uint8_t)(a >> 24), (uint8_t)(a >> 16), (uint8_t)(a >> 8), (uint8_t)a};
-        ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + res->out_bytes, tr, 4, hipMemcpyHostToDevice, st));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-        res->out_bytes += 4;
-    }
-    if (gz) {
-        const uint32_t c = res->crc32, isz = (uint32_t)in_bytes;
-        uint8_t tr[8] = {(uint8_t)c, (uint8_t)(c >> 8), (uint8_t)(c >> 16), (uint8_t)(c >> 24), (uint8_t)isz, (uint8_t)(isz >> 8), (uint8_t)(isz >> 16), (uint8_t)(isz >> 24)};
-        ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + res->out_bytes, tr, 8, hipMemcpyHostToDevice, st));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-        res->out_bytes += 8;
-    }
+    if ((wrap || gz) && (rc = write_trailer(e, gz, res->adler32, res->crc32, in_bytes, d_out, &res->out_bytes, st))) return rc;
     if (!f.want_crc) res->crc32 = 0;
     return ZGPU_OK;
 }
@@ -1065,9 +907,7 @@ int zgpu_deflate_cont_host(zgpu_engine *e, const void *hist, uint64_t hist_bytes
     if (p->level < 1 || p->level > 9 || p->strategy < 0 || p->strategy > (int)kFixed || mode < ZGPU_CONT_MORE || mode > ZGPU_CONT_FINISH) return fail(e, ZGPU_STREAM_ERROR, "level 1..9, strategy 0..4, a ZGPU_CONT_* mode");
     if (e->geo_w != 15 || e->geo_m != 8) return fail(e, ZGPU_STREAM_ERROR, "continuous stream: the default geometry");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
-    LevelCfg cfg = level_cfg(p->level);
-    cfg.strategy = (uint32_t)p->strategy;
-    if (e->tuned) { cfg.good = e->tune[0]; cfg.lazy = e->tune[1]; cfg.nice = e->tune[2]; cfg.chain = (e->tune[3] && e->tune[3] < 0xffffu) ? e->tune[3] : 0xffffu; if (cfg.nice > kMaxMatch) cfg.nice = kMaxMatch; }
+    const LevelCfg cfg = level_cfg_for(e, p->level, p->strategy);
     const uint64_t bound = zgpu_deflate_cont_bound(buf_bytes) + kContCarry * 4;
     int rc = ensure_stage(e, buf_bytes, bound);
     if (rc) return rc;
@@ -1215,10 +1055,7 @@ int zgpu_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const u
     const uint64_t need_out = nchunks * (uint64_t)(chunk_size ? chunk_size : kChunkMax);
     int rc = ensure_stage(e, in_bytes + 64, need_out);
     if (rc) return rc;
-    if (nchunks + 1 > e->offsets_cap) {
-        hipFree(e->offsets); e->offsets = nullptr; e->offsets_cap = 0;
-        ZGPU_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&e->offsets), (nchunks + 1) * sizeof(uint64_t))); e->offsets_cap = nchunks + 1;
-    }
+    if ((rc = e->offsets.reserve(e, nchunks + 1))) return rc;
     ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in, in, in_bytes, hipMemcpyHostToDevice, e->stream));
     ZGPU_HIP_CHECK(hipMemcpyAsync(e->offsets, chunk_offsets, (nchunks + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
     // direct placement with room for every chunk: the output goes to the caller's buffer batch by batch, under the decoding of the next batch
@@ -1238,7 +1075,7 @@ int zgpu_inflate_set_dictionary(zgpu_engine *e, const void *dict, uint32_t len)
     if (!e || (!dict && len)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     if (len > kWSize) { dict = static_cast<const uint8_t *>(dict) + (len - kWSize); len = kWSize; } // the window keeps the tail (inflate.c:1222-1226)
-    if (len && !e->inf_dict) ZGPU_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&e->inf_dict), kWSize));
+    if (len) { const int rc = e->inf_dict.reserve(e, kWSize); if (rc) return rc; }
     if (len) { ZGPU_HIP_CHECK(hipMemcpyAsync(e->inf_dict, dict, len, hipMemcpyHostToDevice, e->stream)); ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream)); }
     e->inf_dict_len = len;
     return ZGPU_OK;
@@ -1256,27 +1093,10 @@ int zgpu_adler32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uin
     if (!e || !adler_out || (!d_in && in_bytes)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
-    const uint64_t nchunks = in_bytes ? (in_bytes + kChunkMax - 1) / kChunkMax : 1;
-    const uint32_t batch = (uint32_t)(nchunks < 65536 ? nchunks : 65536);
     int rc = ensure_deflate_ws(e, 1, false, 1);
     if (rc) return rc;
-    // (the engine's grow-only scratch: these two are called per buffer by checksum-only users)
-    ChunkMeta *meta = engine_meta(e, batch);
-    uint64_t *offs = engine_offsets_scratch(e, nchunks + 1);
-    if (!meta || !offs) return fail(e, ZGPU_MEM_ERROR, "checksum scratch");
-    RunStateHost rs{}; rs.adler_a = 1;
-    ZGPU_HIP_CHECK(hipMemcpyAsync(e->run, &rs, sizeof rs, hipMemcpyHostToDevice, st));
-    for (uint64_t c0 = 0; c0 < nchunks; c0 += batch) {
-        const uint32_t nb = (uint32_t)(nchunks - c0 < batch ? nchunks - c0 : batch);
-        ZGPU_HIP_CHECK(hipMemsetAsync(meta, 0, (size_t)nb * sizeof(ChunkMeta), st));
-        ChunkGeom g{}; g.in = static_cast<const uint8_t *>(d_in); g.in_bytes = in_bytes; g.chunk_size = kChunkMax; g.chunk0 = c0; g.nchunks = nb; g.final_chunk = ~0ull;
-        launch_adler(g, meta, st);
-        launch_scan(meta, nb, c0, offs, e->run, ~0ull, st);
-    }
-    ZGPU_HIP_CHECK(hipMemcpyAsync(&rs, e->run, sizeof rs, hipMemcpyDeviceToHost, st));
-    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-    *adler_out = rs.adler_a | (rs.adler_b << 16);
-    return ZGPU_OK;
+    uint32_t crc;
+    return checksum_pass(e, static_cast<const uint8_t *>(d_in), in_bytes, 1u, 65536, e->inf_meta, st, adler_out, &crc);
 }
 
 int zgpu_crc32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *crc_out, void *hip_stream)
@@ -1284,27 +1104,10 @@ int zgpu_crc32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint3
     if (!e || !crc_out || (!d_in && in_bytes)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
-    const uint64_t nchunks = in_bytes ? (in_bytes + kChunkMax - 1) / kChunkMax : 1;
-    const uint32_t batch = (uint32_t)(nchunks < 65536 ? nchunks : 65536);
     int rc = ensure_deflate_ws(e, 1, false, 1);
     if (rc) return rc;
-    // (the engine's grow-only scratch: these two are called per buffer by checksum-only users)
-    ChunkMeta *meta = engine_meta(e, batch);
-    uint64_t *offs = engine_offsets_scratch(e, nchunks + 1);
-    if (!meta || !offs) return fail(e, ZGPU_MEM_ERROR, "checksum scratch");
-    RunStateHost rs{}; rs.adler_a = 1;
-    ZGPU_HIP_CHECK(hipMemcpyAsync(e->run, &rs, sizeof rs, hipMemcpyHostToDevice, st));
-    for (uint64_t c0 = 0; c0 < nchunks; c0 += batch) {
-        const uint32_t nb = (uint32_t)(nchunks - c0 < batch ? nchunks - c0 : batch);
-        ZGPU_HIP_CHECK(hipMemsetAsync(meta, 0, (size_t)nb * sizeof(ChunkMeta), st));
-        ChunkGeom g{}; g.in = static_cast<const uint8_t *>(d_in); g.in_bytes = in_bytes; g.chunk_size = kChunkMax; g.chunk0 = c0; g.nchunks = nb; g.final_chunk = ~0ull;
-        launch_crc(g, meta, st);
-        launch_scan(meta, nb, c0, offs, e->run, ~0ull, st, true);
-    }
-    ZGPU_HIP_CHECK(hipMemcpyAsync(&rs, e->run, sizeof rs, hipMemcpyDeviceToHost, st));
-    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-    *crc_out = rs.crc;
-    return ZGPU_OK;
+    uint32_t adler;
+    return checksum_pass(e, static_cast<const uint8_t *>(d_in), in_bytes, 2u, 65536, e->inf_meta, st, &adler, crc_out);
 }
 
 void zgpu_profile_enable(zgpu_engine *e, int on) { if (e) e->prof = on != 0; }
@@ -1336,69 +1139,19 @@ int zgpu_corpus_fill_device(zgpu_engine *e, uint32_t kind, uint64_t seed, uint64
 #pragma GCC visibility pop
 } // extern "C"
 
-// hooks used by zgpu_lz_parallel.hip to time its sub-stages with the engine's event pool
 namespace zgpu {
-void *engine_scratch(zgpu_engine *e, size_t bytes)
-{
-    if (bytes > e->inf_status_cap) {
-        hipFree(e->inf_status); e->inf_status = nullptr; e->inf_status_cap = 0;
-        if (hipMalloc(&e->inf_status, bytes) != hipSuccess) return nullptr;
-        e->inf_status_cap = bytes;
-    }
-    return e->inf_status;
-}
-void *engine_scratch2(zgpu_engine *e, size_t bytes)
-{
-    if (bytes > e->inf_slots_cap) {
-        hipFree(e->inf_slots); e->inf_slots = nullptr; e->inf_slots_cap = 0;
-        if (hipMalloc(&e->inf_slots, bytes) != hipSuccess) return nullptr;
-        e->inf_slots_cap = bytes;
-    }
-    return e->inf_slots;
-}
-void *engine_run_state(zgpu_engine *e) { return e->run; }
-uint8_t *engine_stage_in(zgpu_engine *e) { return e->stage_in; }
-uint8_t *engine_stage_out(zgpu_engine *e) { return e->stage_out; }
-const uint8_t *engine_inflate_dict(zgpu_engine *e) { return e->inf_dict; }
-uint32_t engine_inflate_dict_len(zgpu_engine *e) { return e->inf_dict_len; }
-uint32_t engine_inflate_checks(zgpu_engine *e) { return e->inf_checks; }
-int engine_ensure_stage(zgpu_engine *e, uint64_t in_bytes, uint64_t out_bytes) { return ensure_stage(e, in_bytes, out_bytes); }
-hipStream_t engine_stream(zgpu_engine *e) { return e->stream; }
-hipStream_t engine_copy_stream(zgpu_engine *e) { return e->copy_stream; }
 hipEvent_t engine_copy_event(zgpu_engine *e, size_t i)
 {
     while (e->copy_ev.size() <= i) { hipEvent_t ev; if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr; e->copy_ev.push_back(ev); }
     return e->copy_ev[i];
 }
-ChunkMeta *engine_meta(zgpu_engine *e, uint32_t batch)
+// stage timing for the launches of the other files (zgpu_lz_parallel.hip, zgpu_lz_sorted.hip, zgpu_inflate.hip) with the engine's event pool
+void prof_span_begin(zgpu_engine *e, hipStream_t st, hipEvent_t *a)
 {
-    if (batch > e->inf_meta_cap) {
-        hipFree(e->inf_meta); e->inf_meta = nullptr; e->inf_meta_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&e->inf_meta), (size_t)batch * sizeof(ChunkMeta)) != hipSuccess) return nullptr;
-        e->inf_meta_cap = batch;
-    }
-    return e->inf_meta;
-}
-uint64_t *engine_offsets_scratch(zgpu_engine *e, uint64_t n)
-{
-    if (n > e->inf_offs_cap) {
-        hipFree(e->inf_offs); e->inf_offs = nullptr; e->inf_offs_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&e->inf_offs), n * sizeof(uint64_t)) != hipSuccess) return nullptr;
-        e->inf_offs_cap = n;
-    }
-    return e->inf_offs;
-}
-int engine_device(zgpu_engine *e) { return e->device; }
-void engine_collect(zgpu_engine *e) { collect_spans(e); }
-int engine_fail(zgpu_engine *e, int code, const char *msg) { return fail(e, code, msg); }
-void prof_span_begin(void *eng, hipStream_t st, hipEvent_t *a)
-{
-    zgpu_engine *e = static_cast<zgpu_engine *>(eng);
     if (e && e->prof) { *a = next_event(e); hipEventRecord(*a, st); }
 }
-void prof_span_end(void *eng, hipStream_t st, int stage, hipEvent_t a)
+void prof_span_end(zgpu_engine *e, hipStream_t st, int stage, hipEvent_t a)
 {
-    zgpu_engine *e = static_cast<zgpu_engine *>(eng);
     if (e && e->prof) { hipEvent_t b = next_event(e); hipEventRecord(b, st); e->spans.push_back({stage, a, b}); }
 }
 } // namespace zgpu

@@ -18,6 +18,7 @@
 // sizes it, a workgroup prefix scan turns sizes into bit offsets, and each lane packs its range into 32-bit
 // words (plain stores for interior words, atomic OR for the two words it may share with a neighbour).
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 
 namespace zgpu {
 

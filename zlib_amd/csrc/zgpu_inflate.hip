@@ -14,27 +14,14 @@
 // match copies (64 bytes per step) and the final store of the chunk (16 bytes per lane).  The whole output chunk
 // (<= 64 KiB) lives in LDS while it is decoded, so back-references never touch global memory.
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #include <type_traits>
 #include "../../include/zamd_gpu.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-struct zgpu_engine;
-
 namespace zgpu {
-
-int fail_hip(zgpu_engine *e, hipError_t err, const char *what, const char *file, int line);
-void prof_span_begin(void *eng, hipStream_t st, hipEvent_t *a);
-void prof_span_end(void *eng, hipStream_t st, int stage, hipEvent_t a);
-const uint8_t *engine_inflate_dict(zgpu_engine *e);
-uint32_t engine_inflate_dict_len(zgpu_engine *e);
-uint32_t engine_inflate_checks(zgpu_engine *e);
-void launch_adler(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
-void launch_crc(const ChunkGeom &g, ChunkMeta *meta, hipStream_t st);
-void launch_scan(const ChunkMeta *meta, uint32_t nchunks, uint64_t chunk0, uint64_t *offsets, void *run, uint64_t out_cap, hipStream_t st, bool with_crc = false);
-void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
-                   uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
 
 static const char *const kInfMessages[kMsgCount] = {
     "", "invalid block type", "invalid stored block lengths", "too many length or distance symbols", "invalid code lengths set",
@@ -1045,56 +1032,20 @@ __global__ void __launch_bounds__(1024) inflate_reduce_kernel(const InfStatus *s
     }
 }
 
-int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t nchunks, uint32_t chunk_size,
-                uint8_t *d_out, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode, const uint64_t *h_offsets,
-                bool open_end = false, uint8_t *h_dst = nullptr, uint64_t h_cap = 0);
-
 } // namespace zgpu
 
 using namespace zgpu;
 
-// engine internals needed here (defined in zgpu_engine.hip)
 namespace zgpu {
-void *engine_scratch(zgpu_engine *e, size_t bytes);          // grow-only device scratch
-void *engine_scratch2(zgpu_engine *e, size_t bytes);
-void *engine_run_state(zgpu_engine *e);
-ChunkMeta *engine_meta(zgpu_engine *e, uint32_t batch);
-uint64_t *engine_offsets_scratch(zgpu_engine *e, uint64_t n);
-int engine_device(zgpu_engine *e);
-void engine_collect(zgpu_engine *e);
-int engine_fail(zgpu_engine *e, int code, const char *msg);
-hipStream_t engine_copy_stream(zgpu_engine *e);
-hipEvent_t engine_copy_event(zgpu_engine *e, size_t i);
-struct RunStateHostI { uint64_t out_total, in_total, ntokens; uint32_t adler_a, adler_b, data_type, overflow, crc, pad; };
-
-// Adler-32 and CRC-32 of the produced bytes (same kernels as the compress side), over 64 KiB pieces of the output
+// Adler-32 and CRC-32 of the produced bytes, as far as zgpu_inflate_set_checks asks for them, over 64 KiB pieces of the output (checksum_pass, zgpu_engine.hip)
 static int output_checksums(zgpu_engine *e, const uint8_t *d_out, uint64_t nbytes, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st)
 {
-    const uint32_t checks = engine_inflate_checks(e); // bit 0: Adler-32, bit 1: CRC-32 (zgpu_inflate_set_checks)
-    if (!checks) { engine_collect(e); res->adler32 = 1; res->crc32 = 0; return ZGPU_OK; }
     const uint64_t max_pieces = (out_cap >> 16) + 2;
-    const uint32_t cbatch_cap = (uint32_t)(max_pieces < 65536 ? max_pieces : 65536);
-    const uint64_t npieces = nbytes ? (nbytes + kChunkMax - 1) / kChunkMax : 1;
-    const uint32_t cbatch = (uint32_t)(npieces < cbatch_cap ? npieces : cbatch_cap);
-    ChunkMeta *meta = engine_meta(e, cbatch);
-    uint64_t *oscr = engine_offsets_scratch(e, npieces + 2);
-    if (!meta || !oscr) return engine_fail(e, ZGPU_MEM_ERROR, "checksum scratch");
-    RunStateHostI rs{}; rs.adler_a = 1;
-    ZGPU_HIP_CHECK(hipMemcpyAsync(engine_run_state(e), &rs, sizeof rs, hipMemcpyHostToDevice, st));
-    for (uint64_t c0 = 0; c0 < npieces; c0 += cbatch) {
-        const uint32_t nb = (uint32_t)(npieces - c0 < cbatch ? npieces - c0 : cbatch);
-        ChunkGeom g{}; g.in = d_out; g.in_bytes = nbytes; g.chunk_size = kChunkMax; g.chunk0 = c0; g.nchunks = nb; g.final_chunk = ~0ull;
-        ZGPU_HIP_CHECK(hipMemsetAsync(meta, 0, (size_t)nb * sizeof(ChunkMeta), st));
-        if (checks & 1u) launch_adler(g, meta, st); // (not computed: the pieces read a = 0, b = 0; the result is not reported)
-        if (checks & 2u) launch_crc(g, meta, st);
-        launch_scan(meta, nb, c0, oscr, engine_run_state(e), ~0ull, st, (checks & 2u) != 0);
-    }
-    ZGPU_HIP_CHECK(hipMemcpyAsync(&rs, engine_run_state(e), sizeof rs, hipMemcpyDeviceToHost, st));
-    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-    engine_collect(e);
-    res->adler32 = (checks & 1u) ? rs.adler_a | (rs.adler_b << 16) : 1u;
-    res->crc32 = (checks & 2u) ? rs.crc : 0u;
-    return ZGPU_OK;
+    int rc = ZGPU_OK;
+    res->adler32 = 1; res->crc32 = 0;
+    if (e->inf_checks) rc = checksum_pass(e, d_out, nbytes, e->inf_checks, (uint32_t)(max_pieces < 65536 ? max_pieces : 65536), e->inf_meta, st, &res->adler32, &res->crc32);
+    collect_spans(e);
+    return rc;
 }
 
 // stream_mode (compact or whole-stream calls): see inflate_reduce_kernel; h_offsets = the offsets table on the host (for res->in_used);
@@ -1114,8 +1065,8 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
     const uint64_t last_chunk = open_end ? ~0ull : nchunks - 1;
     if (!e || !res || !d_in || !d_out || !d_offsets || nchunks == 0 || (chunk_size > kChunkMax && !(chunk_size == kWholeStream && nchunks == 1)) ||
         (chunk_size == kWholeStream && in_bytes >= (1ull << 29)))
-        return engine_fail(e, ZGPU_STREAM_ERROR, "bad inflate arguments");
-    ZGPU_HIP_CHECK(hipSetDevice(engine_device(e)));
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate arguments");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
     const bool compact = chunk_size == 0; // segments of any size: decode into slots, then concatenate
     // (one batch has nothing to overlap with.  Until round 3 these copies were bounded by the device buffer's size, not by the caller's: a buffer of
     // exactly the decoded length was overrun by up to a chunk -- which is what "threw inside the runtime" on small calls)
@@ -1124,26 +1075,28 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
     const bool to_host = h_dst && chunk_size != 0 && chunk_size <= kChunkMax && (long)nchunks >= tohost_min;
     const uint32_t batch_cap = to_host ? 4096u : 65536u; // (host output: batches small enough for copies and kernels to take turns)
     const uint32_t batch = (uint32_t)(nchunks < batch_cap ? nchunks : batch_cap);
-    InfStatus *status = static_cast<InfStatus *>(engine_scratch(e, (size_t)batch * sizeof(InfStatus) + 64));
-    if (!status) return engine_fail(e, ZGPU_MEM_ERROR, "inflate scratch");
+    if (e->inf_status.reserve(e, (size_t)batch * sizeof(InfStatus) + 64)) return ZGPU_MEM_ERROR;
+    InfStatus *status = reinterpret_cast<InfStatus *>(e->inf_status.p);
     uint64_t *acc = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(status) + (((size_t)batch * sizeof(InfStatus) + 15) & ~(size_t)15));
     const uint64_t max_pieces = (out_cap >> 16) + 2;
     const uint32_t cbatch_cap = (uint32_t)(max_pieces < 65536 ? max_pieces : 65536); // the checksum pass works on 64 KiB pieces of the OUTPUT
-    ChunkMeta *meta = engine_meta(e, batch > cbatch_cap ? batch : cbatch_cap);
-    if (!meta) return engine_fail(e, ZGPU_MEM_ERROR, "inflate meta");
+    // meta and the offsets scratch (below) are sized here for the decode AND for the checksum pass behind it, so that the pass never regrows a buffer
+    // the decode kernels were given
+    if (e->inf_meta.reserve(e, batch > cbatch_cap ? batch : cbatch_cap)) return ZGPU_MEM_ERROR;
+    ChunkMeta *meta = e->inf_meta;
     uint8_t *slots = nullptr;
-    if (compact) { slots = static_cast<uint8_t *>(engine_scratch2(e, (size_t)batch * kChunkMax + 256)); if (!slots) return engine_fail(e, ZGPU_MEM_ERROR, "inflate slots"); }
+    if (compact) { if (e->inf_slots.reserve(e, (size_t)batch * kChunkMax + 256)) return ZGPU_MEM_ERROR; slots = e->inf_slots; }
     res->adler32 = 1; res->crc32 = 0; res->first_bad_chunk = -1; res->error_code = 0; res->error_msg = 0; res->out_bytes = 0;
     res->in_used = in_bytes; res->in_used_bits = 0; res->stream_end = 0; res->incomplete = 0;
     ZGPU_HIP_CHECK(hipMemsetAsync(acc, 0, 8 * sizeof(uint64_t), st));
-    RunStateHostI rs{}; rs.adler_a = 1;
-    ZGPU_HIP_CHECK(hipMemcpyAsync(engine_run_state(e), &rs, sizeof rs, hipMemcpyHostToDevice, st));
+    RunState rs{}; rs.adler_a = 1;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(e->run, &rs, sizeof rs, hipMemcpyHostToDevice, st));
     // the ring: 32 KiB (every distance inside it), or -- chunks that go straight to their place in the destination, no dictionary in front -- a smaller
     // one with the far matches read back from the destination (more segments per CU).  ZGPU_INF_RING_KB=8|16|32 picks it.
     int ring_kb = ZGPU_INF_RING_DEFAULT_KB; // (read at every call: tests/test_gpu_inflate.py runs the same streams through all three)
     if (const char *v = getenv("ZGPU_INF_RING_KB")) ring_kb = atoi(v);
     if (ring_kb != 8 && ring_kb != 16) ring_kb = 32;
-    const int ring_here = (!compact && chunk_size != kWholeStream && engine_inflate_dict_len(e) == 0) ? ring_kb : 32;
+    const int ring_here = (!compact && chunk_size != kWholeStream && e->inf_dict_len == 0) ? ring_kb : 32;
     static bool opt_in = false;
     if (!opt_in) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLds));
@@ -1154,22 +1107,22 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
     hipEvent_t ev{};
     int rc_sum = 0;
     prof_span_begin(e, st, &ev);
-    uint64_t *oscr = engine_offsets_scratch(e, nchunks + 1 + (out_cap >> 16) + 2);
-    if (!oscr) return engine_fail(e, ZGPU_MEM_ERROR, "inflate offsets");
+    if (e->inf_offs.reserve(e, nchunks + 1 + (out_cap >> 16) + 2)) return ZGPU_MEM_ERROR;
+    uint64_t *oscr = e->inf_offs;
     for (uint64_t c0 = 0; c0 < nchunks; c0 += batch) {
         const uint32_t nb = (uint32_t)(nchunks - c0 < batch ? nchunks - c0 : batch);
         if (ring_here == 8)
             hipLaunchKernelGGL((inflate_kernel_t<false, 8192>), dim3(nb), dim3(128), sizeof(InflateLdsT<uint8_t, 8192>), st, d_in, in_bytes, d_offsets, c0, nb, last_chunk, chunk_size,
-                               d_out, out_cap, status, nullptr, engine_inflate_dict(e), 0u, kern_mode, SpecArgs{});
+                               d_out, out_cap, status, nullptr, e->inf_dict.p, 0u, kern_mode, SpecArgs{});
         else if (ring_here == 16)
             hipLaunchKernelGGL((inflate_kernel_t<false, 16384>), dim3(nb), dim3(128), sizeof(InflateLdsT<uint8_t, 16384>), st, d_in, in_bytes, d_offsets, c0, nb, last_chunk, chunk_size,
-                               d_out, out_cap, status, nullptr, engine_inflate_dict(e), 0u, kern_mode, SpecArgs{});
+                               d_out, out_cap, status, nullptr, e->inf_dict.p, 0u, kern_mode, SpecArgs{});
         else
         hipLaunchKernelGGL(inflate_kernel_t<false>, dim3(nb), dim3(128), sizeof(InflateLds), st, d_in, in_bytes, d_offsets, c0, nb, last_chunk, chunk_size,
-                           compact ? slots : d_out, out_cap, status, compact ? meta : nullptr, engine_inflate_dict(e), engine_inflate_dict_len(e), kern_mode, SpecArgs{});
+                           compact ? slots : d_out, out_cap, status, compact ? meta : nullptr, e->inf_dict.p, e->inf_dict_len, kern_mode, SpecArgs{});
         hipLaunchKernelGGL(inflate_reduce_kernel, dim3(1), dim3(1024), 0, st, status, nb, c0, chunk_size, acc, stream_mode, last_chunk, compact ? meta : nullptr, (uint32_t)kMsgTruncated);
         if (compact) {
-            launch_scan(meta, nb, c0, oscr, engine_run_state(e), out_cap, st); // out_bytes -> byte offsets, continuing across batches
+            launch_scan(meta, nb, c0, oscr, e->run, out_cap, st); // out_bytes -> byte offsets, continuing across batches
             launch_stitch(slots, meta, oscr, c0, nb, d_out, out_cap, kChunkMax, st);
         }
         ZGPU_HIP_CHECK(hipGetLastError());
@@ -1178,17 +1131,17 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
             ZGPU_HIP_CHECK(hipEventRecord(engine_copy_event(e, b), st));
             if (b > 0) {
                 const uint64_t lo = (c0 - batch) * chunk_size, hi = c0 * (uint64_t)chunk_size < host_cap ? c0 * (uint64_t)chunk_size : host_cap;
-                ZGPU_HIP_CHECK(hipStreamWaitEvent(engine_copy_stream(e), engine_copy_event(e, b - 1), 0));
-                if (hi > lo) ZGPU_HIP_CHECK(hipMemcpyAsync(h_dst + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, engine_copy_stream(e)));
+                ZGPU_HIP_CHECK(hipStreamWaitEvent(e->copy_stream, engine_copy_event(e, b - 1), 0));
+                if (hi > lo) ZGPU_HIP_CHECK(hipMemcpyAsync(h_dst + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, e->copy_stream));
             }
         }
     }
     if (to_host) {
         const size_t b = (size_t)((nchunks - 1) / batch);
         const uint64_t lo = b * (uint64_t)batch * chunk_size, hi = nchunks * (uint64_t)chunk_size < host_cap ? nchunks * (uint64_t)chunk_size : host_cap;
-        ZGPU_HIP_CHECK(hipStreamWaitEvent(engine_copy_stream(e), engine_copy_event(e, b), 0));
-        if (hi > lo) ZGPU_HIP_CHECK(hipMemcpyAsync(h_dst + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, engine_copy_stream(e)));
-        ZGPU_HIP_CHECK(hipStreamSynchronize(engine_copy_stream(e)));
+        ZGPU_HIP_CHECK(hipStreamWaitEvent(e->copy_stream, engine_copy_event(e, b), 0));
+        if (hi > lo) ZGPU_HIP_CHECK(hipMemcpyAsync(h_dst + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, e->copy_stream));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(e->copy_stream));
     }
     prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
     uint64_t h[8];
@@ -1199,8 +1152,8 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
         else if (h[7]) { res->incomplete = 1; res->in_used = h_offsets ? h_offsets[h[7] - 1] : 0; }
     }
     res->out_bytes = h[0]; res->first_bad_chunk = h[1] ? (int32_t)(h[1] - 1) : -1; res->error_code = (int32_t)(int64_t)h[2]; res->error_msg = (uint32_t)h[3];
-    if (h[1]) { engine_collect(e); return engine_fail(e, res->error_code, kInfMessages[res->error_msg < kMsgCount ? res->error_msg : 0]); }
-    if (h[0] > out_cap || (h_dst && h[0] > host_cap)) { engine_collect(e); return engine_fail(e, ZGPU_BUF_ERROR, "output capacity too small"); }
+    if (h[1]) { collect_spans(e); return fail(e, res->error_code, kInfMessages[res->error_msg < kMsgCount ? res->error_msg : 0]); }
+    if (h[0] > out_cap || (h_dst && h[0] > host_cap)) { collect_spans(e); return fail(e, ZGPU_BUF_ERROR, "output capacity too small"); }
     rc_sum = output_checksums(e, d_out, h[0], out_cap, res, st);
     if (rc_sum) return rc_sum;
     if (h_dst && !to_host && h[0]) { // a host destination that was not served batch by batch
@@ -1217,9 +1170,6 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
 // workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and the finish
 // kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.
 namespace zgpu {
-void launch_batch_finish(const BatchItemState *items, uint64_t n, const ChunkMeta *meta, const uint8_t *in, uint32_t do_adler, uint32_t do_crc,
-                         zgpu_inflate_item *out_items, unsigned long long *nfailed, hipStream_t st);
-
 __device__ inline uint32_t crc_bytes(uint32_t c, const uint8_t *p, uint64_t n) // crc32() of the reference (crc32.c:219), bit by bit: headers are short
 {
     c = ~c;
@@ -1339,9 +1289,9 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
     if (nfailed) *nfailed = 0;
     if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (checks & ~3u) || (n && (!d_in_off || !d_out_off || !d_items)) || (n && in_bytes && !d_in) || (n && out_cap && !d_out) ||
         n >= (1ull << 32))
-        return engine_fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
     if (n == 0) return ZGPU_OK;
-    ZGPU_HIP_CHECK(hipSetDevice(engine_device(e)));
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
     // the check each item's wrapper needs is always computed (AUTO: both), the others when asked for
     const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
     const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
@@ -1350,8 +1300,8 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_seg = 0, o_items = o_seg + al(n * 32), o_status = o_items + al(n * sizeof(BatchItemState)), o_cnt = o_status + al(n * sizeof(InfStatus)),
                  o_tab = o_cnt + 256, o_map = o_tab + al((max_pieces + n + 1) * 8), o_meta = o_map + al(max_pieces * 4), total = o_meta + al(max_pieces * sizeof(ChunkMeta));
-    uint8_t *scr = static_cast<uint8_t *>(engine_scratch(e, total));
-    if (!scr) return engine_fail(e, ZGPU_MEM_ERROR, "inflate batch scratch");
+    if (e->inf_status.reserve(e, total)) return ZGPU_MEM_ERROR;
+    uint8_t *scr = e->inf_status;
     uint64_t *seg = reinterpret_cast<uint64_t *>(scr + o_seg);
     BatchItemState *items = reinterpret_cast<BatchItemState *>(scr + o_items);
     InfStatus *status = reinterpret_cast<InfStatus *>(scr + o_status);
@@ -1388,7 +1338,7 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
     unsigned long long h[3] = {0, 0, 0};
     ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-    if (h[2]) { engine_collect(e); return engine_fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range"); }
+    if (h[2]) { collect_spans(e); return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range"); }
     if (h[0]) {
         ChunkGeom g{}; g.in = d_out; g.in_bytes = out_cap; g.seg_off = tab; g.chunk0 = 0; g.final_chunk = ~0ull; g.chunk_size = kChunkMax;
         g.nchunks = (uint32_t)h[0]; g.chunk_map = map;
@@ -1399,7 +1349,7 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
     ZGPU_HIP_CHECK(hipGetLastError());
     ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
-    engine_collect(e);
+    collect_spans(e);
     if (nfailed) *nfailed = h[1];
     return ZGPU_OK;
 }
@@ -1417,10 +1367,6 @@ __global__ void __launch_bounds__(256) marker_scan_kernel(const uint8_t *__restr
         }
     }
 }
-uint8_t *engine_stage_in(zgpu_engine *e);
-uint8_t *engine_stage_out(zgpu_engine *e);
-int engine_ensure_stage(zgpu_engine *e, uint64_t in_bytes, uint64_t out_bytes);
-hipStream_t engine_stream(zgpu_engine *e);
 } // namespace zgpu
 
 #include <algorithm>
@@ -1608,7 +1554,7 @@ __global__ void __launch_bounds__(64) spec_find_kernel(const uint8_t *__restrict
     // the bytes to scan come through LDS, kScanBytes at a time
     uint32_t *scan = reinterpret_cast<uint32_t *>(L.out);
     const uint4 *g128 = reinterpret_cast<const uint4 *>(in);
-    const uint64_t gvecs = (in_bytes + 15) >> 4; // (the allocation behind `in` is padded: engine_ensure_stage)
+    const uint64_t gvecs = (in_bytes + 15) >> 4; // (the allocation behind `in` is padded: ensure_stage)
     for (uint64_t blk = lo_bit; blk < hi_bit && result == ~0ull; blk += kScanBytes * 8) {
         wave_sync();
 #pragma unroll
@@ -1840,8 +1786,8 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
     const uint64_t fspacing = spacing / 4 < 16384 ? 16384 : (spacing / 4 + 4095) & ~4095ull;
     const uint32_t ntargets = (uint32_t)((in_bytes - 1) / fspacing);
     if (ntargets < 3 && !force) return 1;
-    uint64_t *d_found = static_cast<uint64_t *>(engine_scratch(e, (size_t)ntargets * 16 + 64));
-    if (!d_found) return engine_fail(e, ZGPU_MEM_ERROR, "inflate scratch");
+    if (e->inf_status.reserve(e, (size_t)ntargets * 16 + 64)) return ZGPU_MEM_ERROR;
+    uint64_t *d_found = reinterpret_cast<uint64_t *>(e->inf_status.p);
     static bool opt_in = false;
     if (!opt_in) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsSpec));
@@ -1912,7 +1858,7 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
         const size_t o_starts = carve((size_t)(nseg + 1) * 8), o_ends = carve((size_t)nseg * sizeof(SpecEnd)), o_ostart = carve((size_t)(nseg + 1) * 8),
                      o_status = carve((size_t)nseg * sizeof(InfStatus)), o_cnt = carve(64), o_owner = carve((size_t)page_cap * 8),
                      o_win = carve((size_t)nseg * kOutRing), o_entry = carve((size_t)(nseg / 8 + 2) * kOutRing), o_tails = carve((size_t)nseg * kOutRing * 2), o_mid = carve((size_t)page_cap * kOutHalf * 2);
-        uint8_t *base = static_cast<uint8_t *>(engine_scratch2(e, off));
+        uint8_t *base = e->inf_slots.reserve(nullptr, off) ? nullptr : e->inf_slots.p; // (declining is no error: no error text)
         if (!base) { prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev); return 1; } // (no room for the symbols: the slow way needs none)
         uint64_t *d_starts = reinterpret_cast<uint64_t *>(base + o_starts), *d_ostart = reinterpret_cast<uint64_t *>(base + o_ostart);
         SpecEnd *d_ends = reinterpret_cast<SpecEnd *>(base + o_ends);
@@ -1926,7 +1872,7 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
         ZGPU_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 64, st));
         ZGPU_HIP_CHECK(hipMemsetAsync(d_ends, 0xFF, (size_t)nseg * sizeof(SpecEnd), st));
         hipLaunchKernelGGL(inflate_kernel_t<true>, dim3(nseg), dim3(128), sizeof(InflateLdsSpec), st, d_in, in_bytes, d_starts, 0ull, nseg, ~0ull, kWholeStream,
-                           d_out, out_cap, reinterpret_cast<InfStatus *>(base + o_status), nullptr, engine_inflate_dict(e), engine_inflate_dict_len(e), 1u, sp);
+                           d_out, out_cap, reinterpret_cast<InfStatus *>(base + o_status), nullptr, e->inf_dict.p, e->inf_dict_len, 1u, sp);
         ZGPU_HIP_CHECK(hipGetLastError());
         std::vector<SpecEnd> ends(nseg);
         uint32_t cnt[2] = {0, 0};
@@ -1982,8 +1928,8 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
         if (total > out_cap) {
             prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
             res->out_bytes = total; res->first_bad_chunk = -1; res->error_code = ZGPU_BUF_ERROR; res->error_msg = 0;
-            engine_collect(e);
-            return engine_fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+            collect_spans(e);
+            return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
         }
         if (dry) { // the pool was sized from the guess: now the size is known
             if (attempt) { prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev); return 1; }
@@ -2007,7 +1953,7 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
             hipLaunchKernelGGL(spec_window_abs_kernel, dim3(used_seg), dim3(256), 0, st, sp.tails, used_seg, group, base + o_entry, base + o_win);
         }
         if (npages) hipLaunchKernelGGL(spec_resolve_kernel, dim3(npages), dim3(256), 0, st, sp.mid, sp.page_owner, npages, d_ends, used_seg, base + o_win, d_ostart,
-                                       engine_inflate_dict_len(e), d_out, out_cap, d_cnt + 4);
+                                       e->inf_dict_len, d_out, out_cap, d_cnt + 4);
         ZGPU_HIP_CHECK(hipGetLastError());
         uint32_t flag = 0;
         ZGPU_HIP_CHECK(hipMemcpyAsync(&flag, d_cnt + 4, 4, hipMemcpyDeviceToHost, st));
@@ -2032,44 +1978,45 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
 static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes, uint32_t flags, void *out, uint64_t out_cap, zgpu_inflate_result *res,
                                std::vector<uint64_t> *offsets_out, uint32_t start_bit = 0)
 {
-    if (!e || !in || !res || in_bytes == 0 || start_bit > 7) return engine_fail(e, ZGPU_STREAM_ERROR, "bad inflate arguments");
-    ZGPU_HIP_CHECK(hipSetDevice(engine_device(e)));
-    hipStream_t st = engine_stream(e);
+    if (!e || !in || !res || in_bytes == 0 || start_bit > 7) return fail(e, ZGPU_STREAM_ERROR, "bad inflate arguments");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
     const uint32_t stream_mode = (flags & ZGPU_INF_STREAM) ? 1u : 0u;
     if (start_bit) { // the stream goes on inside its first byte (behind the last whole piece of an earlier call): the pieces are the decoder that starts at a bit
-        int rc0 = engine_ensure_stage(e, in_bytes + 256, out_cap ? out_cap : 1); // (the input, then the offsets of the fallback below)
+        int rc0 = ensure_stage(e, in_bytes + 256, out_cap ? out_cap : 1); // (the input, then the offsets of the fallback below)
         if (rc0) return rc0;
-        uint8_t *d_in0 = engine_stage_in(e);
+        uint8_t *d_in0 = e->stage_in;
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_in0, in, in_bytes, hipMemcpyHostToDevice, st));
         // (ZGPU_SPEC_DECLINE_AT_BIT=1, tests: the pieces say "not this way" although the stream is whole)
-        const int src = getenv("ZGPU_SPEC_DECLINE_AT_BIT") ? 1 : inflate_spec_run(e, d_in0, static_cast<const uint8_t *>(in), in_bytes, engine_stage_out(e), out_cap, res, st, stream_mode, start_bit, true);
-        if (src == ZGPU_OK) { if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, engine_stage_out(e), res->out_bytes, hipMemcpyDeviceToHost)); return ZGPU_OK; }
+        const int src = getenv("ZGPU_SPEC_DECLINE_AT_BIT") ? 1 : inflate_spec_run(e, d_in0, static_cast<const uint8_t *>(in), in_bytes, e->stage_out, out_cap, res, st, stream_mode, start_bit, true);
+        if (src == ZGPU_OK) { if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost)); return ZGPU_OK; }
         if (src != 1) return src;
         // The pieces do not chain: damage, most likely, or a harmless reason (no scratch room, too many repairs of the chain -- stored blocks full of
         // what reads as headers --, a flag of the resolve pass).  The verdict is the one-workgroup decoder's, started at the same bit of the same bytes.
         // (Not on a copy shifted to bit 0: a stored block aligns to the bytes of the stream, and in the shifted copy it read its LEN from the wrong bits.)
-        if (in_bytes >= (1ull << 29)) return engine_fail(e, ZGPU_DATA_ERROR, "stream too long for the one-workgroup decoder");
+        if (in_bytes >= (1ull << 29)) return fail(e, ZGPU_DATA_ERROR, "stream too long for the one-workgroup decoder");
         const uint64_t h_offs[2] = {0, in_bytes};
         uint64_t *d_offs0 = reinterpret_cast<uint64_t *>(d_in0 + ((in_bytes + 127) & ~63ull));
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_offs0, h_offs, sizeof h_offs, hipMemcpyHostToDevice, st));
         g_whole_done++;
-        const int rc2 = inflate_run(e, d_in0, in_bytes, d_offs0, 1, kWholeStream, engine_stage_out(e), out_cap, res, st, stream_mode | (start_bit << 8), h_offs);
+        const int rc2 = inflate_run(e, d_in0, in_bytes, d_offs0, 1, kWholeStream, e->stage_out, out_cap, res, st, stream_mode | (start_bit << 8), h_offs);
         // stream mode: input that stops inside a block is not an error, nothing of it is taken (the stream still goes on at start_bit)
         if (stream_mode && ((rc2 == ZGPU_DATA_ERROR && res->error_msg == kMsgTruncated) || (rc2 == ZGPU_OK && res->incomplete))) {
             res->incomplete = 1; res->in_used = 0; res->in_used_bits = start_bit; res->out_bytes = 0; res->stream_end = 0; return ZGPU_OK;
         }
         if (rc2 != ZGPU_OK) return rc2;
-        if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, engine_stage_out(e), res->out_bytes, hipMemcpyDeviceToHost));
+        if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost));
         return ZGPU_OK;
     }
     const uint64_t max_cand = in_bytes / 5 + 2;
-    int rc = engine_ensure_stage(e, in_bytes + 64 + (max_cand + 2) * 2 * sizeof(uint64_t) + 64, out_cap ? out_cap : 1);
+    int rc = ensure_stage(e, in_bytes + 64 + (max_cand + 2) * 2 * sizeof(uint64_t) + 64, out_cap ? out_cap : 1);
     if (rc) return rc;
-    uint8_t *d_in = engine_stage_in(e);
+    uint8_t *d_in = e->stage_in;
     const uint64_t tab_off = (in_bytes + 127) & ~63ull;
     uint64_t *d_cand = reinterpret_cast<uint64_t *>(d_in + tab_off);          // candidates, later the offsets table
     uint64_t *d_offs = d_cand + max_cand + 2;
-    uint32_t *d_count = static_cast<uint32_t *>(engine_scratch(e, 64 * 1024));
+    if (e->inf_status.reserve(e, 64 * 1024)) return ZGPU_MEM_ERROR;
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(e->inf_status.p);
     ZGPU_HIP_CHECK(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, st));
     ZGPU_HIP_CHECK(hipMemsetAsync(d_count, 0, 4, st));
     hipLaunchKernelGGL(marker_scan_kernel, dim3(2048), dim3(256), 0, st, d_in, in_bytes, d_cand, (uint32_t)max_cand, d_count);
@@ -2092,10 +2039,10 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
     bool tried_pieces = false;
     if (ncand == 0 && in_bytes >= (1u << 20)) {
         tried_pieces = true;
-        const int src = inflate_spec_run(e, d_in, static_cast<const uint8_t *>(in), in_bytes, engine_stage_out(e), out_cap, res, st, stream_mode);
+        const int src = inflate_spec_run(e, d_in, static_cast<const uint8_t *>(in), in_bytes, e->stage_out, out_cap, res, st, stream_mode);
         if (src != 1) {
             if (src != ZGPU_OK) return src;
-            if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, engine_stage_out(e), res->out_bytes, hipMemcpyDeviceToHost));
+            if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost));
             if (offsets_out) *offsets_out = b;
             return ZGPU_OK;
         }
@@ -2107,7 +2054,7 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
     for (int pass = 0;; pass++) {
         const uint64_t nseg = b.size() - 1;
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_offs, b.data(), b.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        rc = inflate_run(e, d_in, in_bytes, d_offs, nseg, 0, engine_stage_out(e), out_cap, res, st, stream_mode, b.data(), open_end);
+        rc = inflate_run(e, d_in, in_bytes, d_offs, nseg, 0, e->stage_out, out_cap, res, st, stream_mode, b.data(), open_end);
         if (rc == ZGPU_OK) break;
         if (rc != ZGPU_DATA_ERROR) return rc;
         const bool last_bad = res->first_bad_chunk >= 0 && (uint64_t)res->first_bad_chunk + 1 == nseg;
@@ -2119,24 +2066,24 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
         break;
     }
     if (whole && !tried_pieces) {
-        const int src = inflate_spec_run(e, d_in, hin, in_bytes, engine_stage_out(e), out_cap, res, st, stream_mode);
+        const int src = inflate_spec_run(e, d_in, hin, in_bytes, e->stage_out, out_cap, res, st, stream_mode);
         if (src != 1 && src != ZGPU_OK) return src;
         whole = src == 1;
         if (!whole) b.assign({0, in_bytes});
     }
     if (whole) {
-        if (in_bytes >= (1ull << 29)) return engine_fail(e, ZGPU_DATA_ERROR, "stream too long for the one-workgroup decoder");
+        if (in_bytes >= (1ull << 29)) return fail(e, ZGPU_DATA_ERROR, "stream too long for the one-workgroup decoder");
         b.assign({0, in_bytes});
         g_whole_done++;
         ZGPU_HIP_CHECK(hipMemcpyAsync(d_offs, b.data(), b.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        rc = inflate_run(e, d_in, in_bytes, d_offs, 1, kWholeStream, engine_stage_out(e), out_cap, res, st, stream_mode, b.data());
+        rc = inflate_run(e, d_in, in_bytes, d_offs, 1, kWholeStream, e->stage_out, out_cap, res, st, stream_mode, b.data());
         if (rc != ZGPU_OK) {
             // stream mode: input that stops inside a block is not an error, nothing of it is taken (one workgroup cannot hand a window on)
             if (stream_mode && rc == ZGPU_DATA_ERROR && res->error_msg == kMsgTruncated) { res->incomplete = 1; res->in_used = 0; res->out_bytes = 0; res->stream_end = 0; return ZGPU_OK; }
             return rc;
         }
     }
-    if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, engine_stage_out(e), res->out_bytes, hipMemcpyDeviceToHost));
+    if (out && res->out_bytes) ZGPU_HIP_CHECK(hipMemcpy(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost));
     if (offsets_out) *offsets_out = b;
     return ZGPU_OK;
 }
@@ -2165,7 +2112,7 @@ int zgpu_inflate_find_chunks_host(zgpu_engine *e, const void *in, uint64_t in_by
         if (cap > cap_max) cap = cap_max;
     }
     if (rc) return rc;
-    if (b.size() - 1 > max_chunks) return engine_fail(e, ZGPU_BUF_ERROR, "offset table too small");
+    if (b.size() - 1 > max_chunks) return fail(e, ZGPU_BUF_ERROR, "offset table too small");
     for (size_t i = 0; i < b.size(); i++) offsets[i] = b[i];
     *nchunks = b.size() - 1;
     return ZGPU_OK;
@@ -2194,7 +2141,7 @@ int zgpu_inflate_batch_device(zgpu_engine *e, const void *d_in, uint64_t in_byte
                               void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream)
 {
     if (!e) return ZGPU_STREAM_ERROR;
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : engine_stream(e);
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
     return inflate_batch_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, checks, static_cast<uint8_t *>(d_out), out_cap,
                              d_out_offsets, d_items, nfailed, st);
 }
@@ -2207,19 +2154,19 @@ int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, c
 {
     if (!e) return ZGPU_STREAM_ERROR;
     if (nfailed) *nfailed = 0;
-    if (n && (!in_offsets || !out_offsets || !items || (in_bytes && !in) || (out_cap && !out))) return engine_fail(e, ZGPU_STREAM_ERROR, "null argument");
+    if (n && (!in_offsets || !out_offsets || !items || (in_bytes && !in) || (out_cap && !out))) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     if (n == 0) return ZGPU_OK;
     for (uint64_t k = 0; k < n; k++)
         if (in_offsets[k] > in_offsets[k + 1] || in_offsets[k + 1] > in_bytes || out_offsets[k] > out_offsets[k + 1] || out_offsets[k + 1] > out_cap)
-            return engine_fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
-    ZGPU_HIP_CHECK(hipSetDevice(engine_device(e)));
+            return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
     const uint64_t o_tab = (in_bytes + 255) & ~255ull, tab_bytes = (n + 1) * sizeof(uint64_t);
     const uint64_t o_items = o_tab + 2 * ((tab_bytes + 255) & ~255ull);
     const uint64_t lo = out_offsets[0], hi = out_offsets[n];
-    int rc = engine_ensure_stage(e, o_items + n * sizeof(zgpu_inflate_item), hi);
+    int rc = ensure_stage(e, o_items + n * sizeof(zgpu_inflate_item), hi);
     if (rc) return rc;
-    uint8_t *sin = engine_stage_in(e), *sout = engine_stage_out(e);
-    hipStream_t st = engine_stream(e);
+    uint8_t *sin = e->stage_in, *sout = e->stage_out;
+    hipStream_t st = e->stream;
     uint64_t *d_in_off = reinterpret_cast<uint64_t *>(sin + o_tab), *d_out_off = reinterpret_cast<uint64_t *>(sin + o_tab + ((tab_bytes + 255) & ~255ull));
     zgpu_inflate_item *d_items = reinterpret_cast<zgpu_inflate_item *>(sin + o_items);
     if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(sin, in, in_bytes, hipMemcpyHostToDevice, st));

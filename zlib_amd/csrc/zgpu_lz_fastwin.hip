@@ -24,6 +24,7 @@
 // windows in turn, each evaluating and walking its window ahead of the parse and only checking at its turn.  Exact, and slower: a wave two to
 // five windows ahead sees bits that are not there yet, 0.7-0.8 evaluations per window stay on the serial path.
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #include <cstdlib>
 
 #ifdef ZGPU_FW_TIME // timing builds only (scripts/build_variant.sh fwtime -DZGPU_FW_TIME; scripts/fw_time.py): cycles by phase, counts

@@ -22,13 +22,11 @@
 // reference turns into NIL when it slides the window (deflate.c:1309-1312); K3 applies it only once the slide has
 // happened.
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #include <cstdlib>
 #include "../../include/zamd_gpu.h"
 
 namespace zgpu {
-
-void prof_span_begin(void *eng, hipStream_t st, hipEvent_t *a);
-void prof_span_end(void *eng, hipStream_t st, int stage, hipEvent_t a);
 
 constexpr uint32_t kNoLink = 0; // links are stored as q+1 (q = position of the previous same-hash string), 0 = none
 constexpr uint32_t kTile = 8192, kRing = 40960; // ring >= MAX_DIST + tile: 40960 links = 80 KiB
@@ -441,8 +439,6 @@ __global__ void __launch_bounds__(64) parse_kernel(ChunkGeom g, LevelCfg cfg, co
     meta[c].ntok = ntok; meta[c].nostore = nostore; meta[c].in_bytes = n;
 }
 
-void launch_parse2(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st); // zgpu_lz_parse.hip
-
 void launch_parse(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st)
 {
     static int serial = -1; // ZGPU_PARSE=1: the lane-per-chunk restatement of the reference loop (kept as the cross-check)
@@ -451,7 +447,7 @@ void launch_parse(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t 
     else launch_parse2(g, cfg, recs, tokens, meta, st);
 }
 
-void launch_lz_parallel(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, void *prof)
+void launch_lz_parallel(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof)
 {
     uint16_t *links = static_cast<uint16_t *>(workspace);
     // records follow the links; links take batch*65536*2 bytes, the caller sized the workspace for its batch capacity

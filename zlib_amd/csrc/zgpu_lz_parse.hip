@@ -1,6 +1,7 @@
 // zgpu_lz_parse.hip -- the kernels around the parallel parse (zgpu_lz_parse.h, zgpu_lz_parse_body.inc): the deflate_slow parse over
 // match3's records, and its lite form over the games walk_kernel has played (used when the two are not fused, ZGPU_WALK_FUSE=0).
 #include "zgpu_lz_parse.h"
+#include "zgpu_engine.h"
 
 namespace zgpu {
 

@@ -13,6 +13,7 @@
 // position-0-matchable chunk, off = 32768 once the slide has happened.  An entry is the
 // reference's NIL exactly when its derived index is <= 0.
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #include <cstdlib>
 
 namespace zgpu {

@@ -19,6 +19,7 @@
 //                       candidate in the same step, full compares deferred to a per-wave stack and folded with atomic max
 //   K3                  parse2_kernel (zgpu_lz_parse.hip), or parse_kernel of zgpu_lz_parallel.hip with ZGPU_PARSE=1
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #define ZGPU_PARSE_HEADER_ONLY
 #include "zgpu_lz_parse.h"
 #include <cstdlib>
@@ -29,12 +30,6 @@ static std::atomic<int> g_inject_sort_fault{0};
 extern "C" __attribute__((visibility("default"))) void zgpu_debug_inject_sort_fault(void) { g_inject_sort_fault.store(1); }
 
 namespace zgpu {
-
-void prof_span_begin(void *eng, hipStream_t st, hipEvent_t *a);
-void prof_span_end(void *eng, hipStream_t st, int stage, hipEvent_t a);
-void launch_parse(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
-void launch_parse_lite(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
-void launch_lz_fastwin(const ChunkGeom &g, LevelCfg cfg, const uint16_t *S, const uint32_t *ir, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
 
 __device__ inline uint32_t lds_off(const void *p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p; }
 // wave-private LDS words by byte offset (plain C++ volatile accesses through a generic pointer compile to flat_* memory instructions)
@@ -1591,7 +1586,7 @@ __global__ void __launch_bounds__(64) fast_kernel(ChunkGeom g, LevelCfg cfg, con
 // `walk`: parse-driven search (walk_kernel + the lite parse) instead of the all-position search (match3_kernel + parse2_kernel)
 // `walk` 2: levels 1-3, deflate_fast on the sorted buckets (fast_kernel); `walk` 3: the same by a wave per chunk (zgpu_lz_fastwin.hip)
 // returns true when the sort has left the chunks' Adler-32 in meta[] (sort3_kernel does; the ballot-only sort does not)
-bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, void *prof, int exact_sort, int walk)
+bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, int walk)
 {
     bool adler_done = false;
     uint8_t *w = static_cast<uint8_t *>(workspace);
@@ -1668,10 +1663,9 @@ bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_
 }
 
 // A batch of tiles of a continuous stream (zgpu_cont.hip): sort, walkers + exit functions, the chain of entries, the tiles' tokens.
-void launch_chain(const uint16_t *exits, uint32_t ntiles, uint16_t *comp, uint16_t *gentry, uint16_t *entry, hipStream_t st);
-void launch_parse_tile(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, const TileGeom &tg, hipStream_t st);
+
 // the sort alone (levels 1-3 go on with fastwin_tile_kernel's rounds, zgpu_engine.hip): where S and ir of the batch's tiles are
-void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, void *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out)
+void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out)
 {
     uint8_t *w = static_cast<uint8_t *>(workspace);
     const size_t nch = g.nchunks;
@@ -1697,7 +1691,7 @@ void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hip
     *S_out = S; *ir_out = ir;
 }
 void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st,
-                     void *prof, int exact_sort)
+                     zgpu_engine *prof, int exact_sort)
 {
     uint8_t *w = static_cast<uint8_t *>(workspace);
     const size_t nch = g.nchunks;
@@ -1733,7 +1727,7 @@ void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void 
 }
 // ... and the tiles' tokens from their true entries: a launch of its own, so that it can run on another stream under the next batch's walkers (it is all
 // latency -- a window at a time, one wave threading the path -- and they are bound by the vector units: what the chunk path gets by fusing the two)
-void launch_lz_tiles_parse(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, void *prof)
+void launch_lz_tiles_parse(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof)
 {
     uint8_t *w = static_cast<uint8_t *>(workspace);
     const size_t nch = g.nchunks;

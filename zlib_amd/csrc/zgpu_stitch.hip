@@ -4,23 +4,13 @@
 // segment to its final byte offset ("stitching").  Segments end byte-aligned (flush marker / bi_windup), so
 // stitching is a byte copy, never a bit shift.  Also hosts the corpus generator kernel used by bench.py.
 #include "zgpu_common.h"
+#include "zgpu_engine.h"
 #include "corpus.h"
 #include "../../include/zamd_gpu.h"
 
 namespace zgpu {
 
 constexpr uint32_t kAdlerBase = 65521;
-
-// running totals carried across batches of one call (device memory)
-struct RunState {
-    uint64_t out_total; // bytes placed so far (starts at 2 when a zlib header is prepended)
-    uint64_t in_total;
-    uint64_t ntokens;
-    uint32_t adler_a, adler_b; // Adler-32 halves of all input so far (a starts at 1, b at 0)
-    uint32_t data_type;
-    uint32_t overflow;         // set when the output capacity was exceeded
-    uint32_t crc, pad;         // CRC-32 of all input so far (meaningful when the chunks' crc fields were filled)
-};
 
 // ---- Adler-32 of each chunk: A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521) ----
 __global__ void __launch_bounds__(256) adler_kernel(ChunkGeom g, ChunkMeta *meta)
