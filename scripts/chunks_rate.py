@@ -22,5 +22,5 @@ for level in levels:
         res = eng.deflate_device(src.data_ptr(), n, level, dst.data_ptr(), cap, flags=gpu.F_FINAL | gpu.F_ZLIB_WRAP, stream=st)
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 2
     pr = eng.profile_read(); eng.profile(False)
-    print("level %d chunks %.2f GiB: %7.1f ms = %6.2f GiB/s, out %d, stages/ms %s [lib %s fuse %s]" % (level, n / 2**30, dt * 1e3, n / dt / 2**30, res.out_bytes,
-          {k: round(v[0] / 2, 1) for k, v in pr.items() if v[1]}, os.path.basename(os.environ.get("ZAMD_GPU_LIB", "default")), os.environ.get("ZGPU_WALK_FUSE")), flush=True)
+    print("level %d chunks %.2f GiB: %7.1f ms = %6.2f GiB/s, out %d, stages/ms %s [lib %s]" % (level, n / 2**30, dt * 1e3, n / dt / 2**30, res.out_bytes,
+          {k: round(v[0] / 2, 1) for k, v in pr.items() if v[1]}, os.path.basename(os.environ.get("ZAMD_GPU_LIB", "default"))), flush=True)

@@ -1,7 +1,7 @@
 """GPU: the alternative kernel paths of the levels 4-9 pipeline must produce the same bytes as the default one.
 
-  ZGPU_SORT=1            sort_kernel (ballots only) instead of sort3_kernel (ordered LDS atomics + self-check)
-  ZTEST_SORT_FAULT=1 (read by the child script, which calls zgpu_debug_inject_sort_fault): sort3's self-check reports a fault -> the engine redoes the call with sort_kernel
+  ZGPU_SORT=1            sort_kernel (ballots only) instead of sort4_kernel (ordered LDS atomics + self-check)
+  ZTEST_SORT_FAULT=1 (read by the child script, which calls zgpu_debug_inject_sort_fault): sort4's self-check reports a fault -> the engine redoes the call with sort_kernel
   ZGPU_PARSE=1           parse_kernel (the reference loop, one lane per chunk) instead of parse2_kernel
 
 The switches are read once per process, so every variant runs in a child process (one at a time) and prints the
@@ -43,12 +43,12 @@ print("DIGESTS " + json.dumps(out, sort_keys=True))
 """ % ROOT
 
 
-def run_variant(env_extra):
+def run_variant(env_extra, child=CHILD):
     env = dict(os.environ)
     for k in ("ZGPU_SORT", "ZTEST_SORT_FAULT", "ZGPU_PARSE", "ZGPU_BATCH_CHUNKS"):
         env.pop(k, None)
     env.update(env_extra)
-    p = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, "-c", child], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("DIGESTS ")][-1]
     return json.loads(line[len("DIGESTS "):])
@@ -67,9 +67,48 @@ def test_alternative_paths_agree():
         assert got == base, "variant %r differs: %s" % (env, [k for k in base if got.get(k) != base[k]])
 
 
+CONT_BYTES = 100000
+CONT_LEVELS = (6, 1)  # 6: launch_lz_tiles (sort + walkers), 1: launch_sort_tiles (sort + the fastwin rounds)
+
+CONT_CHILD = r"""
+import hashlib, json, os, sys
+sys.path.insert(0, %r)
+from oracle import corpus_py as CP
+import zlib_amd
+from zlib_amd import gpu
+data = CP.chunks(0, 0, 2).tobytes()[:%d]
+F = gpu.F_FINAL | gpu.F_ZLIB_WRAP | gpu.F_CONTINUOUS
+out = {}
+for lvl in %r:
+    e = zlib_amd.Engine(0)  # (one per level: the fallback is sticky, and the injected fault is taken by the next self-checked sort)
+    if os.environ.get("ZTEST_SORT_FAULT"):
+        e.L.zgpu_debug_inject_sort_fault.restype = None
+        e.L.zgpu_debug_inject_sort_fault()
+    for call in ("first", "again"):
+        out["%%d/%%s" %% (lvl, call)] = hashlib.sha256(e.deflate_host(data, lvl, flags=F)).hexdigest()
+    e.close()
+print("DIGESTS " + json.dumps(out, sort_keys=True))
+""" % (ROOT, CONT_BYTES, CONT_LEVELS)
+
+
+def test_continuous_stream_survives_the_sort_selfcheck():
+    """The sort of a continuous stream's tiles (launch_lz_tiles at level 6, launch_sort_tiles at level 1) by its three routes: the default, the
+    ballot-only sort asked for (ZGPU_SORT=1), and the ballot-only sort after the self-check's word was raised (the engine redoes the feed and keeps
+    to that sort: the call after it must match too).  100 000 bytes of corpus 0 as one stream: four tiles, ragged at the end."""
+    from oracle import corpus_py as CP, oracle_py as O
+    data = CP.chunks(0, 0, 2).tobytes()[:CONT_BYTES]
+    want = {lvl: hashlib.sha256(O.cont_stream(data, lvl)).hexdigest() for lvl in CONT_LEVELS}
+    base = run_variant({}, CONT_CHILD)
+    for lvl in CONT_LEVELS:
+        assert base["%d/first" % lvl] == want[lvl] and base["%d/again" % lvl] == want[lvl], lvl
+    for env in ({"ZGPU_SORT": "1"}, {"ZTEST_SORT_FAULT": "1"}):
+        got = run_variant(env, CONT_CHILD)
+        assert got == base, "variant %r differs: %s" % (env, [k for k in base if got.get(k) != base[k]])
+
+
 def test_chunks_the_loop_hands_on_come_out_the_same(monkeypatch):
     """Levels 1-3, large calls: the lane-per-chunk loop gives chunks that do not compress to the wave-per-chunk kernel (lz_serial_chunk's hand_on, a list
-    launch of sort3 + fastwin over ChunkGeom::chunk_map).  Forced here at test size (ZGPU_HAND_ON=2): a call of compressible, incompressible and
+    launch of the sort + fastwin over ChunkGeom::chunk_map).  Forced here at test size (ZGPU_HAND_ON=2): a call of compressible, incompressible and
     half-and-half chunks, ragged at the end, against the same call with the hand-on switched off and against the oracle; the counter says it happened."""
     import ctypes as C
     import numpy as np

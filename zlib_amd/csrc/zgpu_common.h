@@ -15,6 +15,9 @@ constexpr uint32_t kMinMatch = 3, kMaxMatch = 258, kMinLookahead = kMaxMatch + k
 constexpr uint32_t kMaxDist = kWSize - kMinLookahead; // 32506
 constexpr uint32_t kTooFar = 4096;
 constexpr uint32_t kChunkMax = 65536;
+// S, the chunk's positions counting-sorted by hash (written by zgpu_lz_sorted.hip's sorts, read there and by zgpu_lz_fastwin.hip): u16 entries,
+// kSPad of them in front of every chunk's S (group loads may reach below index 0)
+constexpr uint32_t kSPad = 8, kSStride = kChunkMax + kSPad;
 constexpr uint32_t kBlockTokens = 16383;       // lit_bufsize-1: a block is cut after this many tokens
 constexpr uint32_t kSerialTableEntries = 32768 + 32768; // uint4 entries per chunk of the lane-per-chunk loop's tables: one per hash bucket, one per window position (1 MiB)
 constexpr uint32_t kGeoTableEntries = 65536 + 32768;   // the same at memLevel 9 / windowBits 15

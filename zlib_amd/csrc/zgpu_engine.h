@@ -144,16 +144,16 @@ void launch_parse(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t 
 
 // ---- zgpu_lz_parse.hip ----
 void launch_parse2(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
-void launch_parse_lite(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st);
 void launch_parse_tile(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, const TileGeom &tg, hipStream_t st);
 
 // ---- zgpu_lz_sorted.hip ----
 size_t lz_sorted_workspace_bytes(uint32_t batch_chunks);
 uint32_t *lz_sorted_fault_word(void *workspace);
-bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, int walk);
+bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort,
+                      int impl); // impl: ZGPU_LZ_SORTED, _WALK, _FAST or _FASTWIN
 // continuous stream
-void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st,
-                     zgpu_engine *prof, int exact_sort);
+void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st, zgpu_engine *prof,
+                     int exact_sort);
 void launch_lz_tiles_parse(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof);
 void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out);
 

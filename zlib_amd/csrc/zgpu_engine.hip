@@ -341,13 +341,13 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
                 ZGPU_HIP_CHECK(hipStreamSynchronize(st));
                 for (uint32_t at = 0; at < handed; at += hand_piece) {
                     ChunkGeom gl = g; gl.nchunks = handed - at < hand_piece ? handed - at : hand_piece; gl.chunk_map = e->hand_list + 1 + at;
-                    launch_lz_sorted(gl, cfg, e->par_ws, e->tokens, e->meta, st, e, e->exact_sort, 3);
+                    launch_lz_sorted(gl, cfg, e->par_ws, e->tokens, e->meta, st, e, e->exact_sort, ZGPU_LZ_FASTWIN);
                 }
                 e->handed_on += handed;
             }
         } else {
             if (impl == ZGPU_LZ_SORTED || impl == ZGPU_LZ_WALK || impl == ZGPU_LZ_FAST || impl == ZGPU_LZ_FASTWIN)
-                adler_done = launch_lz_sorted(g, cfg, e->par_ws, e->tokens, e->meta, st, e, e->exact_sort, impl == ZGPU_LZ_WALK ? 1 : impl == ZGPU_LZ_FAST ? 2 : impl == ZGPU_LZ_FASTWIN ? 3 : 0);
+                adler_done = launch_lz_sorted(g, cfg, e->par_ws, e->tokens, e->meta, st, e, e->exact_sort, impl);
             else launch_lz_parallel(g, cfg, e->par_ws, e->tokens, e->meta, st, e);
         }
         {
@@ -667,7 +667,7 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
         tg.exits = e->ct_exits + (size_t)set * batch * kTileExitStride;
         g.chunk0 = t0; g.nchunks = nb;
         if (pipe && kbatch >= 2) ZGPU_HIP_CHECK(hipStreamWaitEvent(st, e->ct_ev_b[set], 0)); // this set's buffers: the batch before last is done with them
-        if (nb && !fast_lz) launch_lz_tiles(g, tg, cfg, ws_set[set], tokens, tmeta, e->ct_comp, e->ct_gentry, st, e, e->exact_sort);
+        if (nb && !fast_lz) launch_lz_tiles(g, tg, cfg, ws_set[set], tmeta, e->ct_comp, e->ct_gentry, st, e, e->exact_sort);
         else if (nb && (rc = lz_tiles_fast(e, g, tg, cfg, st))) return rc;
         if (pipe) { ZGPU_HIP_CHECK(hipEventRecord(e->ct_ev_a[set], st)); ZGPU_HIP_CHECK(hipStreamWaitEvent(sb, e->ct_ev_a[set], 0)); }
         if (nb && !fast_lz) launch_lz_tiles_parse(g, tg, cfg, ws_set[set], tokens, tmeta, sb, e);

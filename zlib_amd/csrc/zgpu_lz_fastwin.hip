@@ -3,7 +3,7 @@
 //
 // The chains of deflate_fast depend on the parse: the strings inside a match longer than max_insert_length never enter them
 // (deflate.c:1510-1534).  So neither head[]/prev[] filled ahead of the parse nor the static chains of levels 4-9 apply.  What IS known ahead of
-// the parse is which positions share a hash: sort3_kernel has counting-sorted the positions by hash (S; idx(p), rank(p) in `ir`), the bucket
+// the parse is which positions share a hash: the sort (zgpu_lz_sorted.hip) has counting-sorted the positions by hash (S; idx(p), rank(p) in `ir`), the bucket
 // predecessors of p, nearest first, are S[idx-1], S[idx-2], ... S[idx-rank], and the chain of p is those of them that have been inserted.
 // "Inserted" is ONE BIT PER S INDEX, kept in LDS (8 KiB): the bits of p's 32 nearest predecessors are 32 consecutive bits -- one read, and
 // the first `max_chain_length` set ones are the chain.  The bytes the candidates are compared with come from a ring of the last 33 KiB of the
@@ -47,7 +47,6 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_fw_time(unsign
 
 namespace zgpu {
 
-constexpr uint32_t kSPadF = 8, kSStrideF = kChunkMax + kSPadF; // S layout of zgpu_lz_sorted.hip (kSPad entries in front of every chunk's S)
 constexpr uint32_t kFwRing = 34 * 1024;             // bytes of the chunk in LDS: MAX_DIST back, a window + MAX_MATCH ahead, filled 1 KiB at a time
 constexpr uint32_t kFwMirror = 48;                  // the ring's first bytes again behind its end: a 40-byte read (nice_match 32 + 8) may start at its last byte
 constexpr uint32_t kFwFlagWords = kChunkMax / 32 + 2;
@@ -130,7 +129,7 @@ __global__ void __launch_bounds__(64) fastwin_kernel(ChunkGeom g, uint32_t max_i
     chunk_span(g, c, lo, n);
     const uint8_t *src = g.in + lo;
     const uint64_t safe_end = g.in_bytes - lo;
-    const uint16_t *S = S_all + (size_t)c * kSStrideF + kSPadF;
+    const uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
     const uint32_t *ir = ir_all + (size_t)c * kChunkMax;
     const uint32_t cm = chunk_of(g, c); // (a launch over a list of chunks: input, tokens and meta are the listed chunk's, the sorted buckets are slot c's)
     uint32_t *tok = tokens + (size_t)cm * kChunkMax;
@@ -455,7 +454,7 @@ __global__ void __launch_bounds__(64) fastwin_tile_kernel(ChunkGeom g, TileGeom 
     tile_span(g, tg, c, wb, n, h0, h1, nent);
     const uint8_t *src = g.in + wb;
     const uint64_t safe_end = g.in_bytes - wb;
-    const uint16_t *S = S_all + (size_t)c * kSStrideF + kSPadF;
+    const uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
     const uint32_t *ir = ir_all + (size_t)c * kChunkMax;
     uint32_t *tok = tokens + (size_t)c * kChunkMax;
     const uint32_t base = (tg.abs0_nil && tg.abs0 + wb == 0) ? 0u : 1u, npos = n >= 3 ? n - 2 : 0;

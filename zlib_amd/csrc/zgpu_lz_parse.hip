@@ -1,5 +1,6 @@
 // zgpu_lz_parse.hip -- the kernels around the parallel parse (zgpu_lz_parse.h, zgpu_lz_parse_body.inc): the deflate_slow parse over
-// match3's records, and its lite form over the games walk_kernel has played (used when the two are not fused, ZGPU_WALK_FUSE=0).
+// match3's records, and its lite form over the games the walkers of a continuous stream's tiles have played (a chunk's walk_kernel<1> runs the
+// lite form itself, behind its walkers).
 #include "zgpu_lz_parse.h"
 #include "zgpu_engine.h"
 
@@ -28,11 +29,6 @@ __global__ void __launch_bounds__(1024, 8) parse2_kernel(ChunkGeom g, LevelCfg c
 void launch_parse2(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st)
 {
     hipLaunchKernelGGL((parse2_kernel<false, false>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, recs, nullptr, nullptr, tokens, meta, TileGeom{});
-}
-
-void launch_parse_lite(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st)
-{
-    hipLaunchKernelGGL((parse2_kernel<true, false>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, nullptr, gm, gs, tokens, meta, TileGeom{});
 }
 
 // a tile of a continuous stream: the games walk_kernel<2> has played, the entry the chain over the tiles' exits has found (zgpu_cont.hip)

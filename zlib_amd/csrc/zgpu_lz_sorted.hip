@@ -12,12 +12,15 @@
 // link ring in LDS (the match kernel needs only the 64 KiB chunk there, so two 1024-lane workgroups fit a CU instead
 // of one), no tiles and no per-tile barriers (any position can be searched at any time).
 //
-//   K1'' sort3_kernel   the sort: ranks by ordered LDS atomics under a wave token, scatter staged through LDS, self-check;
-//                       output S (u16 positions), one bit per S index marking bucket heads, heads_below per 64 indices
-//   K1'  sort_kernel    the same result with ballots only (6x slower): fallback when sort3's self-check fails, ZGPU_SORT=1
+//   K1c  sort4_kernel   the sort: ranks by ordered LDS atomics under a wave token, kept in registers, scatter staged through LDS,
+//                       self-check; output S (u16 positions), ir (idx | rank << 16 by position), one bit per S index marking
+//                       bucket heads, heads_below per 64 indices
+//   K1'  sort_kernel    the same result with ballots only (6x slower): fallback when sort4's self-check fails, ZGPU_SORT=1
 //   K2'' match3_kernel  one 1024-lane workgroup per chunk, a wave per 64 consecutive S entries, all lanes on their k-th
 //                       candidate in the same step, full compares deferred to a per-wave stack and folded with atomic max
 //   K3                  parse2_kernel (zgpu_lz_parse.hip), or parse_kernel of zgpu_lz_parallel.hip with ZGPU_PARSE=1
+//   K2w  walk_kernel    the default at levels 4-9: parse-driven search with the rest of the parse behind it (replaces K2'' + K3)
+//        fast_kernel    levels 1-3 (ZGPU_LZ_FAST): deflate_fast on the sorted buckets, one lane per chunk
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
 #define ZGPU_PARSE_HEADER_ONLY
@@ -43,16 +46,43 @@ __device__ inline void lds_st8(uint32_t a, uint32_t v) { asm volatile("ds_write_
 __device__ inline uint32_t lds_ld8(uint32_t a) { uint32_t v; asm volatile("ds_read_u8 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory"); return v; }
 
 constexpr uint32_t kSuperS = 1024;   // positions per superblock of the sort passes
-constexpr uint32_t kSPad = 8;        // entries in front of every chunk's S (group loads may reach below index 0)
-constexpr uint32_t kSStride = kChunkMax + kSPad;
-
-// workspace layout: 256-byte header (fault word) | S (u16) | rank, then idx, by position (u16) | bucket-head bits | records |
-// ir: idx | rank << 16 by position (u32; what walk_kernel looks a position up with)
 
 constexpr uint32_t kHeadWords = kChunkMax / 32;                  // dwords of bucket-head bits per chunk ...
 constexpr uint32_t kHeadStride = kHeadWords + kChunkMax / 64 / 2; // ... followed by one u16 per 64 S indices (dwords per chunk)
+constexpr uint32_t kGPad = 32, kGStride = kChunkMax + 2 * kGPad;  // fast_kernel's flag bytes per chunk, room in front for the group reads
 
-size_t lz_sorted_workspace_bytes(uint32_t batch) { return 256 + (size_t)batch * (kSStride * 2 + kChunkMax * 2 + kHeadStride * 4 + kChunkMax * 8 + kChunkMax * 4) + 1024; }
+// The workspace of a batch of chunks (host side): the one place that says where its arrays lie and how large it is.
+//   header (fault: the word the sort's self-check raises) | S (u16; kSStride per chunk, zgpu_common.h) | rk: sort_kernel's ranks by position (u16) |
+//   heads: bucket-head bits, heads_below | recs: match3's records (uint2 by position) | ir: idx | rank << 16 by position (u32; what the walkers
+//   and the levels 1-3 kernels look a position up with)
+// The records' memory serves whichever search runs: match3's records, the walkers' games gm (u32 by position) with the bitmaps gs (a bit by
+// position) behind them, or fast_kernel's flag bytes G.
+struct SortedWs {
+    static constexpr size_t kHeaderBytes = 256, kSBytes = kSStride * 2, kRkBytes = kChunkMax * 2, kHeadBytes = kHeadStride * 4, kRecBytes = kChunkMax * 8, kIrBytes = kChunkMax * 4;
+    static constexpr size_t kSlack = 1024; // S's end is rounded up to 256 bytes; the rest is margin
+    static_assert(kChunkMax * 4 + kChunkMax / 8 <= kRecBytes && kGStride <= kRecBytes, "gm + gs, and G, lie in the records' memory");
+    static size_t bytes(size_t nchunks) { return kHeaderBytes + nchunks * (kSBytes + kRkBytes + kHeadBytes + kRecBytes + kIrBytes) + kSlack; }
+
+    size_t nch;
+    uint32_t *fault; uint16_t *S, *rk; uint32_t *heads; uint2 *recs; uint32_t *ir;
+    SortedWs(void *workspace, size_t nchunks) : nch(nchunks)
+    {
+        uint8_t *p = static_cast<uint8_t *>(workspace);
+        auto take = [&p](size_t n) { uint8_t *at = p; p += n; return at; };
+        fault = reinterpret_cast<uint32_t *>(take(kHeaderBytes));
+        S = reinterpret_cast<uint16_t *>(take((nch * kSBytes + 255) & ~(size_t)255));
+        rk = reinterpret_cast<uint16_t *>(take(nch * kRkBytes));
+        heads = reinterpret_cast<uint32_t *>(take(nch * kHeadBytes));
+        recs = reinterpret_cast<uint2 *>(take(nch * kRecBytes));
+        ir = reinterpret_cast<uint32_t *>(take(nch * kIrBytes));
+    }
+    uint32_t *gm() const { return reinterpret_cast<uint32_t *>(recs); }
+    uint32_t *gs() const { return gm() + nch * kChunkMax; }
+    uint8_t *G() const { return reinterpret_cast<uint8_t *>(recs); }
+};
+
+size_t lz_sorted_workspace_bytes(uint32_t batch) { return SortedWs::bytes(batch); }
+uint32_t *lz_sorted_fault_word(void *workspace) { return SortedWs(workspace, 0).fault; }
 
 // For block w of 64 S indices (1024 lanes, lane w holds the 64 head bits of its block): the distance from index 64*w down
 // to the last bucket head below the block, 65535 if there is none (w == 0) or it is farther.  The rank of an S entry in
@@ -214,7 +244,7 @@ __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_
     }
 }
 
-// ------------------------------------------------------------------------------------------------- K1''
+// ------------------------------------------------------------------------------------------------- K1c
 // The default sort.  What makes a counting sort that keeps equal keys in position order sequential is the ranking,
 // rank(p) = count[h(p)]++ taken in position order.  On this hardware one LDS atomic instruction serves the lanes that
 // hit the same address in ascending lane order (scripts/micro/lds_atomic_order.hip: no exception in 5e10 lane-operations),
@@ -222,245 +252,75 @@ __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_
 // 16-bit counts per word; the add is 1 or 1<<16), and all that has to be sequenced is the order in which the 16 waves of
 // the workgroup issue their instructions: a token in LDS walks round the waves, a turn is 8 instructions (512 positions)
 // followed by the token store -- same wave, same queue, so the next holder's atomics arrive behind them.  Hashes are
-// computed, and ranks stored, outside the turn.
+// computed, and ranks taken over, outside the turn.
 // The lane order inside an atomic is an observed property, not an architected one: pass V checks the result (a bucket
 // must ascend), and a violation makes the engine redo the call with sort_kernel above, which relies on ballots only.
-// Output: S (positions, u16) and one bit per S index that marks the first entry of a bucket -- the rank of an entry in its
-// bucket, which bounds its chain, is its distance from the last marked index.
-#ifdef ZGPU_S3_STOP // timing builds only (scripts/sweep_variants.sh): leave after phase N with a trivially valid S (no candidates anywhere)
-#define S3_STOP(N) do { if (ZGPU_S3_STOP == N) { for (uint32_t i_ = tid; i_ < kChunkMax; i_ += kS3Threads) { S[i_] = (uint16_t)i_; if (i_ < kHeadStride) hd[i_] = ~0u; } return; } } while (0)
-#else
-#define S3_STOP(N) do { } while (0)
-#endif
-#ifndef ZGPU_S3_BATCH
-#define ZGPU_S3_BATCH 8 // positions a lane has in flight in the index and scatter passes (A/B builds: scripts/build_variant.sh NAME -DZGPU_S3_BATCH=n)
-#endif
-constexpr uint32_t kS3Threads = 1024, kS3Waves = kS3Threads / 64, kS3TurnSteps = 8, kS3TurnPos = 64 * kS3TurnSteps, kS3Batch = ZGPU_S3_BATCH;
+// Output: S (positions, u16), ir (idx | rank << 16 by position) and one bit per S index that marks the first entry of a
+// bucket -- the rank of an entry in its bucket, which bounds its chain, is its distance from the last marked index.
+//
+// A lane keeps ITS positions through all passes -- the 64 of pass A's turns (turn T = wave + 16 j, step u: position
+// 512 T + 64 u + lane) -- one register each: the hash, then hash | rank << 16, then the position's `ir` word, from which pass
+// C1 scatters.  The input is read once, and what goes to HBM is S, ir and the head bits.  (The kernel's first form kept the
+// ranks in a scratch array by position, because a lane's passes worked on different positions: 43 GB of the sort's 77 GB per
+// 4 GiB went there and back.  DESIGN.md, K1'' and K1''', has the history.)
+//   pass A   rank(p): the token round.  The chunk's Adler-32 rides along: the pass has every byte of the chunk in a register once,
+//            and the kernel is waiting for the LDS, not for the vector unit -- a kernel of its own re-read the input for 0.7 ms per 4 GiB.
+//   pass B   exclusive scan of the 32768 counts -> bucket starts, in place (the count of hash h is half (h & 1) of word h >> 1);
+//            32 consecutive counts, four 16-byte vectors, per lane.
+//   pass C0  idx(p) = start(hash) + rank: the position's ir word, written and kept; a bit per bucket head.
+//   pass C1  the scatter itself, through LDS (a scattered 2-byte store to HBM costs a whole partial line): the half of S with
+//            idx >> 15 == half is assembled in the memory of the dead count table and written out in order, 16 bytes per lane and step.
+//   pass V   the self-check, on those 16 bytes as they go out: inside a bucket the positions must ascend.
+// Continuous stream: positions in front of earlier flush points have three bytes but are in no chain -- no rank, no place in S
+// (kNone32 in the lane's register, as for the positions the chunk does not have).
+constexpr uint32_t kS4Threads = 1024, kS4Waves = kS4Threads / 64, kS4TurnSteps = 8, kS4TurnPos = 64 * kS4TurnSteps;
 struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
 __device__ inline uint32_t lds_add_rtn32_nowait(uint32_t a, uint32_t v) { uint32_t o; asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(v) : "memory"); return o; }
 
-__global__ void __launch_bounds__(kS3Threads) sort3_kernel(ChunkGeom g, uint16_t *__restrict__ S_all, uint16_t *__restrict__ rank_all, uint32_t *__restrict__ heads_all,
-                                                           uint32_t *__restrict__ fault, uint32_t *__restrict__ ir_all, ChunkMeta *__restrict__ meta)
+__global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t *__restrict__ S_all, uint32_t *__restrict__ heads_all, uint32_t *__restrict__ fault,
+                                                           uint32_t *__restrict__ ir_all, ChunkMeta *__restrict__ meta)
 {
-    // (the chunk's Adler-32 rides along: pass A has every byte of the chunk in a register once, and the kernel is waiting for the LDS, not for
-    // the vector unit -- a kernel of its own re-read the input for 0.7 ms per 4 GiB)
-    __shared__ uint32_t ad1[kS3Waves];
-    __shared__ uint64_t ad2[kS3Waves];
+    __shared__ uint32_t ad1[kS4Waves];
+    __shared__ uint64_t ad2[kS4Waves];
     __shared__ __attribute__((aligned(16))) uint32_t cnt[kHashSize / 2]; // count of hash h in half (h & 1) of word h >> 1; later the bucket starts
-    __shared__ uint32_t wave_tot[kS3Waves];
+    __shared__ uint32_t wave_tot[kS4Waves];
     __shared__ uint32_t token;
     __shared__ __attribute__((aligned(8))) uint32_t heads[kChunkMax / 32]; // bit i: S[i] is the first entry of its bucket
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t lo; uint32_t n;
     chunk_span(g, c, lo, n);
     const uint8_t *src = g.in + lo;
-    uint16_t *S = S_all + (size_t)c * kSStride + kSPad, *rk = rank_all + (size_t)c * kChunkMax;
+    uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
     uint32_t *hd = heads_all + (size_t)c * kHeadStride, *ir = ir_all + (size_t)c * kChunkMax;
     if (threadIdx.x < kSPad) S[-(int)kSPad + (int)threadIdx.x] = 0; // the pad reads as "position 0" (match3's finished lanes)
     uint32_t last_of_half0 = 0;
-    const uint32_t npos = n >= 3 ? n - 2 : 0, nturns = (npos + kS3TurnPos - 1) / kS3TurnPos;
-    // continuous stream: positions in front of earlier flush points have three bytes but are in no chain: no rank, no place in S (marker 0xffff in rk)
+    const uint32_t npos = n >= 3 ? n - 2 : 0, nturns = (npos + kS4TurnPos - 1) / kS4TurnPos;
+    // (continuous stream: the positions of the chunk that are in no chain, and those that are)
     const uint32_t nout = g.nexcl ? excl_lower(g, lo + npos) - excl_lower(g, lo) : 0u, nin = npos - nout;
     const uint32_t cnt_a = lds_off(cnt), tok_a = lds_off(&token);
     {
         uint4 *z = reinterpret_cast<uint4 *>(cnt);
-        for (uint32_t i = tid; i < kHashSize * 2 / 16; i += kS3Threads) z[i] = make_uint4(0, 0, 0, 0);
+        for (uint32_t i = tid; i < kHashSize * 2 / 16; i += kS4Threads) z[i] = make_uint4(0, 0, 0, 0);
         if (tid == 0) token = 0;
-        for (uint32_t i = tid; i < kChunkMax / 32; i += kS3Threads) heads[i] = 0;
+        for (uint32_t i = tid; i < kChunkMax / 32; i += kS4Threads) heads[i] = 0;
     }
     __syncthreads();
-    S3_STOP(0);
     auto bytes3 = [&](uint32_t p) -> uint32_t { // b0 | b1<<8 | b2<<16 of position p < npos
         if (p + 4 <= n) return reinterpret_cast<const U32u *>(src + p)->v & 0xffffffu;
         return (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16);
     };
     auto hash_of = [](uint32_t v) { return hash3(v & 255u, (v >> 8) & 255u, v >> 16); };
-
-    // ---- pass A: rank(p) ----
-    {
-        uint32_t hv[kS3TurnSteps];
-        uint32_t s1 = 0, s2 = 0; // Adler: sum of this lane's bytes, and of (n - p) * byte (64 positions a lane: below 2^32)
-        auto preload = [&](uint32_t T) {
-#pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) {
-                const uint32_t p = T * kS3TurnPos + 64 * u + lane, v = p < npos ? bytes3(p) : 0u;
-                hv[u] = p < npos ? hash_of(v) : ~0u;
-                if (nout && p < npos && excl_has(g, lo + p)) { hv[u] = ~0u; rk[p] = 0xffffu; }
-                s1 += v & 255u; s2 += (n - p) * (v & 255u);
-            }
-        };
-        if (wave < nturns) preload(wave);
-#pragma unroll 1
-        for (uint32_t T = wave; T < nturns; T += kS3Waves) {
-            uint32_t aa[kS3TurnSteps], vv[kS3TurnSteps], old[kS3TurnSteps]; // nothing but the atomics happens while the token is held
-#pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) {
-                const bool ok = hv[u] != ~0u;
-                aa[u] = cnt_a + (ok ? (hv[u] >> 1) << 2 : 0);
-                vv[u] = ok ? 1u << ((hv[u] & 1u) << 4) : 0; // adding 0 is harmless
-            }
-            while (lds_ld32(tok_a) != T) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) old[u] = lds_add_rtn32_nowait(aa[u], vv[u]);
-            lds_st32(tok_a, T + 1);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(old[0]), "+v"(old[1]), "+v"(old[2]), "+v"(old[3]), "+v"(old[4]), "+v"(old[5]), "+v"(old[6]), "+v"(old[7])::"memory");
-            static_assert(kS3TurnSteps == 8, "the wait names eight results");
-#pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) {
-                const uint32_t p = T * kS3TurnPos + 64 * u + lane;
-                if (hv[u] != ~0u) rk[p] = (uint16_t)(old[u] >> ((hv[u] & 1u) << 4));
-            }
-            if (T + kS3Waves < nturns) preload(T + kS3Waves);
-        }
-        uint64_t t2 = s2;
-        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o); t2 += __shfl_down(t2, o); }
-        if (lane == 0) { ad1[wave] = s1; ad2[wave] = t2; }
-    }
-    __syncthreads();
-    if (tid == 0) { // A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521); the last two bytes start no three-byte string and are added here
-        uint64_t a = 1, b = n;
-        for (uint32_t w = 0; w < kS3Waves; w++) { a += ad1[w]; b += ad2[w] % 65521u; }
-        for (uint32_t p = npos; p < n; p++) { a += src[p]; b += (uint64_t)(n - p) * src[p]; }
-        ChunkMeta &mc = meta[chunk_of(g, c)];
-        mc.adler_a = (uint32_t)(a % 65521u); mc.adler_b = (uint32_t)(b % 65521u); mc.in_bytes = n;
-    }
-    S3_STOP(1);
-
-    // ---- pass B: exclusive scan of the 32768 counts -> bucket starts (in place); 32 consecutive counts per lane ----
-    {
-        constexpr uint32_t per = kHashSize / kS3Threads, nv = per * 2 / 16; // counts and 16-byte vectors per lane
-        static_assert(per % 8 == 0, "a lane scans whole 16-byte vectors");
-        uint4 *c4 = reinterpret_cast<uint4 *>(cnt) + tid * nv;
-        uint32_t v[nv * 4], sum = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < nv; i++) { const uint4 q = c4[i]; v[4 * i] = q.x; v[4 * i + 1] = q.y; v[4 * i + 2] = q.z; v[4 * i + 3] = q.w; }
-#pragma unroll
-        for (uint32_t i = 0; i < nv * 4; i++) sum += (v[i] & 0xffffu) + (v[i] >> 16);
-        uint32_t x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if ((int)lane >= d) x += y; }
-        if (lane == 63) wave_tot[wave] = x;
-        __syncthreads();
-        uint32_t basev = x - sum;
-        for (uint32_t w = 0; w < wave; w++) basev += wave_tot[w];
-#pragma unroll
-        for (uint32_t i = 0; i < nv * 4; i++) {
-            const uint32_t c0 = v[i] & 0xffffu, c1 = v[i] >> 16;
-            v[i] = (basev & 0xffffu) | ((basev + c0) << 16);
-            basev += c0 + c1;
-        }
-#pragma unroll
-        for (uint32_t i = 0; i < nv; i++) c4[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-    }
-    __syncthreads();
-    S3_STOP(2);
-
-    // ---- pass C0: idx(p) = start(hash) + rank, kept in place of the rank; a bit per bucket head ----
-    const uint16_t *start = reinterpret_cast<const uint16_t *>(cnt);
-    for (uint32_t i0 = 0; i0 < npos; i0 += kS3Threads * kS3Batch) {
-        uint32_t bv[kS3Batch], rv[kS3Batch];
-#pragma unroll
-        for (uint32_t u = 0; u < kS3Batch; u++) { const uint32_t p = i0 + u * kS3Threads + tid; bv[u] = p < npos ? bytes3(p) : 0; rv[u] = p < npos ? rk[p] : 0; }
-#pragma unroll
-        for (uint32_t u = 0; u < kS3Batch; u++) {
-            const uint32_t p = i0 + u * kS3Threads + tid;
-            if (p < npos && rv[u] != 0xffffu) {
-                const uint32_t id = (uint32_t)start[hash_of(bv[u])] + rv[u];
-                rk[p] = (uint16_t)id;
-                ir[p] = id | (rv[u] << 16);
-                if (rv[u] == 0) atomicOr(&heads[id >> 5], 1u << (id & 31u));
-            }
-        }
-    }
-    __syncthreads();
-    S3_STOP(3);
-    for (uint32_t i = tid; i < kChunkMax / 32; i += kS3Threads) hd[i] = heads[i];
-    reinterpret_cast<uint16_t *>(hd + kHeadWords)[tid] = (uint16_t)heads_below(reinterpret_cast<const unsigned long long *>(heads)[tid], tid, wave_tot);
-
-    // ---- pass C1: the scatter itself, through LDS (a scattered 2-byte store to HBM costs a whole partial line): the half of S
-    //      with idx >> 15 == half is assembled in the memory of the dead count table and written out in order ----
-    uint16_t *stage = reinterpret_cast<uint16_t *>(cnt);
-    bool bad = false;
-    for (uint32_t half = 0; half < 2 && half * 32768u < nin; half++) {
-        __syncthreads(); // the table (pass C0), or the previous half's write-out, is done with this memory
-        for (uint32_t i0 = 0; i0 < npos; i0 += kS3Threads * kS3Batch) {
-            uint32_t iv[kS3Batch];
-#pragma unroll
-            for (uint32_t u = 0; u < kS3Batch; u++) { const uint32_t p = i0 + u * kS3Threads + tid; iv[u] = p < npos ? rk[p] : ~0u; }
-#pragma unroll
-            for (uint32_t u = 0; u < kS3Batch; u++) if ((iv[u] >> 15) == half && iv[u] != 0xffffu) stage[iv[u] & 32767u] = (uint16_t)(i0 + u * kS3Threads + tid);
-        }
-        __syncthreads();
-        const uint32_t cntH = nin - half * 32768u < 32768u ? nin - half * 32768u : 32768u; // entries of this half
-        for (uint32_t v = tid; v * 8 < cntH; v += kS3Threads) { // 8 entries = 16 bytes per lane and step
-            const uint4 q = reinterpret_cast<const uint4 *>(stage)[v];
-            *reinterpret_cast<uint4 *>(S + half * 32768u + v * 8) = q; // S is 16-byte aligned (kSPad); the tail past npos is don't-care
-            // pass V: inside a bucket the positions must ascend (the lane order of the LDS atomic, see above)
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-            const uint32_t hb = (heads[(half * 32768u + v * 8) >> 5] >> ((v * 8) & 31u)) & 0xffu;
-            uint32_t prev = v ? stage[v * 8 - 1] : (half ? last_of_half0 : 0);
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint32_t cur = (w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                if (v * 8 + j < cntH && !((hb >> j) & 1u) && prev >= cur) bad = true;
-                prev = cur;
-            }
-        }
-        if (half == 0 && nin > 32768u) { __syncthreads(); last_of_half0 = stage[32767]; } // (uniform branch)
-    }
-    if (bad) atomicOr(fault, 1u);
-}
-
-// ------------------------------------------------------------------------------------------------- K1c (round 4)
-// sort3_kernel with the ranks kept where they are made.  sort3 writes every position's rank to HBM in pass A (rk[]), reads it back and rewrites it as the
-// index in pass C0 (which also reads the input a second time for the hashes), and reads the index twice more in pass C1: 43 GB of the sort's 77 GB per 4 GiB,
-// for a scratch array that exists only because a lane's passes work on different positions.  Here a lane keeps ITS positions through all passes -- the 64 of
-// pass A's turns (turn T = wave + 16 j, step u: position 512 T + 64 u + lane) -- one register each: hash, then hash | rank << 16, then the position's `ir` word
-// (index | rank << 16), from which pass C1 scatters.  The input is read once, rk[] is not touched, what goes to HBM is S and ir.  Same token round, same
-// self-check, same results (tests/test_gpu_deflate.py runs every golden vector through it; ZGPU_SORT=3 is the older kernel).
-__global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t *__restrict__ S_all, uint32_t *__restrict__ heads_all, uint32_t *__restrict__ fault,
-                                                           uint32_t *__restrict__ ir_all, ChunkMeta *__restrict__ meta)
-{
-    __shared__ uint32_t ad1[kS3Waves];
-    __shared__ uint64_t ad2[kS3Waves];
-    __shared__ __attribute__((aligned(16))) uint32_t cnt[kHashSize / 2];
-    __shared__ uint32_t wave_tot[kS3Waves];
-    __shared__ uint32_t token;
-    __shared__ __attribute__((aligned(8))) uint32_t heads[kChunkMax / 32];
-    const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint64_t lo; uint32_t n;
-    chunk_span(g, c, lo, n);
-    const uint8_t *src = g.in + lo;
-    uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
-    uint32_t *hd = heads_all + (size_t)c * kHeadStride, *ir = ir_all + (size_t)c * kChunkMax;
-    if (threadIdx.x < kSPad) S[-(int)kSPad + (int)threadIdx.x] = 0;
-    uint32_t last_of_half0 = 0;
-    const uint32_t npos = n >= 3 ? n - 2 : 0, nturns = (npos + kS3TurnPos - 1) / kS3TurnPos;
-    const uint32_t nout = g.nexcl ? excl_lower(g, lo + npos) - excl_lower(g, lo) : 0u, nin = npos - nout;
-    const uint32_t cnt_a = lds_off(cnt), tok_a = lds_off(&token);
-    {
-        uint4 *z = reinterpret_cast<uint4 *>(cnt);
-        for (uint32_t i = tid; i < kHashSize * 2 / 16; i += kS3Threads) z[i] = make_uint4(0, 0, 0, 0);
-        if (tid == 0) token = 0;
-        for (uint32_t i = tid; i < kChunkMax / 32; i += kS3Threads) heads[i] = 0;
-    }
-    __syncthreads();
-    auto bytes3 = [&](uint32_t p) -> uint32_t {
-        if (p + 4 <= n) return reinterpret_cast<const U32u *>(src + p)->v & 0xffffffu;
-        return (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16);
-    };
-    auto hash_of = [](uint32_t v) { return hash3(v & 255u, (v >> 8) & 255u, v >> 16); };
-    constexpr uint32_t kTurnsPerWave = kChunkMax / kS3TurnPos / kS3Waves; // 8
+    constexpr uint32_t kTurnsPerWave = kChunkMax / kS4TurnPos / kS4Waves; // 8
     constexpr uint32_t kNone32 = 0xffffffffu;
-    uint32_t pk[kTurnsPerWave][kS3TurnSteps]; // this lane's 64 positions: hash -> hash | rank << 16 -> index | rank << 16; kNone32: no position, or not in the chains
+    uint32_t pk[kTurnsPerWave][kS4TurnSteps]; // this lane's 64 positions: hash -> hash | rank << 16 -> index | rank << 16; kNone32: no position, or not in the chains
 
     // ---- pass A: rank(p) ----
     {
-        uint32_t s1 = 0, s2 = 0;
-        auto preload = [&](uint32_t T, uint32_t (&h)[kS3TurnSteps]) {
+        uint32_t s1 = 0, s2 = 0; // Adler: sum of this lane's bytes, and of (n - p) * byte (64 positions a lane: below 2^32)
+        auto preload = [&](uint32_t T, uint32_t (&h)[kS4TurnSteps]) {
 #pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) {
-                const uint32_t p = T * kS3TurnPos + 64 * u + lane, v = p < npos ? bytes3(p) : 0u;
+            for (uint32_t u = 0; u < kS4TurnSteps; u++) {
+                const uint32_t p = T * kS4TurnPos + 64 * u + lane, v = p < npos ? bytes3(p) : 0u;
                 h[u] = p < npos ? hash_of(v) : kNone32;
                 if (nout && p < npos && excl_has(g, lo + p)) h[u] = kNone32;
                 s1 += v & 255u; s2 += (n - p) * (v & 255u);
@@ -469,29 +329,30 @@ __global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t
 #pragma unroll
         for (uint32_t j = 0; j < kTurnsPerWave; j++)
 #pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) pk[j][u] = kNone32;
+            for (uint32_t u = 0; u < kS4TurnSteps; u++) pk[j][u] = kNone32;
         if (wave < nturns) preload(wave, pk[0]);
 #pragma unroll
         for (uint32_t j = 0; j < kTurnsPerWave; j++) {
-            const uint32_t T = wave + j * kS3Waves;
+            const uint32_t T = wave + j * kS4Waves;
             __builtin_amdgcn_sched_barrier(0);
             if (T < nturns) { // (uniform)
-                uint32_t aa[kS3TurnSteps], vv[kS3TurnSteps], old[kS3TurnSteps];
+                uint32_t aa[kS4TurnSteps], vv[kS4TurnSteps], old[kS4TurnSteps]; // nothing but the atomics happens while the token is held
 #pragma unroll
-                for (uint32_t u = 0; u < kS3TurnSteps; u++) {
+                for (uint32_t u = 0; u < kS4TurnSteps; u++) {
                     const bool ok = pk[j][u] != kNone32;
                     aa[u] = cnt_a + (ok ? (pk[j][u] >> 1) << 2 : 0);
-                    vv[u] = ok ? 1u << ((pk[j][u] & 1u) << 4) : 0;
+                    vv[u] = ok ? 1u << ((pk[j][u] & 1u) << 4) : 0; // adding 0 is harmless
                 }
                 while (lds_ld32(tok_a) != T) __builtin_amdgcn_s_sleep(1);
 #pragma unroll
-                for (uint32_t u = 0; u < kS3TurnSteps; u++) old[u] = lds_add_rtn32_nowait(aa[u], vv[u]);
+                for (uint32_t u = 0; u < kS4TurnSteps; u++) old[u] = lds_add_rtn32_nowait(aa[u], vv[u]);
                 lds_st32(tok_a, T + 1);
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(old[0]), "+v"(old[1]), "+v"(old[2]), "+v"(old[3]), "+v"(old[4]), "+v"(old[5]), "+v"(old[6]), "+v"(old[7])::"memory");
+                static_assert(kS4TurnSteps == 8, "the wait names eight results");
 #pragma unroll
-                for (uint32_t u = 0; u < kS3TurnSteps; u++)
+                for (uint32_t u = 0; u < kS4TurnSteps; u++)
                     if (pk[j][u] != kNone32) pk[j][u] |= ((old[u] >> ((pk[j][u] & 1u) << 4)) & 0xffffu) << 16;
-                if (j + 1 < kTurnsPerWave && T + kS3Waves < nturns) preload(T + kS3Waves, pk[j + 1 < kTurnsPerWave ? j + 1 : j]);
+                if (j + 1 < kTurnsPerWave && T + kS4Waves < nturns) preload(T + kS4Waves, pk[j + 1 < kTurnsPerWave ? j + 1 : j]);
             }
         }
         uint64_t t2 = s2;
@@ -499,9 +360,9 @@ __global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t
         if (lane == 0) { ad1[wave] = s1; ad2[wave] = t2; }
     }
     __syncthreads();
-    if (tid == 0) {
+    if (tid == 0) { // A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521); the last two bytes start no three-byte string and are added here
         uint64_t a = 1, b = n;
-        for (uint32_t w = 0; w < kS3Waves; w++) { a += ad1[w]; b += ad2[w] % 65521u; }
+        for (uint32_t w = 0; w < kS4Waves; w++) { a += ad1[w]; b += ad2[w] % 65521u; }
         for (uint32_t p = npos; p < n; p++) { a += src[p]; b += (uint64_t)(n - p) * src[p]; }
         ChunkMeta &mc = meta[chunk_of(g, c)];
         mc.adler_a = (uint32_t)(a % 65521u); mc.adler_b = (uint32_t)(b % 65521u); mc.in_bytes = n;
@@ -509,7 +370,8 @@ __global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t
 
     // ---- pass B: exclusive scan of the 32768 counts -> bucket starts (in place) ----
     {
-        constexpr uint32_t per = kHashSize / kS3Threads, nv = per * 2 / 16;
+        constexpr uint32_t per = kHashSize / kS4Threads, nv = per * 2 / 16; // counts and 16-byte vectors per lane
+        static_assert(per % 8 == 0, "a lane scans whole 16-byte vectors");
         uint4 *c4 = reinterpret_cast<uint4 *>(cnt) + tid * nv;
         uint32_t v[nv * 4], sum = 0;
 #pragma unroll
@@ -538,12 +400,12 @@ __global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t
     const uint16_t *start = reinterpret_cast<const uint16_t *>(cnt);
 #pragma unroll
     for (uint32_t j = 0; j < kTurnsPerWave; j++) {
-        const uint32_t T = wave + j * kS3Waves;
+        const uint32_t T = wave + j * kS4Waves;
         __builtin_amdgcn_sched_barrier(0); // one turn's eight at a time: all 64 in flight do not fit the registers
         if (T < nturns) {
 #pragma unroll
-            for (uint32_t u = 0; u < kS3TurnSteps; u++) {
-                const uint32_t p = T * kS3TurnPos + 64 * u + lane;
+            for (uint32_t u = 0; u < kS4TurnSteps; u++) {
+                const uint32_t p = T * kS4TurnPos + 64 * u + lane;
                 if (pk[j][u] != kNone32) {
                     const uint32_t r = pk[j][u] >> 16, id = (uint32_t)start[pk[j][u] & 0x7fffu] + r;
                     pk[j][u] = id | (r << 16);
@@ -554,31 +416,32 @@ __global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t
         }
     }
     __syncthreads();
-    for (uint32_t i = tid; i < kChunkMax / 32; i += kS3Threads) hd[i] = heads[i];
+    for (uint32_t i = tid; i < kChunkMax / 32; i += kS4Threads) hd[i] = heads[i];
     reinterpret_cast<uint16_t *>(hd + kHeadWords)[tid] = (uint16_t)heads_below(reinterpret_cast<const unsigned long long *>(heads)[tid], tid, wave_tot);
 
-    // ---- pass C1: the scatter through LDS, half of S at a time, and the self-check (see sort3_kernel) ----
+    // ---- pass C1: the scatter through LDS, half of S at a time, and pass V, the self-check ----
     uint16_t *stage = reinterpret_cast<uint16_t *>(cnt);
     bool bad = false;
     for (uint32_t half = 0; half < 2 && half * 32768u < nin; half++) {
-        __syncthreads();
+        __syncthreads(); // the table (pass C0), or the previous half's write-out, is done with this memory
 #pragma unroll
         for (uint32_t j = 0; j < kTurnsPerWave; j++) {
-            const uint32_t T = wave + j * kS3Waves;
+            const uint32_t T = wave + j * kS4Waves;
             __builtin_amdgcn_sched_barrier(0);
             if (T < nturns) {
 #pragma unroll
-                for (uint32_t u = 0; u < kS3TurnSteps; u++) {
+                for (uint32_t u = 0; u < kS4TurnSteps; u++) {
                     asm volatile("" : "+v"(pk[j][u])); // (nothing derived from it is kept across the two halves: there are no registers for that)
-                    if (pk[j][u] != kNone32 && ((pk[j][u] >> 15) & 1u) == half) stage[pk[j][u] & 32767u] = (uint16_t)(T * kS3TurnPos + 64 * u + lane);
+                    if (pk[j][u] != kNone32 && ((pk[j][u] >> 15) & 1u) == half) stage[pk[j][u] & 32767u] = (uint16_t)(T * kS4TurnPos + 64 * u + lane);
                 }
             }
         }
         __syncthreads();
-        const uint32_t cntH = nin - half * 32768u < 32768u ? nin - half * 32768u : 32768u;
-        for (uint32_t v = tid; v * 8 < cntH; v += kS3Threads) {
+        const uint32_t cntH = nin - half * 32768u < 32768u ? nin - half * 32768u : 32768u; // entries of this half
+        for (uint32_t v = tid; v * 8 < cntH; v += kS4Threads) { // 8 entries = 16 bytes per lane and step
             const uint4 q = reinterpret_cast<const uint4 *>(stage)[v];
-            *reinterpret_cast<uint4 *>(S + half * 32768u + v * 8) = q;
+            *reinterpret_cast<uint4 *>(S + half * 32768u + v * 8) = q; // S is 16-byte aligned (kSPad); the tail past nin is don't-care
+            // pass V: inside a bucket the positions must ascend (the lane order of the LDS atomic, see above)
             const uint32_t w[4] = {q.x, q.y, q.z, q.w};
             const uint32_t hb = (heads[(half * 32768u + v * 8) >> 5] >> ((v * 8) & 31u)) & 0xffu;
             uint32_t prev = v ? stage[v * 8 - 1] : (half ? last_of_half0 : 0);
@@ -589,7 +452,7 @@ __global__ void __launch_bounds__(kS3Threads) sort4_kernel(ChunkGeom g, uint16_t
                 prev = cur;
             }
         }
-        if (half == 0 && nin > 32768u) { __syncthreads(); last_of_half0 = stage[32767]; }
+        if (half == 0 && nin > 32768u) { __syncthreads(); last_of_half0 = stage[32767]; } // (uniform branch)
     }
     if (bad) atomicOr(fault, 1u);
 }
@@ -885,15 +748,13 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
 //     behind the current one and for the position behind the match in hand.
 //   * Output: for every neutral position r that a game started from, gm[r] = (m - r) << 24 | len << 15 | dist of the match the
 //     game ends with, and bit r of the chunk's bitmap gs: what parse2_kernel's stage A1 derives from match3's records,
-//     restricted to the positions some walker stood on (which include the whole path).  parse2 (lite form) does the rest.
+//     restricted to the positions some walker stood on (which include the whole path).  The lite form of the parse (zgpu_lz_parse_body.inc)
+//     does the rest: behind the walkers in the same workgroup (chunks), or as parse2_kernel<true, true> once the tiles' entries are known.
 #ifndef ZGPU_WTRIG
 #define ZGPU_WTRIG 48 // lanes waiting for a pass that make the wave run one
 #endif
 #ifndef ZGPU_WBLK
 #define ZGPU_WBLK 64 // positions per block
-#endif
-#ifndef ZGPU_WTHREADS
-#define ZGPU_WTHREADS 512
 #endif
 #ifndef ZGPU_WNEU_SHIFT
 #define ZGPU_WNEU_SHIFT 0 // walkers meet at positions that are multiples of 1 << this (fewer bits in LDS, a little more duplicate work)
@@ -902,7 +763,7 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
 #define ZGPU_WFOLD_AT 64 // parked candidates that make a wave compare them (at most 64 more arrive with one step: the stack holds 128)
 #endif
 constexpr uint32_t kWFoldAt = ZGPU_WFOLD_AT;
-constexpr uint32_t kWThreads = ZGPU_WTHREADS, kWWaves = kWThreads / 64, kWBlk = ZGPU_WBLK, kWTrig = ZGPU_WTRIG, kWNeuShift = ZGPU_WNEU_SHIFT;
+constexpr uint32_t kWThreads = 512, kWWaves = kWThreads / 64, kWBlk = ZGPU_WBLK, kWTrig = ZGPU_WTRIG, kWNeuShift = ZGPU_WNEU_SHIFT;
 constexpr uint32_t kWNeuBytes = (kChunkMax >> kWNeuShift) / 8;
 constexpr uint32_t kWLds = kM3DataLds + 16 + kWNeuBytes + kWWaves * kM3WaveLds;
 static_assert(2 * kWLds <= 160 * 1024, "two walker workgroups per CU");
@@ -1044,12 +905,13 @@ __device__ inline void tile_exits(uint8_t *pl, const uint32_t *gm, const uint32_
 // chunk bytes lived in).  That part is all latency -- a window at a time, one wave threading the path -- and leaves the CU's vector
 // units to the other workgroup's walkers, which are bound by exactly those; as a kernel of its own it cost as much as a third of the walk.
 static_assert(kP2LdsBytes <= kM3DataLds, "the parse works in the memory of the chunk bytes");
-// MODE 0: the walkers alone; 1: the rest of the parse behind them (FUSE); 2: a TILE of a continuous stream (zgpu_cont.hip) -- walkers start at every possible
+// MODE 1: a chunk, the rest of the parse behind its walkers (FUSE); 2: a TILE of a continuous stream (zgpu_cont.hip) -- walkers start at every possible
 // entry of the tile and at every 64th position of its range [h0, h1), stop at h1, and the workgroup ends with the tile's exit as a function of its entry.
 template <int MODE>
 __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkGeom g, LevelCfg cfg, const uint16_t *__restrict__ S_all, const uint32_t *__restrict__ ir_all,
                                                             uint32_t *__restrict__ gm_all, uint32_t *__restrict__ gs_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg)
 {
+    static_assert(MODE == 1 || MODE == 2, "a chunk or a tile");
     constexpr bool FUSE = MODE == 1, TILE = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t *d32 = lds;
@@ -1360,7 +1222,6 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         }
         W_T(1);
     }
-#if ZGPU_WTHREADS == 512 // (other workgroup sizes: experiments with the walkers alone, MODE 0)
     if (TILE) {
         __syncthreads(); // every walker of the tile is done: gm / gs are complete
         tile_exits<kWThreads>(reinterpret_cast<uint8_t *>(lds), gm, gs, th0, th1, tnent_all, tg.exits + (size_t)c * kTileExitStride, tid);
@@ -1379,7 +1240,6 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         uint32_t &sh_entry = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry), &sh_exit = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry + 4);
 #include "zgpu_lz_parse_body.inc"
     }
-#endif
 }
 
 // ======================================================================================================================================
@@ -1393,7 +1253,6 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
 // The window slide, NIL, MAX_DIST, nice_match and the chain budget are longest_match's (deflate.c:1027-1168), as in SerialLz::longest.
 // ======================================================================================================================================
 struct __attribute__((packed, aligned(1))) U128b { uint4 v; };
-constexpr uint32_t kGPad = 32, kGStride = kChunkMax + 2 * kGPad; // flag bytes per chunk, room in front for the group reads
 enum : uint32_t { F_IR = 0, F_GROUP, F_CAND, F_EXT, F_DONE };
 
 // index of the first byte in which two 16-byte strings differ (16: none)
@@ -1582,83 +1441,63 @@ __global__ void __launch_bounds__(64) fast_kernel(ChunkGeom g, LevelCfg cfg, con
     if (live) { meta[c].ntok = ntok; meta[c].nostore = nostore; meta[c].in_bytes = n; }
 }
 
-// `exact_sort`: use the ballot-only sort (the engine sets it after sort3's pass V reported a fault, or ZGPU_SORT=1 asks)
-// `walk`: parse-driven search (walk_kernel + the lite parse) instead of the all-position search (match3_kernel + parse2_kernel)
-// `walk` 2: levels 1-3, deflate_fast on the sorted buckets (fast_kernel); `walk` 3: the same by a wave per chunk (zgpu_lz_fastwin.hip)
-// returns true when the sort has left the chunks' Adler-32 in meta[] (sort3_kernel does; the ballot-only sort does not)
-bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, int walk)
+// The sort of a batch of chunks or tiles: sort4_kernel, or -- `exact_sort` (the engine sets it after pass V has reported a fault) or ZGPU_SORT=1 --
+// the ballot-only sort_kernel + heads_below_kernel.  Returns true when the sort has left the chunks' Adler-32 in meta[] (sort4_kernel does; the
+// ballot-only sort does not).
+static bool launch_sort(const ChunkGeom &g, const SortedWs &ws, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort)
 {
-    bool adler_done = false;
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    const size_t nch = g.nchunks;
-    uint32_t *fault = reinterpret_cast<uint32_t *>(w);
-    uint16_t *S = reinterpret_cast<uint16_t *>(w + 256);
-    uint16_t *rk = reinterpret_cast<uint16_t *>(w + 256 + ((nch * kSStride * 2 + 255) & ~(size_t)255));
-    uint32_t *heads = reinterpret_cast<uint32_t *>(rk + nch * kChunkMax);
-    uint2 *recs = reinterpret_cast<uint2 *>(heads + nch * kHeadStride);
-    uint32_t *ir = reinterpret_cast<uint32_t *>(recs + nch * kChunkMax);
+    static int sort_env = -1;
+    if (sort_env < 0) { const char *e = getenv("ZGPU_SORT"); sort_env = e ? atoi(e) : 4; } // 4: sort4_kernel, 1: the ballot-ranked sort
+    const bool exact = exact_sort || sort_env == 1;
     hipEvent_t ev{};
     prof_span_begin(prof, st, &ev);
-    static int sort_env = -1;
-    if (sort_env < 0) { const char *e = getenv("ZGPU_SORT"); sort_env = e ? atoi(e) : 4; } // 4: sort4_kernel, 3: sort3_kernel, 1: the ballot-ranked sort
-    if (exact_sort || sort_env == 1) {
-        hipLaunchKernelGGL(sort_kernel, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, S, rk, heads, ir);
-        hipLaunchKernelGGL(heads_below_kernel, dim3(g.nchunks), dim3(1024), 0, st, heads);
-    }
-    else {
-        if (sort_env == 3) hipLaunchKernelGGL(sort3_kernel, dim3(g.nchunks), dim3(kS3Threads), 0, st, g, S, rk, heads, fault, ir, meta);
-        else hipLaunchKernelGGL(sort4_kernel, dim3(g.nchunks), dim3(kS3Threads), 0, st, g, S, heads, fault, ir, meta);
-        adler_done = true;
-        if (g_inject_sort_fault.exchange(0)) hipMemsetAsync(fault, 1, 4, st); // zgpu_debug_inject_sort_fault(): exercise the engine's fallback without a real fault
+    if (exact) {
+        hipLaunchKernelGGL(sort_kernel, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, ws.S, ws.rk, ws.heads, ws.ir);
+        hipLaunchKernelGGL(heads_below_kernel, dim3(g.nchunks), dim3(1024), 0, st, ws.heads);
+    } else {
+        hipLaunchKernelGGL(sort4_kernel, dim3(g.nchunks), dim3(kS4Threads), 0, st, g, ws.S, ws.heads, ws.fault, ws.ir, meta);
+        if (g_inject_sort_fault.exchange(0)) hipMemsetAsync(ws.fault, 1, 4, st); // zgpu_debug_inject_sort_fault(): exercise the engine's fallback without a real fault
     }
     prof_span_end(prof, st, ZGPU_STAGE_CHAIN, ev);
+    return !exact;
+}
+
+template <int MODE> static void launch_walk(const ChunkGeom &g, LevelCfg cfg, const SortedWs &ws, uint32_t *tokens, ChunkMeta *meta, const TileGeom &tg, hipStream_t st)
+{
+    static bool opt_in = false; // (one per MODE)
+    if (!opt_in) { hipFuncSetAttribute(reinterpret_cast<const void *>(walk_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWLds); opt_in = true; }
+    hipLaunchKernelGGL(walk_kernel<MODE>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, ws.S, ws.ir, ws.gm(), ws.gs(), tokens, meta, tg);
+}
+
+// A batch of chunks: the sort, then the search and parse `impl` names -- ZGPU_LZ_WALK: walk_kernel<1>; ZGPU_LZ_SORTED: the all-position search
+// (match3_kernel + parse2_kernel); levels 1-3: ZGPU_LZ_FAST, fast_kernel, or ZGPU_LZ_FASTWIN, a wave per chunk (zgpu_lz_fastwin.hip).
+// Returns what launch_sort returns.
+bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, int impl)
+{
+    const SortedWs ws(workspace, g.nchunks);
+    const bool adler_done = launch_sort(g, ws, meta, st, prof, exact_sort);
+    hipEvent_t ev{};
     prof_span_begin(prof, st, &ev);
-    if (walk == 3) {
-        launch_lz_fastwin(g, cfg, S, ir, tokens, meta, st);
-        prof_span_end(prof, st, ZGPU_STAGE_MATCH, ev);
-        return adler_done;
-    }
-    if (walk == 2) { // the records' memory holds the flag bytes
-        uint8_t *G = reinterpret_cast<uint8_t *>(recs);
-        hipMemsetAsync(G, 0, nch * kGStride, st);
+    if (impl == ZGPU_LZ_FASTWIN) launch_lz_fastwin(g, cfg, ws.S, ws.ir, tokens, meta, st);
+    else if (impl == ZGPU_LZ_FAST) {
+        hipMemsetAsync(ws.G(), 0, ws.nch * kGStride, st);
         static int forced = -1; // chunks per wave (ZGPU_FAST_LANES): a wave's step takes as long as its slowest lane's memory access
         if (forced < 0) { const char *v = getenv("ZGPU_FAST_LANES"); forced = v ? atoi(v) : 0; if (forced < 0 || forced > 64) forced = 0; }
         uint32_t lanes = (uint32_t)forced;
         if (!lanes) { lanes = 1; while (lanes < 64 && (uint64_t)lanes * 4096 < g.nchunks) lanes <<= 1; } // (measured best at 4 GiB: 16 chunks per wave)
-        hipLaunchKernelGGL(fast_kernel, dim3((g.nchunks + lanes - 1) / lanes), dim3(64), 0, st, g, cfg, S, ir, G, tokens, meta, lanes);
-        prof_span_end(prof, st, ZGPU_STAGE_MATCH, ev);
-        return adler_done;
-    }
-    if (walk) { // the records' memory holds the walkers' output: gm (u32 per position), then the bitmaps gs (2048 words per chunk)
-        uint32_t *gm = reinterpret_cast<uint32_t *>(recs), *gs = gm + nch * kChunkMax;
-        static int fuse = -1; // ZGPU_WALK_FUSE=0: the rest of the parse as a kernel of its own (A/B runs)
-        if (fuse < 0) { const char *v = getenv("ZGPU_WALK_FUSE"); fuse = v ? atoi(v) : 1; }
-        static bool opt_inw = false;
-        if (!opt_inw) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(walk_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWLds);
-            hipFuncSetAttribute(reinterpret_cast<const void *>(walk_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWLds);
-            opt_inw = true;
-        }
-        if (fuse) {
-            hipLaunchKernelGGL(walk_kernel<1>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, S, ir, gm, gs, tokens, meta, TileGeom{});
-            prof_span_end(prof, st, ZGPU_STAGE_MATCH, ev);
-            return adler_done;
-        }
-        hipLaunchKernelGGL(walk_kernel<0>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, S, ir, gm, gs, tokens, meta, TileGeom{});
+        hipLaunchKernelGGL(fast_kernel, dim3((g.nchunks + lanes - 1) / lanes), dim3(64), 0, st, g, cfg, ws.S, ws.ir, ws.G(), tokens, meta, lanes);
+    } else if (impl == ZGPU_LZ_WALK) launch_walk<1>(g, cfg, ws, tokens, meta, TileGeom{}, st);
+    else { // ZGPU_LZ_SORTED
+        static bool opt_in3 = false;
+        if (!opt_in3) { hipFuncSetAttribute(reinterpret_cast<const void *>(match3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kM3Lds); opt_in3 = true; }
+        hipLaunchKernelGGL(match3_kernel, dim3(g.nchunks), dim3(kM2Threads), kM3Lds, st, g, cfg, ws.S, ws.heads, ws.recs);
         prof_span_end(prof, st, ZGPU_STAGE_MATCH, ev);
         prof_span_begin(prof, st, &ev);
-        launch_parse_lite(g, cfg, gm, gs, tokens, meta, st);
+        launch_parse(g, cfg, ws.recs, tokens, meta, st);
         prof_span_end(prof, st, ZGPU_STAGE_PARSE, ev);
         return adler_done;
     }
-    static bool opt_in3 = false;
-    if (!opt_in3) { hipFuncSetAttribute(reinterpret_cast<const void *>(match3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kM3Lds); opt_in3 = true; }
-    hipLaunchKernelGGL(match3_kernel, dim3(g.nchunks), dim3(kM2Threads), kM3Lds, st, g, cfg, S, heads, recs);
     prof_span_end(prof, st, ZGPU_STAGE_MATCH, ev);
-    prof_span_begin(prof, st, &ev);
-    launch_parse(g, cfg, recs, tokens, meta, st);
-
-    prof_span_end(prof, st, ZGPU_STAGE_PARSE, ev);
     return adler_done;
 }
 
@@ -1667,81 +1506,32 @@ bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_
 // the sort alone (levels 1-3 go on with fastwin_tile_kernel's rounds, zgpu_engine.hip): where S and ir of the batch's tiles are
 void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out)
 {
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    const size_t nch = g.nchunks;
-    uint32_t *fault = reinterpret_cast<uint32_t *>(w);
-    uint16_t *S = reinterpret_cast<uint16_t *>(w + 256);
-    uint16_t *rk = reinterpret_cast<uint16_t *>(w + 256 + ((nch * kSStride * 2 + 255) & ~(size_t)255));
-    uint32_t *heads = reinterpret_cast<uint32_t *>(rk + nch * kChunkMax);
-    uint2 *recs = reinterpret_cast<uint2 *>(heads + nch * kHeadStride);
-    uint32_t *ir = reinterpret_cast<uint32_t *>(recs + nch * kChunkMax);
-    hipEvent_t ev{};
-    prof_span_begin(prof, st, &ev);
-    static int sort_env = -1;
-    if (sort_env < 0) { const char *e = getenv("ZGPU_SORT"); sort_env = e ? atoi(e) : 4; } // 4: sort4_kernel, 3: sort3_kernel, 1: the ballot-ranked sort
-    if (exact_sort || sort_env == 1) {
-        hipLaunchKernelGGL(sort_kernel, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, S, rk, heads, ir);
-        hipLaunchKernelGGL(heads_below_kernel, dim3(g.nchunks), dim3(1024), 0, st, heads);
-    } else {
-        if (sort_env == 3) hipLaunchKernelGGL(sort3_kernel, dim3(g.nchunks), dim3(kS3Threads), 0, st, g, S, rk, heads, fault, ir, meta);
-        else hipLaunchKernelGGL(sort4_kernel, dim3(g.nchunks), dim3(kS3Threads), 0, st, g, S, heads, fault, ir, meta);
-        if (g_inject_sort_fault.exchange(0)) hipMemsetAsync(fault, 1, 4, st);
-    }
-    prof_span_end(prof, st, ZGPU_STAGE_CHAIN, ev);
-    *S_out = S; *ir_out = ir;
+    const SortedWs ws(workspace, g.nchunks);
+    launch_sort(g, ws, meta, st, prof, exact_sort);
+    *S_out = ws.S; *ir_out = ws.ir;
 }
-void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st,
-                     zgpu_engine *prof, int exact_sort)
+void launch_lz_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, ChunkMeta *meta, uint16_t *comp, uint16_t *gentry, hipStream_t st, zgpu_engine *prof,
+                     int exact_sort)
 {
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    const size_t nch = g.nchunks;
-    uint32_t *fault = reinterpret_cast<uint32_t *>(w);
-    uint16_t *S = reinterpret_cast<uint16_t *>(w + 256);
-    uint16_t *rk = reinterpret_cast<uint16_t *>(w + 256 + ((nch * kSStride * 2 + 255) & ~(size_t)255));
-    uint32_t *heads = reinterpret_cast<uint32_t *>(rk + nch * kChunkMax);
-    uint2 *recs = reinterpret_cast<uint2 *>(heads + nch * kHeadStride);
-    uint32_t *ir = reinterpret_cast<uint32_t *>(recs + nch * kChunkMax);
-    uint32_t *gm = reinterpret_cast<uint32_t *>(recs), *gs = gm + nch * kChunkMax;
+    const SortedWs ws(workspace, g.nchunks);
+    launch_sort(g, ws, meta, st, prof, exact_sort);
     hipEvent_t ev{};
     prof_span_begin(prof, st, &ev);
-    static int sort_env = -1;
-    if (sort_env < 0) { const char *e = getenv("ZGPU_SORT"); sort_env = e ? atoi(e) : 4; } // 4: sort4_kernel, 3: sort3_kernel, 1: the ballot-ranked sort
-    if (exact_sort || sort_env == 1) {
-        hipLaunchKernelGGL(sort_kernel, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, S, rk, heads, ir);
-        hipLaunchKernelGGL(heads_below_kernel, dim3(g.nchunks), dim3(1024), 0, st, heads);
-    } else {
-        if (sort_env == 3) hipLaunchKernelGGL(sort3_kernel, dim3(g.nchunks), dim3(kS3Threads), 0, st, g, S, rk, heads, fault, ir, meta);
-        else hipLaunchKernelGGL(sort4_kernel, dim3(g.nchunks), dim3(kS3Threads), 0, st, g, S, heads, fault, ir, meta);
-        if (g_inject_sort_fault.exchange(0)) hipMemsetAsync(fault, 1, 4, st);
-    }
-    prof_span_end(prof, st, ZGPU_STAGE_CHAIN, ev);
-    prof_span_begin(prof, st, &ev);
-    static bool opt_in = false;
-    if (!opt_in) { hipFuncSetAttribute(reinterpret_cast<const void *>(walk_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWLds); opt_in = true; }
-    hipLaunchKernelGGL(walk_kernel<2>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, S, ir, gm, gs, tokens, meta, tg);
+    launch_walk<2>(g, cfg, ws, nullptr, meta, tg, st); // (a tile's walkers write games and exits, no tokens)
     prof_span_end(prof, st, ZGPU_STAGE_MATCH, ev);
     prof_span_begin(prof, st, &ev);
     launch_chain(tg.exits, g.nchunks, comp, gentry, tg.entry + g.chunk0, st);
     prof_span_end(prof, st, ZGPU_STAGE_PARSE, ev);
-    (void)tokens;
 }
 // ... and the tiles' tokens from their true entries: a launch of its own, so that it can run on another stream under the next batch's walkers (it is all
 // latency -- a window at a time, one wave threading the path -- and they are bound by the vector units: what the chunk path gets by fusing the two)
 void launch_lz_tiles_parse(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, void *workspace, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof)
 {
-    uint8_t *w = static_cast<uint8_t *>(workspace);
-    const size_t nch = g.nchunks;
-    uint16_t *rk = reinterpret_cast<uint16_t *>(w + 256 + ((nch * kSStride * 2 + 255) & ~(size_t)255));
-    uint32_t *heads = reinterpret_cast<uint32_t *>(rk + nch * kChunkMax);
-    uint2 *recs = reinterpret_cast<uint2 *>(heads + nch * kHeadStride);
-    uint32_t *gm = reinterpret_cast<uint32_t *>(recs), *gs = gm + nch * kChunkMax;
+    const SortedWs ws(workspace, g.nchunks);
     hipEvent_t ev{};
     prof_span_begin(prof, st, &ev);
-    launch_parse_tile(g, cfg, gm, gs, tokens, meta, tg, st);
+    launch_parse_tile(g, cfg, ws.gm(), ws.gs(), tokens, meta, tg, st);
     prof_span_end(prof, st, ZGPU_STAGE_PARSE, ev);
 }
-
-// the word sort3's pass V raises (first word of the workspace)
-uint32_t *lz_sorted_fault_word(void *workspace) { return static_cast<uint32_t *>(workspace); }
 
 } // namespace zgpu
