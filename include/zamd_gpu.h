@@ -52,6 +52,11 @@ extern "C" {
                                 (qcsrc/deflate.c:1266-1358), matches cross every 64 KiB boundary, blocks are cut every 16383 tokens counted from the
                                 stream's start (h/deflate.h:313).  Needs FINAL; chunk_size, POS0*, prime do not apply; no chunk table. */
 
+#define ZGPU_F_BGZF_WRAP 128u /* zgpu_deflate_segments_device / _host only: every segment becomes one BGZF block (SAM specification 4.1) -- the 18-byte gzip header
+                                bgzip writes (FEXTRA with the one subfield 'B' 'C', whose value BSIZE is the block's total length - 1), the raw body, CRC-32 and
+                                ISIZE.  Needs FINAL, no other wrapper flag, segments of at most 65280 bytes (then BSIZE always fits its 16 bits) and the default
+                                geometry (zgpu_deflate_set_geometry 15 / 8); anything else is ZGPU_STREAM_ERROR.  out_offsets marks where each block begins. */
+
 /* LZ77 match-finder implementation selector (debug / A-B measurements) */
 #define ZGPU_LZ_AUTO 0
 #define ZGPU_LZ_SERIAL 1   /* one lane per chunk, tables in HBM: any level 1..9 */
@@ -208,10 +213,25 @@ int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *s
                                const zgpu_deflate_params *p, void *out, uint64_t out_cap, uint64_t *out_offsets,
                                zgpu_deflate_result *res);
 
-/* Output capacity that is enough for zgpu_deflate_segments_* of nseg segments holding in_bytes in all (flags: the wrapper asked for), on an
+/* Output capacity that is enough for zgpu_deflate_segments_* of nseg segments holding in_bytes in all (flags: the wrapper asked for; 26 bytes a segment for ZGPU_F_BGZF_WRAP), on an
  * engine with the default geometry (windowBits 15, memLevel 8; zgpu_deflate_set_geometry); the host entry sizes its own staging in any case. */
 uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t flags);
 
+/* ---- BGZF: blocked gzip, the container of bgzip, BAM, tabix and .vcf.gz (RFC 1952 + SAM specification 4.1) ----
+ * A file is gzip members laid end to end, each at most 64 KiB long and decoding to at most 64 KiB, each carrying its own total length in its header
+ * (BSIZE in the 'B' 'C' extra subfield), closed by a fixed 28-byte empty block.
+ * Encode: the input is cut every block_size bytes (0 selects 65280, which is also the most), every piece becomes one block whose body is what
+ * deflateInit2(level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) + deflate(Z_FINISH) of the piece emits (the segments path with ZGPU_F_BGZF_WRAP), and the
+ * end block is appended; empty input gives the end block alone.  level 1..9 (the segment engine has no level 0: stored blocks are not written here),
+ * strategy as in zgpu_deflate_params.  out_offsets (optional; nblocks + 2 entries, device memory for the device entry): where every block begins, where
+ * the end block begins, the file's length.  res->nchunks = nblocks (the end block not counted), res->crc32 / adler32 cover the whole input.
+ * Out of scope: level 0, general multi-member gzip whose members carry no size, preset dictionaries, htslib's .gzi file I/O (the two arrays of
+ * zgpu_bgzf_index_device hold its content; writing the file of 8-byte pairs is a caller's loop), BAM / VCF record awareness. */
+uint64_t zgpu_bgzf_bound(uint64_t in_bytes, uint32_t block_size); /* output capacity that is enough */
+int zgpu_bgzf_deflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, int level, int strategy, uint32_t block_size, void *d_out, uint64_t out_cap,
+                             uint64_t *d_out_offsets, zgpu_deflate_result *res, void *hip_stream);
+int zgpu_bgzf_deflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, int level, int strategy, uint32_t block_size, void *out, uint64_t out_cap,
+                           uint64_t *out_offsets, zgpu_deflate_result *res);
 /* One chunk with a preset dictionary (deflateSetDictionary, qcsrc/deflate.c:315-354).  `window` holds the dictionary bytes the
  * reference copies into its window -- the last min(length, 32506) bytes of the dictionary, at least 3 -- followed by the data;
  * window_bytes <= 65536.  Output: the raw deflate stream of the data alone, exactly what the reference's fresh stream emits
@@ -317,6 +337,30 @@ int zgpu_inflate_batch_device(zgpu_engine *e, const void *d_in, uint64_t in_byte
 int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,
                             uint32_t checks, void *out, uint64_t out_cap, const uint64_t *out_offsets, zgpu_inflate_item *items,
                             uint64_t *nfailed);
+
+/* ---- BGZF decode (the encode side and the format: zgpu_bgzf_deflate_* above) ---- */
+/* The block index of a BGZF file in device memory, found on the device from the headers alone (zlib_amd/csrc/zgpu_bgzf.hip): d_in_offsets[0..n] =
+ * where every block begins, entry n = in_bytes; d_out_offsets[0..n] = the exclusive sum of the blocks' ISIZE (entry n = *out_bytes).  Both arrays
+ * (device memory, cap_blocks + 1 entries each) are what a .gzi index holds and are the tables zgpu_inflate_batch_device(..., ZGPU_WRAP_GZIP, ...)
+ * takes.  cap_blocks too small: ZGPU_BUF_ERROR with *nblocks = the number of blocks (nothing written).  The file is valid only if its blocks chain
+ * from byte 0 to exactly in_bytes: bad magic at a chain position, no 'B' 'C' subfield there, a block that leaves the buffer or is shorter than its own
+ * frame (header, two bytes of deflate data, trailer), trailing bytes or an ISIZE above 65536 give ZGPU_DATA_ERROR (zgpu_engine_error(): "invalid BGZF block chain", also in zgpu_inflate_message()).
+ * Empty blocks in the middle (concatenated files) are ordinary blocks; a file without the end block is valid, *ends_with_eof_block says which it is.
+ * An empty buffer is a valid file of no blocks.  Blocks until the tables are written. */
+int zgpu_bgzf_index_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint64_t *d_in_offsets, uint64_t *d_out_offsets, uint64_t cap_blocks,
+                           uint64_t *nblocks, uint64_t *out_bytes, uint32_t *ends_with_eof_block, void *hip_stream);
+/* Decode a whole BGZF file: the index above, then every block as one item of the batch decoder (ZGPU_WRAP_GZIP: CRC-32 and ISIZE of every block are
+ * checked on the device).  res->out_bytes = the sum of ISIZE; out_cap too small: ZGPU_BUF_ERROR with res->out_bytes = the size needed, nothing decoded.
+ * items (optional; one record per block, the end block included; device memory for the device entry, room for as many blocks as the file can hold --
+ * in_bytes / 28 records are always enough: a block is 12 bytes of header, an extra field of 6 at least, a deflate body of 2 at least and 8 of trailer,
+ * and what is shorter is no block -- or for the count zgpu_bgzf_index_device gave): each block's own verdict.  A block that decodes to more than its ISIZE
+ * is a ZGPU_DATA_ERROR ("incorrect length check") of that block, as is one whose deflate data ends in front of its trailer.  When a block fails the call
+ * returns ZGPU_DATA_ERROR with res->first_bad_chunk / error_code / error_msg describing the first such block; every other block's bytes are in place.
+ * A file whose blocks do not chain: ZGPU_DATA_ERROR with first_bad_chunk = -1.  res->adler32 / crc32 are not computed (1 / 0).  The host entry uploads
+ * the file once and decodes from there. */
+int zgpu_bgzf_inflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, zgpu_inflate_item *d_items,
+                             zgpu_inflate_result *res, void *hip_stream);
+int zgpu_bgzf_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, void *out, uint64_t out_cap, zgpu_inflate_item *items, zgpu_inflate_result *res);
 
 /* ---- checksums (qcsrc/adler32.c:57-149) ---- */
 int zgpu_adler32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *adler_out, void *hip_stream);

@@ -49,7 +49,7 @@ inline LevelCfg level_cfg(int level)
 enum InfMsg : uint32_t {
     kMsgNone = 0, kMsgBlockType, kMsgStoredLen, kMsgTooMany, kMsgCodeLens, kMsgRepeat, kMsgLitLens, kMsgDists, kMsgLitCode, kMsgDistCode,
     kMsgTooFar, kMsgTruncated, kMsgOutput, kMsgTrailing, kMsgShort, kMsgTable,
-    kMsgHeaderCheck, kMsgMethod, kMsgWindow, kMsgHeaderFlags, kMsgHeaderCrc, kMsgDataCheck, kMsgLengthCheck, kMsgCount
+    kMsgHeaderCheck, kMsgMethod, kMsgWindow, kMsgHeaderFlags, kMsgHeaderCrc, kMsgDataCheck, kMsgLengthCheck, kMsgBgzfChain, kMsgCount
 };
 
 // Batch inflate (zgpu_inflate_batch_*): item k = an independent stream in[in_lo, in_hi) decoded to out[out_lo, out_hi).  The header kernel fills
@@ -64,8 +64,10 @@ struct BatchItemState {
     uint32_t out_bytes, npieces;
 };
 
-// the header every segment of a wrapped segment call starts with (zgpu_stitch.hip, frame_kernel)
-struct FrameHead { uint8_t b[10]; uint8_t n, gzip; };
+// the header every segment of a wrapped segment call starts with (zgpu_stitch.hip, frame_kernel); bgzf: the last two of its bytes are BSIZE,
+// the block's total length - 1, which frame_kernel fills in per segment
+struct FrameHead { uint8_t b[18]; uint8_t n, gzip, bgzf; };
+constexpr uint32_t kBgzfBlockMax = 65280; // 0xff00: what bgzip cuts its input into; a block of that much input always fits BSIZE's 16 bits
 
 struct ChunkMeta {
     uint32_t ntok;        // tokens produced by the LZ77 stage

@@ -90,6 +90,10 @@ struct zgpu_engine {
     DevBuf<uint32_t> cf_dbg, cf_dstat; // (ZGPU_FAST_TRACE only)
     hipStream_t ct_stream = nullptr; hipEvent_t ct_ev_a[2] = {nullptr, nullptr}, ct_ev_b[2] = {nullptr, nullptr}; // levels 4-9: a batch's blocks are made on a second stream under the next batch's walkers
     uint64_t cf_rounds = 0, cf_tile_parses = 0; // (diagnostic: rounds and tile parses since the engine was made)
+    // BGZF block finder (zgpu_bgzf.hip): per 4096 positions (bz_cnt, bz_base), per candidate (the others), one result record
+    DevBuf<uint32_t> bz_cnt, bz_isize, bz_jump_a, bz_jump_b, bz_reach, bz_res;
+    DevBuf<uint64_t> bz_base, bz_pos, bz_next, bz_in_off, bz_out_off;
+    DevBuf<zgpu_inflate_item> bz_items;
     // profiling
     bool prof = false;
     double ms[ZGPU_STAGE_COUNT] = {0};
@@ -132,6 +136,8 @@ void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets
                   uint64_t out_cap, uint32_t slot_stride, void *run, bool with_crc, const FrameHead &h, hipStream_t st);
 void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *offsets, uint64_t chunk0, uint32_t nchunks, uint8_t *out,
                    uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
+void launch_bgzf_cut(uint64_t in_bytes, uint32_t block_size, uint64_t nseg, uint64_t *seg_off, hipStream_t st); // seg_off[k] = min(k * block_size, in_bytes), k = 0..nseg
+void launch_seg_limit(const uint64_t *seg_off, uint64_t nseg, uint64_t in_bytes, uint32_t limit, uint32_t *flag, hipStream_t st); // flag[0] |= 1: a segment over `limit` bytes
 void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st);
 void launch_batch_finish(const BatchItemState *items, uint64_t n, const ChunkMeta *meta, const uint8_t *in, uint32_t do_adler, uint32_t do_crc,
                          zgpu_inflate_item *out_items, unsigned long long *nfailed, hipStream_t st);
@@ -182,5 +188,8 @@ void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const 
 // ---- zgpu_inflate.hip ----
 int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t nchunks, uint32_t chunk_size, uint8_t *d_out, uint64_t out_cap,
                 zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode = 0, const uint64_t *h_offsets = nullptr, bool open_end = false, uint8_t *h_dst = nullptr, uint64_t h_cap = 0);
+
+int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,
+                      const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st);
 
 } // namespace zgpu

@@ -97,9 +97,15 @@ static void zlib_header(int level, int strategy, uint8_t hdr[2]) // qcsrc/deflat
 
 // what a stream that is not part of a wrapped segment call starts with: the zlib header, or the gzip header deflate() writes when no gz_header
 // was set (qcsrc/deflate.c:578-596); OS_CODE 3 as the reference builds here
-static FrameHead frame_head(int level, int strategy, bool wrap, bool gz)
+static FrameHead frame_head(int level, int strategy, bool wrap, bool gz, bool bgzf = false)
 {
     FrameHead fh{};
+    if (bgzf) { // what bgzip writes: FEXTRA, no MTIME, XFL 0, OS 255, the one subfield 'B' 'C' of two bytes -- BSIZE, filled in per block by frame_kernel
+        const uint8_t hdr[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0, 0, 0};
+        for (int i = 0; i < 18; i++) fh.b[i] = hdr[i];
+        fh.n = 18; fh.gzip = 1; fh.bgzf = 1;
+        return fh;
+    }
     if (wrap) { zlib_header(level, strategy, fh.b); fh.n = 2; }
     if (gz) {
         const uint8_t hdr[10] = {31, 139, 8, 0, 0, 0, 0, 0, (uint8_t)(level == 9 ? 2 : (strategy >= 2 || level < 2) ? 4 : 0), 3};
@@ -140,7 +146,7 @@ static LevelCfg level_cfg_for(const zgpu_engine *e, int level, int strategy)
 static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_seg, uint64_t nseg,
                           const zgpu_deflate_params *p, uint8_t *d_out, uint64_t out_cap, uint64_t *d_chunk_offsets,
                           zgpu_deflate_result *res, hipStream_t st, uint32_t skip0 = 0, const uint8_t *h_src = nullptr, uint8_t *h_dst = nullptr,
-                          uint64_t h_cap = 0, uint64_t *h_copied = nullptr)
+                          uint64_t h_cap = 0, uint64_t *h_copied = nullptr, bool seg_checked = false)
 {
     if (!e || !p || !res || (!d_in && in_bytes) || !d_out) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     if (p->level < 1 || p->level > 9) return fail(e, ZGPU_STREAM_ERROR, "level must be 1..9");
@@ -149,7 +155,20 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     if ((p->flags & (ZGPU_F_ZLIB_WRAP | ZGPU_F_GZIP_WRAP)) && !(p->flags & ZGPU_F_FINAL)) return fail(e, ZGPU_STREAM_ERROR, "a wrapper needs FINAL");
     if ((p->flags & ZGPU_F_ZLIB_WRAP) && (p->flags & ZGPU_F_GZIP_WRAP)) return fail(e, ZGPU_STREAM_ERROR, "one wrapper at a time");
     if (p->prime && ((p->prime >> 16) > 16 || (p->flags & (ZGPU_F_ZLIB_WRAP | ZGPU_F_GZIP_WRAP)))) return fail(e, ZGPU_STREAM_ERROR, "prime: at most 16 bits, no wrapper");
+    const bool bgzf = p->flags & ZGPU_F_BGZF_WRAP;
+    if (bgzf && (!d_seg || !(p->flags & ZGPU_F_FINAL) || (p->flags & (ZGPU_F_ZLIB_WRAP | ZGPU_F_GZIP_WRAP | ZGPU_F_CONTINUOUS)) || p->prime || skip0))
+        return fail(e, ZGPU_STREAM_ERROR, "BGZF blocks: segment calls only, with FINAL and no other wrapper");
+    if (bgzf && (e->geo_w != 15 || e->geo_m != 8)) return fail(e, ZGPU_STREAM_ERROR, "BGZF blocks need the default geometry (windowBits 15, memLevel 8)");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    if (bgzf && nseg && !seg_checked) { // BSIZE has 16 bits: no segment may be longer than what always fits (the table is the caller's, in device memory)
+        uint32_t over = 0;
+        uint32_t *flag = &static_cast<RunState *>(e->run)->pad;
+        ZGPU_HIP_CHECK(hipMemsetAsync(flag, 0, 4, st));
+        launch_seg_limit(d_seg, nseg, in_bytes, kBgzfBlockMax, flag, st);
+        ZGPU_HIP_CHECK(hipMemcpyAsync(&over, flag, 4, hipMemcpyDeviceToHost, st));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+        if (over) return fail(e, ZGPU_STREAM_ERROR, "BGZF blocks: a segment is longer than 65280 bytes (or the table leaves the input)");
+    }
     if (p->strategy < 0 || p->strategy > (int)kFixed) return fail(e, ZGPU_STREAM_ERROR, "strategy must be 0..4");
     LevelCfg cfg = level_cfg_for(e, p->level, p->strategy);
     // the chain budget of the all-position search says it all for two strategies (deflate.c:1594-1599): no candidate at all,
@@ -246,11 +265,11 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
         if (e->par_cap > hand_piece) hand_piece = e->par_cap < batch ? e->par_cap : batch; // (an earlier call has left more)
         if ((rc = e->hand_list.reserve(e, (size_t)batch + 1))) return rc;
     }
-    const bool wrap = p->flags & ZGPU_F_ZLIB_WRAP, gz = p->flags & ZGPU_F_GZIP_WRAP;
+    const bool wrap = p->flags & ZGPU_F_ZLIB_WRAP, gz = (p->flags & ZGPU_F_GZIP_WRAP) || bgzf; // (a BGZF block is a gzip member)
     // segments with a wrapper: every segment is a stream of its own, framed by launch_frame; the call itself has no header or trailer
     const bool seg_wrap = d_seg && (wrap || gz);
     const uint32_t head_bytes = seg_wrap ? 0 : wrap ? 2 : gz ? 10 : 0, tail_bytes = seg_wrap ? 0 : wrap ? 4 : gz ? 8 : 0;
-    const FrameHead fh = frame_head(p->level, p->strategy, wrap, gz);
+    const FrameHead fh = frame_head(p->level, p->strategy, wrap, gz, bgzf);
     ChunkGeom g{};
     g.in = d_in; g.in_bytes = in_bytes; g.seg_off = d_seg; g.chunk_size = chunk_size;
     g.final_chunk = (!d_seg && (p->flags & ZGPU_F_FINAL)) ? nchunks - 1 : ~0ull;
@@ -382,7 +401,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     collect_spans(e);
     if (sort_fault) { // the LDS did not serve an atomic's lanes in lane order: redo the call with the sort that does not rely on it
         e->exact_sort = 1;
-        return deflate_device(e, d_in, in_bytes, d_seg, nseg, p, d_out, out_cap, d_chunk_offsets, res, st, skip0, h_src, h_dst, h_cap, h_copied);
+        return deflate_device(e, d_in, in_bytes, d_seg, nseg, p, d_out, out_cap, d_chunk_offsets, res, st, skip0, h_src, h_dst, h_cap, h_copied, seg_checked);
     }
     if (rs.overflow || (tail_bytes && out_cap < rs.out_total + tail_bytes)) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
     const uint32_t adler = rs.adler_a | (rs.adler_b << 16);
@@ -867,6 +886,7 @@ static int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in
     if (!e || !p || !res || (!d_in && in_bytes) || !d_out) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     if (p->level < 1 || p->level > 9 || p->strategy < 0 || p->strategy > (int)kFixed) return fail(e, ZGPU_STREAM_ERROR, "level 1..9, strategy 0..4");
     if (p->prime || (p->flags & (ZGPU_F_POS0 | ZGPU_F_POS0_ALL)) || !(p->flags & ZGPU_F_FINAL) || e->geo_w != 15 || e->geo_m != 8) return fail(e, ZGPU_STREAM_ERROR, "continuous stream: FINAL, no prime, the default geometry");
+    if (p->flags & ZGPU_F_BGZF_WRAP) return fail(e, ZGPU_STREAM_ERROR, "BGZF blocks: segment calls only");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     const LevelCfg cfg = level_cfg_for(e, p->level, p->strategy);
     const bool wrap = p->flags & ZGPU_F_ZLIB_WRAP, gz = p->flags & ZGPU_F_GZIP_WRAP;
@@ -906,6 +926,7 @@ int zgpu_deflate_cont_host(zgpu_engine *e, const void *hist, uint64_t hist_bytes
     const uint64_t buf_bytes = hist_bytes + in_bytes;
     if (p->level < 1 || p->level > 9 || p->strategy < 0 || p->strategy > (int)kFixed || mode < ZGPU_CONT_MORE || mode > ZGPU_CONT_FINISH) return fail(e, ZGPU_STREAM_ERROR, "level 1..9, strategy 0..4, a ZGPU_CONT_* mode");
     if (e->geo_w != 15 || e->geo_m != 8) return fail(e, ZGPU_STREAM_ERROR, "continuous stream: the default geometry");
+    if (p->flags & ZGPU_F_BGZF_WRAP) return fail(e, ZGPU_STREAM_ERROR, "BGZF blocks: segment calls only");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     const LevelCfg cfg = level_cfg_for(e, p->level, p->strategy);
     const uint64_t bound = zgpu_deflate_cont_bound(buf_bytes) + kContCarry * 4;
@@ -999,7 +1020,7 @@ int zgpu_deflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const z
 uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t flags)
 {
     // raw: what zgpu_deflate_segments_host stages for the default geometry; a wrapper adds its header and trailer to every segment
-    return in_bytes + nseg * (40 + (uint64_t)((flags & ZGPU_F_GZIP_WRAP) ? 18 : (flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0)) + 16;
+    return in_bytes + nseg * (40 + (uint64_t)((flags & ZGPU_F_BGZF_WRAP) ? 26 : (flags & ZGPU_F_GZIP_WRAP) ? 18 : (flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0)) + 16;
 }
 
 int zgpu_deflate_segments_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets, uint64_t nseg,
@@ -1023,7 +1044,7 @@ int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *s
     // (every segment may be a chunk of its own: with a non-default geometry each gets the allowance of a full chunk)
     const uint64_t bound = (e->geo_w != 15 || e->geo_m != 8) ? in_bytes + zgpu_deflate_bound_geometry(nseg * (uint64_t)kChunkMax, kChunkMax, e->geo_w, e->geo_m) - nseg * (uint64_t)kChunkMax + ((nseg * (uint64_t)kChunkMax) >> 3)
                                                              : in_bytes + nseg * 40 + 16;
-    const uint64_t framed = bound + nseg * (uint64_t)((p->flags & ZGPU_F_GZIP_WRAP) ? 18 : (p->flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0);
+    const uint64_t framed = bound + nseg * (uint64_t)((p->flags & ZGPU_F_BGZF_WRAP) ? 26 : (p->flags & ZGPU_F_GZIP_WRAP) ? 18 : (p->flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0);
     int rc = ensure_stage(e, in_bytes + (nseg + 1) * sizeof(uint64_t) + 64, framed);
     if (rc) return rc;
     const uint64_t tab_off = (in_bytes + 63) & ~63ull; // segment table staged behind the data
@@ -1036,6 +1057,86 @@ int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *s
     ZGPU_HIP_CHECK(hipMemcpyAsync(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost, e->stream));
     if (out_offsets) ZGPU_HIP_CHECK(hipMemcpyAsync(out_offsets, e->offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
+    return ZGPU_OK;
+}
+
+// ---- BGZF encode: the segments path over a table cut on the device, and the end block behind it ----
+static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+uint64_t zgpu_bgzf_bound(uint64_t in_bytes, uint32_t block_size)
+{
+    if (block_size == 0 || block_size > kBgzfBlockMax) block_size = kBgzfBlockMax;
+    const uint64_t nblocks = (in_bytes + block_size - 1) / block_size;
+    return zgpu_deflate_segments_bound(nblocks, in_bytes, ZGPU_F_FINAL | ZGPU_F_BGZF_WRAP) + sizeof kBgzfEof;
+}
+
+// d_seg: room for nblocks + 1 offsets (device); d_out_offsets: optional, nblocks + 2
+static int bgzf_deflate(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, int level, int strategy, uint32_t block_size, uint64_t *d_seg, uint8_t *d_out,
+                        uint64_t out_cap, uint64_t *d_out_offsets, zgpu_deflate_result *res, hipStream_t st)
+{
+    const uint64_t nblocks = (in_bytes + block_size - 1) / block_size;
+    zgpu_deflate_result r{};
+    r.adler32 = 1; r.data_type = 2;
+    if (nblocks) {
+        zgpu_deflate_params p{};
+        p.level = level; p.strategy = strategy; p.flags = ZGPU_F_FINAL | ZGPU_F_BGZF_WRAP; p.lz_impl = ZGPU_LZ_AUTO;
+        launch_bgzf_cut(in_bytes, block_size, nblocks, d_seg, st);
+        const int rc = deflate_device(e, d_in, in_bytes, d_seg, nblocks, &p, d_out, out_cap, d_out_offsets, &r, st, 0, nullptr, nullptr, 0, nullptr, true); // (a table cut here needs no length check)
+        if (rc) return rc;
+    }
+    if (out_cap < r.out_bytes + sizeof kBgzfEof) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    const uint64_t marks[2] = {r.out_bytes, r.out_bytes + sizeof kBgzfEof};
+    ZGPU_HIP_CHECK(hipMemcpyAsync(d_out + r.out_bytes, kBgzfEof, sizeof kBgzfEof, hipMemcpyHostToDevice, st));
+    if (d_out_offsets) ZGPU_HIP_CHECK(hipMemcpyAsync(d_out_offsets + nblocks, marks, sizeof marks, hipMemcpyHostToDevice, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    r.out_bytes += sizeof kBgzfEof; r.nchunks = nblocks;
+    *res = r;
+    return ZGPU_OK;
+}
+
+static int bgzf_deflate_args(zgpu_engine *e, const void *in, uint64_t in_bytes, int *level, int strategy, uint32_t *block_size, const void *out, const zgpu_deflate_result *res)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (!res || !out || (!in && in_bytes)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
+    if (*level == -1) *level = 6;
+    if (*level < 1 || *level > 9) return fail(e, ZGPU_STREAM_ERROR, "BGZF encode: level must be 1..9 (or -1 for 6)");
+    if (strategy < 0 || strategy > (int)kFixed) return fail(e, ZGPU_STREAM_ERROR, "strategy must be 0..4");
+    if (*block_size == 0) *block_size = kBgzfBlockMax;
+    if (*block_size > kBgzfBlockMax) return fail(e, ZGPU_STREAM_ERROR, "BGZF encode: block_size is at most 65280");
+    return ZGPU_OK;
+}
+
+int zgpu_bgzf_deflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, int level, int strategy, uint32_t block_size, void *d_out, uint64_t out_cap,
+                             uint64_t *d_out_offsets, zgpu_deflate_result *res, void *hip_stream)
+{
+    int rc = bgzf_deflate_args(e, d_in, in_bytes, &level, strategy, &block_size, d_out, res);
+    if (rc) return rc;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    const uint64_t nblocks = (in_bytes + block_size - 1) / block_size;
+    if ((rc = e->inf_offs.reserve(e, nblocks + 1))) return rc; // (the segment table: scratch no deflate call uses)
+    return bgzf_deflate(e, static_cast<const uint8_t *>(d_in), in_bytes, level, strategy, block_size, e->inf_offs, static_cast<uint8_t *>(d_out), out_cap, d_out_offsets, res, st);
+}
+
+int zgpu_bgzf_deflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, int level, int strategy, uint32_t block_size, void *out, uint64_t out_cap,
+                           uint64_t *out_offsets, zgpu_deflate_result *res)
+{
+    int rc = bgzf_deflate_args(e, in, in_bytes, &level, strategy, &block_size, out, res);
+    if (rc) return rc;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    const uint64_t nblocks = (in_bytes + block_size - 1) / block_size, bound = zgpu_bgzf_bound(in_bytes, block_size);
+    // staged behind the data: the segment table (nblocks + 1) and the blocks' offsets (nblocks + 2)
+    const uint64_t tab_off = (in_bytes + 63) & ~63ull, ooff_off = tab_off + (((nblocks + 1) * sizeof(uint64_t) + 63) & ~63ull);
+    if ((rc = ensure_stage(e, ooff_off + (nblocks + 2) * sizeof(uint64_t), bound))) return rc;
+    hipStream_t st = e->stream;
+    if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in, in, in_bytes, hipMemcpyHostToDevice, st));
+    uint64_t *d_ooff = reinterpret_cast<uint64_t *>(e->stage_in + ooff_off);
+    rc = bgzf_deflate(e, e->stage_in, in_bytes, level, strategy, block_size, reinterpret_cast<uint64_t *>(e->stage_in + tab_off), e->stage_out, bound, d_ooff, res, st);
+    if (rc) return rc;
+    if (res->out_bytes > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    ZGPU_HIP_CHECK(hipMemcpyAsync(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost, st));
+    if (out_offsets) ZGPU_HIP_CHECK(hipMemcpyAsync(out_offsets, d_ooff, (nblocks + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     return ZGPU_OK;
 }
 

@@ -29,7 +29,7 @@ static const char *const kInfMessages[kMsgCount] = {
     "invalid distance too far back", "segment ends inside a block", "segment decodes to more than chunk_size bytes",
     "segment holds data after its last block", "segment decodes to fewer than chunk_size bytes", "segment table out of range",
     "incorrect header check", "unknown compression method", "invalid window size", "unknown header flags set", "header crc mismatch",
-    "incorrect data check", "incorrect length check"};
+    "incorrect data check", "incorrect length check", "invalid BGZF block chain"};
 
 // bits of the last byte that belong to a stream whose final block the last decode reached (0: all eight): inflate_stream_host's fallback for a stream taken up at a bit offset maps the end back with it
 static thread_local uint32_t t_end_bits = 0;

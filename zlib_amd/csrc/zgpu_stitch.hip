@@ -331,7 +331,8 @@ void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *
 
 // ---- segments that are streams of their own (zgpu_deflate_segments_* with a wrapper): the scan leaves room for a header and a trailer around
 // every body, the stitch places the body behind its header, and one lane per segment writes both: the zlib header and the big-endian Adler-32, or
-// the gzip header and CRC-32 / ISIZE little-endian (qcsrc/deflate.c:578-596, 625-641, 833-843) ----
+// the gzip header and CRC-32 / ISIZE little-endian (qcsrc/deflate.c:578-596, 625-641, 833-843); a BGZF block is a gzip member whose 18-byte header
+// ends with BSIZE, its own total length - 1 ----
 __global__ void __launch_bounds__(256) frame_kernel(const ChunkMeta *__restrict__ meta, const uint64_t *__restrict__ offsets, const uint64_t *__restrict__ seg_off,
                                                     uint64_t chunk0, uint32_t nchunks, uint8_t *out, uint64_t out_cap, FrameHead h)
 {
@@ -342,6 +343,7 @@ __global__ void __launch_bounds__(256) frame_kernel(const ChunkMeta *__restrict_
     if (off + h.n + n + tail > out_cap) return; // reported through RunState.overflow
     uint8_t *d = out + off;
     for (uint32_t i = 0; i < h.n; i++) d[i] = h.b[i];
+    if (h.bgzf) { const uint32_t bsize = h.n + n + tail - 1; d[h.n - 2] = (uint8_t)bsize; d[h.n - 1] = (uint8_t)(bsize >> 8); } // (at most 65328: the segment is at most 65280 bytes)
     uint8_t *t = d + h.n + n;
     if (h.gzip) {
         const uint32_t crc = meta[c].crc, isz = (uint32_t)(seg_off[gc + 1] - seg_off[gc]);
@@ -358,6 +360,30 @@ void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, meta, nchunks, chunk0, offsets, static_cast<RunState *>(run), out_cap, with_crc ? 1u : 0u, frame);
     hipLaunchKernelGGL(stitch_kernel, dim3(nchunks), dim3(256), 0, st, slots, meta, offsets, chunk0, nchunks, out, out_cap, slot_stride, (uint32_t)h.n, frame);
     hipLaunchKernelGGL(frame_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, st, meta, offsets, seg_off, chunk0, nchunks, out, out_cap, h);
+}
+// ---- BGZF (ZGPU_F_BGZF_WRAP, zgpu_bgzf_deflate_*): the segment table of an input cut every block_size bytes, and the check that no segment of a
+// caller's table is longer than a block may be (flag[0] |= 1: too long or running backwards or leaving the buffer) ----
+__global__ void __launch_bounds__(256) bgzf_cut_kernel(uint64_t in_bytes, uint32_t block_size, uint64_t nseg, uint64_t *seg_off)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k > nseg) return;
+    const uint64_t at = k * block_size;
+    seg_off[k] = at < in_bytes ? at : in_bytes;
+}
+__global__ void __launch_bounds__(256) seg_limit_kernel(const uint64_t *__restrict__ seg_off, uint64_t nseg, uint64_t in_bytes, uint32_t limit, uint32_t *flag)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nseg) return;
+    const uint64_t lo = seg_off[k], hi = seg_off[k + 1];
+    if (hi < lo || hi > in_bytes || hi - lo > limit) atomicOr(flag, 1u);
+}
+void launch_bgzf_cut(uint64_t in_bytes, uint32_t block_size, uint64_t nseg, uint64_t *seg_off, hipStream_t st)
+{
+    hipLaunchKernelGGL(bgzf_cut_kernel, dim3((uint32_t)((nseg + 256) / 256)), dim3(256), 0, st, in_bytes, block_size, nseg, seg_off);
+}
+void launch_seg_limit(const uint64_t *seg_off, uint64_t nseg, uint64_t in_bytes, uint32_t limit, uint32_t *flag, hipStream_t st)
+{
+    hipLaunchKernelGGL(seg_limit_kernel, dim3((uint32_t)((nseg + 255) / 256)), dim3(256), 0, st, seg_off, nseg, in_bytes, limit, flag);
 }
 void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st)
 {

@@ -5,7 +5,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
 
-F_FINAL, F_ZLIB_WRAP, F_POS0, F_POS0_ALL, F_GZIP_WRAP, F_CRC32, F_CONTINUOUS = 1, 2, 4, 8, 16, 32, 64
+F_FINAL, F_ZLIB_WRAP, F_POS0, F_POS0_ALL, F_GZIP_WRAP, F_CRC32, F_CONTINUOUS, F_BGZF_WRAP = 1, 2, 4, 8, 16, 32, 64, 128
+BGZF_BLOCK = 65280  # what zgpu_bgzf_deflate_* cuts its input into by default (and at most)
 CONT_MORE, CONT_FLUSH, CONT_FINISH = 0, 1, 2  # zgpu_deflate_cont_host modes
 WHOLE_STREAM = 0xFFFFFFFF  # inflate chunk_size: the one segment is a complete stream of any size
 LZ_AUTO, LZ_SERIAL, LZ_PARALLEL, LZ_SORTED, LZ_WALK, LZ_FAST, LZ_FASTWIN = 0, 1, 2, 3, 4, 5, 6
@@ -96,6 +97,13 @@ def load_library():
     L.zgpu_deflate_segments_bound.restype = u64
     L.zgpu_inflate_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.zgpu_inflate_batch_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, C.POINTER(u64)]
+    L.zgpu_bgzf_bound.argtypes = [u64, u32]
+    L.zgpu_bgzf_bound.restype = u64
+    L.zgpu_bgzf_deflate_device.argtypes = [vp, vp, u64, C.c_int, C.c_int, u32, vp, u64, vp, C.POINTER(DeflateResult), vp]
+    L.zgpu_bgzf_deflate_host.argtypes = [vp, vp, u64, C.c_int, C.c_int, u32, vp, u64, vp, C.POINTER(DeflateResult)]
+    L.zgpu_bgzf_index_device.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), vp]
+    L.zgpu_bgzf_inflate_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(InflateResult), vp]
+    L.zgpu_bgzf_inflate_host.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(InflateResult)]
     L.zgpu_inflate_find_chunks_host.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64)]
     L.zgpu_inflate_stream_host2.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(InflateResult)]
     L.zgpu_inflate_stream_host3.argtypes = [vp, vp, u64, u32, u32, vp, u64, C.POINTER(InflateResult)]
@@ -298,6 +306,63 @@ class Engine:
         self._check(self.L.zgpu_inflate_batch_device(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks,
                                                      d_out, out_cap, d_out_offsets, d_items, C.byref(failed), stream))
         return failed.value
+
+    # ---- BGZF (blocked gzip) ----
+    def bgzf_deflate_host(self, data, level=6, block_size=0, strategy=0, want_offsets=False):
+        """data -> a BGZF file (zgpu_bgzf_deflate_host); with want_offsets also where every block begins, where the end block begins, the length."""
+        import numpy as np
+        arr = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+        n = int(arr.size) - 1
+        cap = int(self.L.zgpu_bgzf_bound(n, block_size))
+        out = np.empty(cap, dtype=np.uint8)
+        bs = block_size or BGZF_BLOCK
+        offs = np.zeros((n + bs - 1) // bs + 2, dtype=np.uint64)
+        res = DeflateResult()
+        self._check(self.L.zgpu_bgzf_deflate_host(self.h, arr.ctypes.data, n, level, strategy, block_size, out.ctypes.data, cap, offs.ctypes.data, C.byref(res)))
+        self.last = res
+        z = out[: res.out_bytes].tobytes()
+        return (z, offs) if want_offsets else z
+
+    def bgzf_inflate_host(self, data, out_cap=None):
+        """A BGZF file -> (rc, bytes, items): rc the call's code (0, -3 when the chain or a block is bad, -5 when out_cap is too small), items one
+        (code, msg, out_bytes, in_used) per block; self.last_inflate has out_bytes (the size needed) and the first failing block."""
+        import numpy as np
+        arr = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+        n = int(arr.size) - 1
+        items = (InflateItem * max(n // 28, 1))()  # (no block is shorter than 28 bytes)
+        res = InflateResult()
+        cap = out_cap
+        if cap is None:  # ask for the size first: a call with no room says what is needed
+            cap = 0
+            if self.L.zgpu_bgzf_inflate_host(self.h, arr.ctypes.data, n, None, 0, items, C.byref(res)) == -5:
+                cap = res.out_bytes
+        out = np.zeros(cap + 1, dtype=np.uint8)
+        rc = self.L.zgpu_bgzf_inflate_host(self.h, arr.ctypes.data, n, out.ctypes.data, cap, items, C.byref(res))
+        self.last_inflate = res
+        if rc not in (0, -3, -5):
+            self._check(rc)
+        return rc, out[: res.out_bytes].tobytes() if rc in (0, -3) else b"", items
+
+    def bgzf_index_device(self, d_in, in_bytes, d_in_offsets, d_out_offsets, cap_blocks, stream=None):
+        """Device pointers as ints; the tables hold cap_blocks + 1 uint64 each.  Returns (rc, nblocks, out_bytes, ends_with_eof_block)."""
+        n, total, eof = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = self.L.zgpu_bgzf_index_device(self.h, d_in, in_bytes, d_in_offsets, d_out_offsets, cap_blocks, C.byref(n), C.byref(total), C.byref(eof), stream)
+        if rc not in (0, -3, -5):
+            self._check(rc)
+        return rc, n.value, total.value, eof.value
+
+    def bgzf_inflate_device(self, d_in, in_bytes, d_out, out_cap, d_items=None, stream=None):
+        """Returns (rc, InflateResult)."""
+        res = InflateResult()
+        rc = self.L.zgpu_bgzf_inflate_device(self.h, d_in, in_bytes, d_out, out_cap, d_items, C.byref(res), stream)
+        if rc not in (0, -3, -5):
+            self._check(rc)
+        return rc, res
+
+    def bgzf_deflate_device(self, d_in, n, level, d_out, out_cap, block_size=0, strategy=0, d_offsets=None, stream=None):
+        res = DeflateResult()
+        self._check(self.L.zgpu_bgzf_deflate_device(self.h, d_in, n, level, strategy, block_size, d_out, out_cap, d_offsets, C.byref(res), stream))
+        return res
 
     def deflate_device(self, d_in, n, level, d_out, out_cap, flags=F_FINAL | F_ZLIB_WRAP, chunk_size=CHUNK, lz_impl=LZ_AUTO,
                        d_offsets=None, stream=None):

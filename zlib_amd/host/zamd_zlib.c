@@ -86,6 +86,10 @@ static void engine_checkin(zgpu_engine *e)
     pthread_mutex_unlock(&g_lock);
 }
 
+/* the pool for the library's other files (zamd_bgzf.c); not exported */
+zgpu_engine *zamd_engine_checkout(void) { return engine_checkout(); }
+void zamd_engine_checkin(zgpu_engine *e) { engine_checkin(e); }
+
 /* ---- more than one GPU: ZAMD_DEVICES="0,1,2,3" names the devices one deflate() / compress2() call may use.  Chunks are
  * independent, so a large input is cut into contiguous chunk ranges, one per device, each compressed by that device's engine from a thread
  * of its own (no exchange between the devices: the ranges' streams are laid end to end on the host, only the last one carries the final
