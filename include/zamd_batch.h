@@ -27,6 +27,14 @@ int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const
 int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits,
                           int *status);
 
+/* crc32() / adler32() of many buffers, all items in one engine call (zgpu_checksum_batch_host).  crc[k] / adler[k] hold the running value on
+ * entry, as the first argument of crc32() / adler32() (0 / 1 for a fresh one), and crc32(crc[k], buf[k], len[k]) / adler32(...) on return: the
+ * items' own checksums come from the device, the running values are folded in on the host with crc32_combine / adler32_combine.  Items of any
+ * size below 4 GiB.  Z_OK; Z_STREAM_ERROR for bad arguments (a null array with n > 0, a null buffer with a length, an item of 4 GiB or more: nothing
+ * is touched); Z_MEM_ERROR when memory or the engine is not to be had.  n == 0 is Z_OK and creates no engine. */
+int zamd_crc32_batch(uLong *crc, const Bytef *const *buf, const uLong *len, size_t n);
+int zamd_adler32_batch(uLong *adler, const Bytef *const *buf, const uLong *len, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

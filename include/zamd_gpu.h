@@ -213,6 +213,25 @@ int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *s
                                const zgpu_deflate_params *p, void *out, uint64_t out_cap, uint64_t *out_offsets,
                                zgpu_deflate_result *res);
 
+/* The same calls with one record per segment (d_items / items: nseg records, device memory for the device entry; NULL: none, which is what the
+ * two entries above are).  The output bytes do not change.  Record k:
+ *   out_lo, out_bytes  where segment k's stream lies in the output, its wrapper included (out_offsets[k] and the distance to the next)
+ *   in_bytes           the segment's length
+ *   data_type          Z_BINARY 0 / Z_TEXT 1 as strm->data_type after the segment's first block; an empty segment: Z_UNKNOWN 2
+ *   adler32            of the segment's input (1 for an empty one)
+ *   crc32              of the segment's input when ZGPU_F_GZIP_WRAP, ZGPU_F_BGZF_WRAP or ZGPU_F_CRC32 was given, else 0
+ * A call that runs in several batches writes the records batch by batch; they are complete when the call returns ZGPU_OK. */
+typedef struct {
+    uint64_t out_lo, out_bytes;
+    uint32_t in_bytes, data_type, adler32, crc32;
+} zgpu_deflate_item;
+int zgpu_deflate_segments_items_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets,
+                                       uint64_t nseg, const zgpu_deflate_params *p, void *d_out, uint64_t out_cap,
+                                       uint64_t *d_out_offsets, zgpu_deflate_result *res, zgpu_deflate_item *d_items, void *hip_stream);
+int zgpu_deflate_segments_items_host(zgpu_engine *e, const void *in, const uint64_t *seg_offsets, uint64_t nseg,
+                                     const zgpu_deflate_params *p, void *out, uint64_t out_cap, uint64_t *out_offsets,
+                                     zgpu_deflate_result *res, zgpu_deflate_item *items);
+
 /* Output capacity that is enough for zgpu_deflate_segments_* of nseg segments holding in_bytes in all (flags: the wrapper asked for; 26 bytes a segment for ZGPU_F_BGZF_WRAP), on an
  * engine with the default geometry (windowBits 15, memLevel 8; zgpu_deflate_set_geometry); the host entry sizes its own staging in any case. */
 uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t flags);
@@ -366,6 +385,21 @@ int zgpu_bgzf_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, vo
 int zgpu_adler32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *adler_out, void *hip_stream);
 /* CRC-32 as crc32() computes it (qcsrc/crc32.c:219-266), chunk CRCs joined like crc32_combine (crc32.c:370-423) */
 int zgpu_crc32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *crc_out, void *hip_stream);
+
+/* ---- batch checksums: many independent items of one buffer in one call (zlib_amd/csrc/zgpu_checksum.hip) ----
+ * Item k = in[offsets[k] .. offsets[k+1]): n + 1 nondecreasing offsets, the last at most in_bytes; any size below 4 GiB, any alignment.  checks takes
+ * ZGPU_CHECK_* bits; record k holds adler32(1, item) and crc32(0, item) as the reference computes them.  A check that is not asked for reads
+ * adler32 = 1 / crc32 = 0, and so does an empty item.  Offsets that run backwards or leave the buffer (or an item of 4 GiB or more) are found on the
+ * device before anything is written: ZGPU_STREAM_ERROR, the records untouched.  Items of at most 4096 bytes are served one per wave, sixteen to a
+ * workgroup and its CRC table; longer ones in pieces of 64 KiB whose partial results a second launch joins in order.  Blocks until the records are
+ * written. */
+typedef struct {
+    uint32_t adler32, crc32;
+} zgpu_check_item;
+int zgpu_checksum_batch_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t n, uint32_t checks,
+                               zgpu_check_item *d_items, void *hip_stream);
+int zgpu_checksum_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *offsets, uint64_t n, uint32_t checks,
+                             zgpu_check_item *items);
 
 /* ---- measurement support ---- */
 /* Per-stage device time (HIP events on the launch stream), accumulated while profiling is on. */

@@ -289,6 +289,41 @@ __device__ inline uint32_t dist_code_of(uint32_t dist_minus1)
 // 3-byte hash the reference's rolling UPDATE_HASH converges to (deflate.c:170,189-192)
 __host__ __device__ inline uint32_t hash3(uint32_t b0, uint32_t b1, uint32_t b2) { return ((b0 << 10) ^ (b1 << 5) ^ b2) & kHashMask; }
 
+// ---- checksum arithmetic shared by the stitcher (zgpu_stitch.hip) and the batch checksums (zgpu_checksum.hip) ----
+constexpr uint32_t kAdlerBase = 65521;
+// CRC-32 (the reference's crc32.c:219-335 and crc32_combine :370-423, as polynomial arithmetic)
+// Reflected CRC-32 polynomial; a 32-bit word holds a polynomial over GF(2) with x^0 in bit 31.
+constexpr uint32_t kCrcPoly = 0xedb88320u;
+__host__ __device__ inline uint32_t crc_mulmod(uint32_t a, uint32_t b) // a(x) * b(x) mod P(x)
+{
+    uint32_t p = 0;
+    for (uint32_t m = 0x80000000u; m; m >>= 1) {
+        if (a & m) p ^= b;
+        b = (b & 1u) ? (b >> 1) ^ kCrcPoly : b >> 1;
+    }
+    return p;
+}
+__host__ __device__ inline uint32_t crc_xpow8n(uint64_t n) // x^(8n) mod P: the operator "append n zero bytes"
+{
+    uint32_t r = 0x80000000u, sq = 0x00800000u; // x^0, x^8
+    while (n) {
+        if (n & 1) r = crc_mulmod(sq, r);
+        sq = crc_mulmod(sq, sq);
+        n >>= 1;
+    }
+    return r;
+}
+// CRC of X||Y from the finished CRCs of X and Y and |Y| (what crc32_combine computes with its 32x32 bit matrices)
+__host__ __device__ inline uint32_t crc_join(uint32_t cx, uint32_t cy, uint32_t op_leny) { return crc_mulmod(op_leny, cx) ^ cy; }
+// Adler of X||Y from Adler(X) = (ax, bx), Adler(Y) = (ay, by), |Y| = ny:  a = ax + ay - 1,  b = bx + by + ny (ax - 1)
+__device__ inline void adler_join(uint32_t &ax, uint32_t &bx, uint32_t ay, uint32_t by, uint64_t ny)
+{
+    uint64_t rem = ny % kAdlerBase;
+    uint64_t a = ((uint64_t)ax + ay + kAdlerBase - 1) % kAdlerBase;
+    uint64_t b = ((uint64_t)bx + by + rem * ((ax + kAdlerBase - 1) % kAdlerBase)) % kAdlerBase;
+    ax = (uint32_t)a; bx = (uint32_t)b;
+}
+
 #define ZGPU_HIP_CHECK(expr)                                                                     \
     do {                                                                                         \
         hipError_t err__ = (expr);                                                               \

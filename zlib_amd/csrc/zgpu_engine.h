@@ -94,6 +94,8 @@ struct zgpu_engine {
     DevBuf<uint32_t> bz_cnt, bz_isize, bz_jump_a, bz_jump_b, bz_reach, bz_res;
     DevBuf<uint64_t> bz_base, bz_pos, bz_next, bz_in_off, bz_out_off;
     DevBuf<zgpu_inflate_item> bz_items;
+    // batch checksums (zgpu_checksum.hip): pieces in front of every item (n + 1), the bad-table flag, three words per piece (a, b, crc)
+    DevBuf<uint64_t> ck_piece0; DevBuf<uint32_t> ck_flag, ck_part;
     // profiling
     bool prof = false;
     double ms[ZGPU_STAGE_COUNT] = {0};
@@ -138,6 +140,8 @@ void launch_stitch(const uint8_t *slots, const ChunkMeta *meta, const uint64_t *
                    uint64_t out_cap, uint32_t slot_stride, hipStream_t st);
 void launch_bgzf_cut(uint64_t in_bytes, uint32_t block_size, uint64_t nseg, uint64_t *seg_off, hipStream_t st); // seg_off[k] = min(k * block_size, in_bytes), k = 0..nseg
 void launch_seg_limit(const uint64_t *seg_off, uint64_t nseg, uint64_t in_bytes, uint32_t limit, uint32_t *flag, hipStream_t st); // flag[0] |= 1: a segment over `limit` bytes
+// records of the batch's segments behind its scan: where each stream lies in the output (offsets) and what ChunkMeta knows of its input
+void launch_seg_items(const ChunkMeta *meta, const uint64_t *offsets, const uint64_t *seg_off, uint64_t chunk0, uint32_t nchunks, bool with_crc, zgpu_deflate_item *items, hipStream_t st);
 void launch_corpus(uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, uint8_t *out, hipStream_t st);
 void launch_batch_finish(const BatchItemState *items, uint64_t n, const ChunkMeta *meta, const uint8_t *in, uint32_t do_adler, uint32_t do_crc,
                          zgpu_inflate_item *out_items, unsigned long long *nfailed, hipStream_t st);
@@ -191,5 +195,8 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
 
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,
                       const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st);
+
+// ---- zgpu_checksum.hip ----
+int checksum_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t n, uint32_t checks, zgpu_check_item *d_items, hipStream_t st);
 
 } // namespace zgpu

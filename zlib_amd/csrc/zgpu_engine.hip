@@ -146,7 +146,7 @@ static LevelCfg level_cfg_for(const zgpu_engine *e, int level, int strategy)
 static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_seg, uint64_t nseg,
                           const zgpu_deflate_params *p, uint8_t *d_out, uint64_t out_cap, uint64_t *d_chunk_offsets,
                           zgpu_deflate_result *res, hipStream_t st, uint32_t skip0 = 0, const uint8_t *h_src = nullptr, uint8_t *h_dst = nullptr,
-                          uint64_t h_cap = 0, uint64_t *h_copied = nullptr, bool seg_checked = false)
+                          uint64_t h_cap = 0, uint64_t *h_copied = nullptr, bool seg_checked = false, zgpu_deflate_item *d_items = nullptr)
 {
     if (!e || !p || !res || (!d_in && in_bytes) || !d_out) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     if (p->level < 1 || p->level > 9) return fail(e, ZGPU_STREAM_ERROR, "level must be 1..9");
@@ -382,6 +382,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
                 launch_scan(e->meta, nb, c0, e->offsets, e->run, body_cap, st, gz || (p->flags & ZGPU_F_CRC32));
                 launch_stitch(slots, e->meta, e->offsets, c0, nb, d_out, body_cap, g.slot_stride, st);
             }
+            if (d_items) launch_seg_items(e->meta, e->offsets, d_seg, c0, nb, gz || (p->flags & ZGPU_F_CRC32), d_items, st); // (segment calls only: d_seg is there)
         }
         if (home) {
             hipError_t he = hipMemcpyAsync(&e->pin_tot[nbatch], e->run, sizeof(uint64_t), hipMemcpyDeviceToHost, st); // RunState::out_total
@@ -401,7 +402,7 @@ static int deflate_device(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes
     collect_spans(e);
     if (sort_fault) { // the LDS did not serve an atomic's lanes in lane order: redo the call with the sort that does not rely on it
         e->exact_sort = 1;
-        return deflate_device(e, d_in, in_bytes, d_seg, nseg, p, d_out, out_cap, d_chunk_offsets, res, st, skip0, h_src, h_dst, h_cap, h_copied, seg_checked);
+        return deflate_device(e, d_in, in_bytes, d_seg, nseg, p, d_out, out_cap, d_chunk_offsets, res, st, skip0, h_src, h_dst, h_cap, h_copied, seg_checked, d_items);
     }
     if (rs.overflow || (tail_bytes && out_cap < rs.out_total + tail_bytes)) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
     const uint32_t adler = rs.adler_a | (rs.adler_b << 16);
@@ -1023,18 +1024,25 @@ uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t 
     return in_bytes + nseg * (40 + (uint64_t)((flags & ZGPU_F_BGZF_WRAP) ? 26 : (flags & ZGPU_F_GZIP_WRAP) ? 18 : (flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0)) + 16;
 }
 
-int zgpu_deflate_segments_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets, uint64_t nseg,
-                                 const zgpu_deflate_params *p, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
-                                 zgpu_deflate_result *res, void *hip_stream)
+int zgpu_deflate_segments_items_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets, uint64_t nseg,
+                                       const zgpu_deflate_params *p, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                       zgpu_deflate_result *res, zgpu_deflate_item *d_items, void *hip_stream)
 {
     if (!e || !d_seg_offsets) return ZGPU_STREAM_ERROR;
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
     return deflate_device(e, static_cast<const uint8_t *>(d_in), in_bytes, d_seg_offsets, nseg, p, static_cast<uint8_t *>(d_out), out_cap,
-                          d_out_offsets, res, st);
+                          d_out_offsets, res, st, 0, nullptr, nullptr, 0, nullptr, false, d_items);
 }
 
-int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *seg_offsets, uint64_t nseg, const zgpu_deflate_params *p,
-                               void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_deflate_result *res)
+int zgpu_deflate_segments_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_seg_offsets, uint64_t nseg,
+                                 const zgpu_deflate_params *p, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                 zgpu_deflate_result *res, void *hip_stream)
+{
+    return zgpu_deflate_segments_items_device(e, d_in, in_bytes, d_seg_offsets, nseg, p, d_out, out_cap, d_out_offsets, res, nullptr, hip_stream);
+}
+
+int zgpu_deflate_segments_items_host(zgpu_engine *e, const void *in, const uint64_t *seg_offsets, uint64_t nseg, const zgpu_deflate_params *p,
+                                     void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_deflate_result *res, zgpu_deflate_item *items)
 {
     if (!e || !p || !res || !in || !out || !seg_offsets || nseg == 0) return fail(e, ZGPU_STREAM_ERROR, "null argument");
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
@@ -1045,19 +1053,28 @@ int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *s
     const uint64_t bound = (e->geo_w != 15 || e->geo_m != 8) ? in_bytes + zgpu_deflate_bound_geometry(nseg * (uint64_t)kChunkMax, kChunkMax, e->geo_w, e->geo_m) - nseg * (uint64_t)kChunkMax + ((nseg * (uint64_t)kChunkMax) >> 3)
                                                              : in_bytes + nseg * 40 + 16;
     const uint64_t framed = bound + nseg * (uint64_t)((p->flags & ZGPU_F_BGZF_WRAP) ? 26 : (p->flags & ZGPU_F_GZIP_WRAP) ? 18 : (p->flags & ZGPU_F_ZLIB_WRAP) ? 6 : 0);
-    int rc = ensure_stage(e, in_bytes + (nseg + 1) * sizeof(uint64_t) + 64, framed);
+    const uint64_t tab_off = (in_bytes + 63) & ~63ull; // segment table staged behind the data, the records (when asked for) behind the table
+    const uint64_t items_off = (tab_off + (nseg + 1) * sizeof(uint64_t) + 63) & ~63ull;
+    int rc = ensure_stage(e, items_off + (items ? nseg * sizeof(zgpu_deflate_item) : 0) + 64, framed);
     if (rc) return rc;
-    const uint64_t tab_off = (in_bytes + 63) & ~63ull; // segment table staged behind the data
     if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in, in, in_bytes, hipMemcpyHostToDevice, e->stream));
     ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in + tab_off, seg_offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    zgpu_deflate_item *d_items = items ? reinterpret_cast<zgpu_deflate_item *>(e->stage_in + items_off) : nullptr;
     rc = deflate_device(e, e->stage_in, in_bytes, reinterpret_cast<const uint64_t *>(e->stage_in + tab_off), nseg, p, e->stage_out, framed,
-                        nullptr, res, e->stream);
+                        nullptr, res, e->stream, 0, nullptr, nullptr, 0, nullptr, false, d_items);
     if (rc) return rc;
     if (res->out_bytes > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
     ZGPU_HIP_CHECK(hipMemcpyAsync(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost, e->stream));
     if (out_offsets) ZGPU_HIP_CHECK(hipMemcpyAsync(out_offsets, e->offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    if (items) ZGPU_HIP_CHECK(hipMemcpyAsync(items, d_items, nseg * sizeof(zgpu_deflate_item), hipMemcpyDeviceToHost, e->stream));
     ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
     return ZGPU_OK;
+}
+
+int zgpu_deflate_segments_host(zgpu_engine *e, const void *in, const uint64_t *seg_offsets, uint64_t nseg, const zgpu_deflate_params *p,
+                               void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_deflate_result *res)
+{
+    return zgpu_deflate_segments_items_host(e, in, seg_offsets, nseg, p, out, out_cap, out_offsets, res, nullptr);
 }
 
 // ---- BGZF encode: the segments path over a table cut on the device, and the end block behind it ----

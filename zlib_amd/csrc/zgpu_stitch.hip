@@ -10,8 +10,6 @@
 
 namespace zgpu {
 
-constexpr uint32_t kAdlerBase = 65521;
-
 // ---- Adler-32 of each chunk: A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521) ----
 __global__ void __launch_bounds__(256) adler_kernel(ChunkGeom g, ChunkMeta *meta)
 {
@@ -53,31 +51,7 @@ __global__ void __launch_bounds__(256) adler_kernel(ChunkGeom g, ChunkMeta *meta
 }
 
 
-// ---- CRC-32 (the reference's crc32.c:219-335 and crc32_combine :370-423, as polynomial arithmetic) ----
-// Reflected CRC-32 polynomial; a 32-bit word holds a polynomial over GF(2) with x^0 in bit 31.
-constexpr uint32_t kCrcPoly = 0xedb88320u;
-__host__ __device__ inline uint32_t crc_mulmod(uint32_t a, uint32_t b) // a(x) * b(x) mod P(x)
-{
-    uint32_t p = 0;
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        if (a & m) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ kCrcPoly : b >> 1;
-    }
-    return p;
-}
-__host__ __device__ inline uint32_t crc_xpow8n(uint64_t n) // x^(8n) mod P: the operator "append n zero bytes"
-{
-    uint32_t r = 0x80000000u, sq = 0x00800000u; // x^0, x^8
-    while (n) {
-        if (n & 1) r = crc_mulmod(sq, r);
-        sq = crc_mulmod(sq, sq);
-        n >>= 1;
-    }
-    return r;
-}
-// CRC of X||Y from the finished CRCs of X and Y and |Y| (what crc32_combine computes with its 32x32 bit matrices)
-__host__ __device__ inline uint32_t crc_join(uint32_t cx, uint32_t cy, uint32_t op_leny) { return crc_mulmod(op_leny, cx) ^ cy; }
-
+// ---- CRC-32 (the reference's crc32.c:219-335; the polynomial arithmetic of crc32_combine is in zgpu_common.h) ----
 // One 256-lane workgroup per chunk.  Lane t takes a slice of L = ceil(n/256) bytes, slices aligned to the END of the chunk
 // (so every right-hand operand of the tree below has a full power-of-two number of slices and one operator per level
 // serves all lanes; the short or empty slices are on the left, where length does not matter), table-driven bytewise
@@ -144,15 +118,6 @@ __global__ void __launch_bounds__(256) crc_kernel(ChunkGeom g, ChunkMeta *meta)
         __syncthreads();
     }
     if (tid == 0) { meta[c].crc = part[0]; meta[c].in_bytes = n; }
-}
-
-// Adler of X||Y from Adler(X) = (ax, bx), Adler(Y) = (ay, by), |Y| = ny:  a = ax + ay - 1,  b = bx + by + ny (ax - 1)
-__device__ inline void adler_join(uint32_t &ax, uint32_t &bx, uint32_t ay, uint32_t by, uint64_t ny)
-{
-    uint64_t rem = ny % kAdlerBase;
-    uint64_t a = ((uint64_t)ax + ay + kAdlerBase - 1) % kAdlerBase;
-    uint64_t b = ((uint64_t)bx + by + rem * ((ax + kAdlerBase - 1) % kAdlerBase)) % kAdlerBase;
-    ax = (uint32_t)a; bx = (uint32_t)b;
 }
 
 // One workgroup: exclusive scan of out_bytes over the batch (continuing RunState), ordered Adler combination.  frame: bytes of wrapper
@@ -360,6 +325,24 @@ void launch_frame(const uint8_t *slots, const ChunkMeta *meta, uint64_t *offsets
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, meta, nchunks, chunk0, offsets, static_cast<RunState *>(run), out_cap, with_crc ? 1u : 0u, frame);
     hipLaunchKernelGGL(stitch_kernel, dim3(nchunks), dim3(256), 0, st, slots, meta, offsets, chunk0, nchunks, out, out_cap, slot_stride, (uint32_t)h.n, frame);
     hipLaunchKernelGGL(frame_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, st, meta, offsets, seg_off, chunk0, nchunks, out, out_cap, h);
+}
+// ---- zgpu_deflate_segments_items_*: one record per segment, one lane each, from ChunkMeta and the scanned offsets (wrapper counted in) ----
+__global__ void __launch_bounds__(256) seg_items_kernel(const ChunkMeta *__restrict__ meta, const uint64_t *__restrict__ offsets, const uint64_t *__restrict__ seg_off, uint64_t chunk0,
+                                                        uint32_t nchunks, uint32_t with_crc, zgpu_deflate_item *items)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= nchunks) return;
+    const uint64_t gc = chunk0 + c;
+    const ChunkMeta m = meta[c];
+    zgpu_deflate_item r;
+    r.out_lo = offsets[gc]; r.out_bytes = offsets[gc + 1] - offsets[gc];
+    r.in_bytes = (uint32_t)(seg_off[gc + 1] - seg_off[gc]); r.data_type = m.data_type;
+    r.adler32 = m.adler_a | (m.adler_b << 16); r.crc32 = with_crc ? m.crc : 0u;
+    items[gc] = r;
+}
+void launch_seg_items(const ChunkMeta *meta, const uint64_t *offsets, const uint64_t *seg_off, uint64_t chunk0, uint32_t nchunks, bool with_crc, zgpu_deflate_item *items, hipStream_t st)
+{
+    hipLaunchKernelGGL(seg_items_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, st, meta, offsets, seg_off, chunk0, nchunks, with_crc ? 1u : 0u, items);
 }
 // ---- BGZF (ZGPU_F_BGZF_WRAP, zgpu_bgzf_deflate_*): the segment table of an input cut every block_size bytes, and the check that no segment of a
 // caller's table is longer than a block may be (flag[0] |= 1: too long or running backwards or leaving the buffer) ----

@@ -50,6 +50,16 @@ class InflateItem(C.Structure):
     _fields_ = [("code", C.c_int32), ("msg", C.c_uint32), ("out_bytes", C.c_uint64), ("in_used", C.c_uint64), ("adler32", C.c_uint32), ("crc32", C.c_uint32)]
 
 
+class DeflateItem(C.Structure):
+    """zgpu_deflate_item: one segment of zgpu_deflate_segments_items_*."""
+    _fields_ = [("out_lo", C.c_uint64), ("out_bytes", C.c_uint64), ("in_bytes", C.c_uint32), ("data_type", C.c_uint32), ("adler32", C.c_uint32), ("crc32", C.c_uint32)]
+
+
+class CheckItem(C.Structure):
+    """zgpu_check_item: the checksums of one item of zgpu_checksum_batch_*."""
+    _fields_ = [("adler32", C.c_uint32), ("crc32", C.c_uint32)]
+
+
 def library_path():
     # ZAMD_GPU_LIB: load another build of the engine (A/B measurements of kernel variants)
     return os.environ.get("ZAMD_GPU_LIB") or os.path.join(_HERE, "libzamd_gpu.so")
@@ -91,6 +101,10 @@ def load_library():
     L.zgpu_deflate_cont_host.argtypes = [vp, vp, u64, vp, u64, u64, C.POINTER(_Params), C.c_int, C.POINTER(ContState), vp, vp, vp, u32, vp, u64, C.POINTER(DeflateResult)]
     L.zgpu_deflate_segments_host.argtypes = [vp, vp, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult)]
     L.zgpu_deflate_segments_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp]
+    L.zgpu_deflate_segments_items_host.argtypes = [vp, vp, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp]
+    L.zgpu_deflate_segments_items_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp, vp]
+    L.zgpu_checksum_batch_host.argtypes = [vp, vp, u64, vp, u64, u32, vp]
+    L.zgpu_checksum_batch_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp]
     L.zgpu_inflate_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, C.POINTER(InflateResult), vp]
     L.zgpu_inflate_host.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, C.POINTER(InflateResult)]
     L.zgpu_deflate_segments_bound.argtypes = [u64, u64, u32]
@@ -235,8 +249,9 @@ class Engine:
         self._check(self.L.zgpu_deflate_set_geometry(self.h, window_bits, mem_level))
         self.geometry = (window_bits, mem_level)
 
-    def deflate_segments_host(self, buffers, level, flags=0, lz_impl=LZ_AUTO):
-        """Batch of independent buffers (each <= 65536 bytes) -> list of raw-deflate segments, one launch."""
+    def deflate_segments_host(self, buffers, level, flags=0, lz_impl=LZ_AUTO, want_items=False):
+        """Batch of independent buffers (each <= 65536 bytes) -> list of raw-deflate segments, one launch.  want_items: also the per-segment
+        records (zgpu_deflate_segments_items_host) as a list of (out_lo, out_bytes, in_bytes, data_type, adler32, crc32)."""
         import numpy as np
         sizes = [len(b) for b in buffers]
         offs = np.zeros(len(buffers) + 1, dtype=np.uint64)
@@ -249,11 +264,39 @@ class Engine:
         ooffs = np.zeros(len(buffers) + 1, dtype=np.uint64)
         p = _Params(level, 0, flags, lz_impl)
         res = DeflateResult()
-        self._check(self.L.zgpu_deflate_segments_host(self.h, blob.ctypes.data, offs.ctypes.data, len(buffers), C.byref(p),
-                                                      out.ctypes.data, cap, ooffs.ctypes.data, C.byref(res)))
+        if want_items:
+            cap += 26 * len(buffers)  # (room for any wrapper)
+            out = np.empty(cap, dtype=np.uint8)
+            items = (DeflateItem * max(len(buffers), 1))()
+            self._check(self.L.zgpu_deflate_segments_items_host(self.h, blob.ctypes.data, offs.ctypes.data, len(buffers), C.byref(p),
+                                                                out.ctypes.data, cap, ooffs.ctypes.data, C.byref(res), items))
+        else:
+            self._check(self.L.zgpu_deflate_segments_host(self.h, blob.ctypes.data, offs.ctypes.data, len(buffers), C.byref(p),
+                                                          out.ctypes.data, cap, ooffs.ctypes.data, C.byref(res)))
         self.last = res
         raw = out[: res.out_bytes].tobytes()
-        return [raw[int(ooffs[i]): int(ooffs[i + 1])] for i in range(len(buffers))]
+        segs = [raw[int(ooffs[i]): int(ooffs[i + 1])] for i in range(len(buffers))]
+        if want_items:
+            return segs, [(it.out_lo, it.out_bytes, it.in_bytes, it.data_type, it.adler32, it.crc32) for it in items[: len(buffers)]]
+        return segs
+
+    def checksum_batch_host(self, data, offsets, checks=CHECK_ADLER32 | CHECK_CRC32, items=None):
+        """Adler-32 / CRC-32 of the items data[offsets[k]:offsets[k+1]] in one call (zgpu_checksum_batch_host): a list of (adler32, crc32).
+        data: bytes-like, or a numpy uint8 array (used in place).  items: a CheckItem array to fill -- it is left as it was when the call fails,
+        and is itself what is returned (no list is built)."""
+        import numpy as np
+        arr = data if hasattr(data, "ctypes") else np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)[:-1]
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        given = items is not None
+        if not given:
+            items = (CheckItem * max(n, 1))()
+        self._check(self.L.zgpu_checksum_batch_host(self.h, arr.ctypes.data if arr.size else None, arr.size, offs.ctypes.data, n, checks, items))
+        return items if given else [(items[k].adler32, items[k].crc32) for k in range(n)]
+
+    def checksum_batch_device(self, d_in, in_bytes, d_offsets, n, d_items, checks=CHECK_ADLER32 | CHECK_CRC32, stream=None):
+        """Device pointers as ints: d_offsets holds n + 1 uint64, d_items n records of 8 bytes (zgpu_check_item).  Blocks until they are written."""
+        self._check(self.L.zgpu_checksum_batch_device(self.h, d_in, in_bytes, d_offsets, n, checks, d_items, stream))
 
     def deflate_batch_host(self, buffers, level, wrap="zlib", strategy=0):
         """Batch of independent buffers (each <= 65536 bytes) -> one complete stream per buffer, one launch: wrap "zlib" (what compress2()

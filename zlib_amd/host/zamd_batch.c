@@ -7,6 +7,7 @@
  * The batch calls use an engine of their own (created on first use, on the device ZAMD_DEVICE names, like the stream API's). */
 #include "../../include/zamd_batch.h"
 #include "../../include/zamd_gpu.h"
+#include "zamd_host.h"
 #include <pthread.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -19,7 +20,7 @@
 static pthread_mutex_t g_batch_lock = PTHREAD_MUTEX_INITIALIZER; /* one call at a time on the engine (one stream, one workspace) */
 static zgpu_engine *g_batch_engine;
 
-static zgpu_engine *batch_engine_lock(void)
+zgpu_engine *zamd_batch_engine_lock(void)
 {
     pthread_mutex_lock(&g_batch_lock);
     if (!g_batch_engine) {
@@ -29,7 +30,7 @@ static zgpu_engine *batch_engine_lock(void)
     if (!g_batch_engine) pthread_mutex_unlock(&g_batch_lock);
     return g_batch_engine;
 }
-static void batch_engine_unlock(void) { pthread_mutex_unlock(&g_batch_lock); }
+void zamd_batch_engine_unlock(void) { pthread_mutex_unlock(&g_batch_lock); }
 
 static int first_failure(const int *status, size_t n)
 {
@@ -111,11 +112,11 @@ EXPORT int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef
             p.level = level; p.flags = flags; p.lz_impl = ZGPU_LZ_AUTO;
             zgpu_deflate_result res;
             memset(&res, 0, sizeof res);
-            zgpu_engine *e = batch_engine_lock();
+            zgpu_engine *e = zamd_batch_engine_lock();
             if (!e) rc = ZGPU_ERRNO;
             else {
                 rc = zgpu_deflate_segments_host(e, in, seg, nb, &p, out, cap, ooff, &res);
-                batch_engine_unlock();
+                zamd_batch_engine_unlock();
             }
             for (uint64_t i = 0; i < nb; i++) {
                 const size_t k = idx[i];
@@ -163,11 +164,11 @@ EXPORT int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Byte
                     ai += sourceLen[k]; ao += destLen[k];
                 }
             ioff[nb] = ai; ooff[nb] = ao;
-            zgpu_engine *e = batch_engine_lock();
+            zgpu_engine *e = zamd_batch_engine_lock();
             if (!e) rc = ZGPU_ERRNO;
             else {
                 rc = zgpu_inflate_batch_host(e, in, in_total, ioff, nb, wrap, 0, out, out_total, ooff, items, NULL);
-                batch_engine_unlock();
+                zamd_batch_engine_unlock();
             }
             for (uint64_t i = 0; i < nb; i++) {
                 const size_t k = idx[i];
@@ -189,3 +190,42 @@ EXPORT int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Byte
         if (sourceLen[k] >= BATCH_IN_MAX) status[k] = uncompress_one(dest[k], &destLen[k], source[k], sourceLen[k], windowBits);
     return first_failure(status, n);
 }
+
+/* crc32() / adler32() of many buffers: the items' own checksums from one zgpu_checksum_batch_host, the caller's running values folded in here */
+static int checksum_batch(uLong *val, const Bytef *const *buf, const uLong *len, size_t n, int want_crc)
+{
+    if (n && (!val || !buf || !len)) return Z_STREAM_ERROR;
+    uint64_t total = 0;
+    for (size_t k = 0; k < n; k++) {
+        if ((!buf[k] && len[k]) || len[k] >= 0xFFFFFFFFul) return Z_STREAM_ERROR;
+        total += len[k];
+    }
+    if (n == 0) return Z_OK;
+    uint8_t *in = malloc(total + 1);
+    uint64_t *off = malloc((n + 1) * sizeof *off);
+    zgpu_check_item *items = malloc(n * sizeof *items);
+    int rc = in && off && items ? ZGPU_OK : ZGPU_MEM_ERROR;
+    if (rc == ZGPU_OK) {
+        uint64_t at = 0;
+        for (size_t k = 0; k < n; k++) {
+            off[k] = at;
+            if (len[k]) memcpy(in + at, buf[k], len[k]);
+            at += len[k];
+        }
+        off[n] = at;
+        zgpu_engine *e = zamd_batch_engine_lock();
+        if (!e) rc = ZGPU_MEM_ERROR;
+        else {
+            rc = zgpu_checksum_batch_host(e, in, total, off, n, want_crc ? ZGPU_CHECK_CRC32 : ZGPU_CHECK_ADLER32, items);
+            zamd_batch_engine_unlock();
+        }
+    }
+    if (rc == ZGPU_OK)
+        for (size_t k = 0; k < n; k++)
+            val[k] = want_crc ? crc32_combine(val[k], items[k].crc32, (z_off_t)len[k]) : adler32_combine(val[k], items[k].adler32, (z_off_t)len[k]);
+    free(in); free(off); free(items);
+    return rc == ZGPU_OK ? Z_OK : rc == ZGPU_STREAM_ERROR ? Z_STREAM_ERROR : Z_MEM_ERROR;
+}
+
+EXPORT int zamd_crc32_batch(uLong *crc, const Bytef *const *buf, const uLong *len, size_t n) { return checksum_batch(crc, buf, len, n, 1); }
+EXPORT int zamd_adler32_batch(uLong *adler, const Bytef *const *buf, const uLong *len, size_t n) { return checksum_batch(adler, buf, len, n, 0); }

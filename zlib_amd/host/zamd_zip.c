@@ -4,7 +4,9 @@
  * compressor said text :1092-1093.  Reading follows qcsrc/unzip.c: end record search :320-383, central directory :583-717, local
  * header check :983-1050. */
 #include "../../include/zamd_zip.h"
+#include "../../include/zamd_zip_batch.h"
 #include "../../include/zamd_zlib.h"
+#include "zamd_host.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -61,32 +63,24 @@ static int deflate_member(const uint8_t *data, unsigned long len, int level, uin
     return ZAMD_ZIP_OK;
 }
 
-EXPORT int zamd_zip_add(zamd_zip *z, const char *name, const void *data, unsigned long len, int level, unsigned long dos_date, const char *comment)
+static unsigned long level_flag(int level) /* zip.c:760-766 */
 {
-    if (!z || !z->fp || (!data && len) || level < -1 || level > 9 || len >= 0xFFFFFFFFul) return ZAMD_ZIP_PARAMERROR;
-    if (!name) name = "-";
-    const size_t nname = strlen(name), ncomm = comment ? strlen(comment) : 0;
-    if (nname > 0xFFFFu || ncomm > 0xFFFFu || z->entries >= 0xFFFFu) return ZAMD_ZIP_PARAMERROR; /* 16-bit fields (no zip64, as minizip 1.01e) */
-    const int method = level != 0 ? Z_DEFLATED : 0;
     unsigned long flag = 0;
     if (level == 8 || level == 9) flag |= 2;
     if (level == 2) flag |= 4;
     if (level == 1) flag |= 6;
-    uint8_t *gz = NULL; size_t gz_len = 0; unsigned long crc = 0; int data_type = Z_UNKNOWN;
-    const uint8_t *body = (const uint8_t *)data; size_t body_len = len;
-    if (method) {
-        const int rc = deflate_member((const uint8_t *)data, len, level, &gz, &gz_len, &crc, &data_type);
-        if (rc != ZAMD_ZIP_OK) return rc;
-        body = gz + 10; body_len = gz_len - 18;
-    } else {
-        for (unsigned long o = 0; o < len; o += 0x40000000ul) crc = crc32(crc, (const Bytef *)data + o, (uInt)(len - o < 0x40000000ul ? len - o : 0x40000000ul));
-    }
+    return flag;
+}
+
+/* one member's local header, name and body at the file's end, and its entry in the directory kept in memory */
+static int write_member(zamd_zip *z, const char *name, size_t nname, const char *comment, size_t ncomm, int method, unsigned long flag, unsigned long dos_date,
+                        unsigned long crc, const uint8_t *body, size_t body_len, unsigned long len, int data_type)
+{
     const long pos = ftell(z->fp);
     uint8_t lh[30];
     put32(lh, 0x04034b50ul); put16(lh + 4, 20); put16(lh + 6, flag); put16(lh + 8, (unsigned long)method); put32(lh + 10, dos_date);
     put32(lh + 14, crc); put32(lh + 18, (unsigned long)body_len); put32(lh + 22, len); put16(lh + 26, (unsigned long)nname); put16(lh + 28, 0);
     int ok = fwrite(lh, 1, 30, z->fp) == 30 && fwrite(name, 1, nname, z->fp) == nname && (body_len == 0 || fwrite(body, 1, body_len, z->fp) == body_len);
-    free(gz);
     if (!ok || pos < 0) return ZAMD_ZIP_ERRNO;
     const size_t need = 46 + nname + ncomm;
     if (z->cdir_len + need > z->cdir_cap) {
@@ -105,6 +99,97 @@ EXPORT int zamd_zip_add(zamd_zip *z, const char *name, const void *data, unsigne
     z->cdir_len += need; z->entries++;
     return ZAMD_ZIP_OK;
 }
+
+EXPORT int zamd_zip_add(zamd_zip *z, const char *name, const void *data, unsigned long len, int level, unsigned long dos_date, const char *comment)
+{
+    if (!z || !z->fp || (!data && len) || level < -1 || level > 9 || len >= 0xFFFFFFFFul) return ZAMD_ZIP_PARAMERROR;
+    if (!name) name = "-";
+    const size_t nname = strlen(name), ncomm = comment ? strlen(comment) : 0;
+    if (nname > 0xFFFFu || ncomm > 0xFFFFu || z->entries >= 0xFFFFu) return ZAMD_ZIP_PARAMERROR; /* 16-bit fields (no zip64, as minizip 1.01e) */
+    const int method = level != 0 ? Z_DEFLATED : 0;
+    uint8_t *gz = NULL; size_t gz_len = 0; unsigned long crc = 0; int data_type = Z_UNKNOWN;
+    const uint8_t *body = (const uint8_t *)data; size_t body_len = len;
+    if (method) {
+        const int rc = deflate_member((const uint8_t *)data, len, level, &gz, &gz_len, &crc, &data_type);
+        if (rc != ZAMD_ZIP_OK) return rc;
+        body = gz + 10; body_len = gz_len - 18;
+    } else {
+        for (unsigned long o = 0; o < len; o += 0x40000000ul) crc = crc32(crc, (const Bytef *)data + o, (uInt)(len - o < 0x40000000ul ? len - o : 0x40000000ul));
+    }
+    const int rc = write_member(z, name, nname, comment, ncomm, method, level_flag(level), dos_date, crc, body, body_len, len, data_type);
+    free(gz);
+    return rc;
+}
+
+#ifndef ZAMD_SAN_NO_ENGINE /* (a build without the batch engine -- zamd_batch.c is not part of it -- has no batch calls) */
+#define SEG_MAX 65536ul
+EXPORT int zamd_zip_add_batch(zamd_zip *z, size_t n, const char *const *name, const void *const *data, const unsigned long *len, int level,
+                              const unsigned long *dos_date, const char *const *comment)
+{
+    if (!z || !z->fp || level < -1 || level > 9) return ZAMD_ZIP_PARAMERROR;
+    if (n == 0) return ZAMD_ZIP_OK;
+    if (!name || !data || !len || !dos_date || z->entries > 0xFFFFu || n > 0xFFFFu - z->entries) return ZAMD_ZIP_PARAMERROR;
+    for (size_t k = 0; k < n; k++)
+        if ((!data[k] && len[k]) || len[k] >= 0xFFFFFFFFul || (name[k] && strlen(name[k]) > 0xFFFFu) || (comment && comment[k] && strlen(comment[k]) > 0xFFFFu))
+            return ZAMD_ZIP_PARAMERROR;
+    const int method = level != 0 ? Z_DEFLATED : 0;
+    /* the members of the one engine call: at level 0 all of them (checksums), else those of at most a segment's size (compressed) */
+    uint64_t nb = 0, in_total = 0;
+    for (size_t k = 0; k < n; k++)
+        if (!method || len[k] <= SEG_MAX) { nb++; in_total += len[k]; }
+    uint8_t *in = NULL, *out = NULL; uint64_t *seg = NULL; size_t *at = NULL; /* at[k]: member k's place among the call's items */
+    zgpu_deflate_item *ditems = NULL; zgpu_check_item *citems = NULL;
+    int err = ZAMD_ZIP_OK;
+    if (nb) {
+        const uint64_t cap = method ? zgpu_deflate_segments_bound(nb, in_total, ZGPU_F_FINAL) : 0;
+        in = (uint8_t *)malloc(in_total + 1); seg = (uint64_t *)malloc((nb + 1) * sizeof *seg); at = (size_t *)malloc(n * sizeof *at);
+        if (method) { out = (uint8_t *)malloc(cap); ditems = (zgpu_deflate_item *)malloc(nb * sizeof *ditems); }
+        else citems = (zgpu_check_item *)malloc(nb * sizeof *citems);
+        if (!in || !seg || !at || (method ? !out || !ditems : !citems)) err = ZAMD_ZIP_INTERNALERROR;
+        if (err == ZAMD_ZIP_OK) {
+            uint64_t j = 0, pos = 0;
+            for (size_t k = 0; k < n; k++)
+                if (!method || len[k] <= SEG_MAX) {
+                    seg[j] = pos; at[k] = (size_t)j++;
+                    if (len[k]) memcpy(in + pos, data[k], len[k]);
+                    pos += len[k];
+                }
+            seg[nb] = pos;
+            zgpu_engine *e = zamd_batch_engine_lock();
+            if (!e) err = ZAMD_ZIP_INTERNALERROR;
+            else {
+                int rc;
+                if (method) {
+                    zgpu_deflate_params p; zgpu_deflate_result res;
+                    memset(&p, 0, sizeof p); memset(&res, 0, sizeof res);
+                    p.level = level < 0 ? 6 : level; p.flags = ZGPU_F_FINAL | ZGPU_F_CRC32; p.lz_impl = ZGPU_LZ_AUTO;
+                    rc = zgpu_deflate_segments_items_host(e, in, seg, nb, &p, out, cap, NULL, &res, ditems);
+                } else rc = zgpu_checksum_batch_host(e, in, in_total, seg, nb, ZGPU_CHECK_CRC32, citems);
+                zamd_batch_engine_unlock();
+                if (rc != ZGPU_OK) err = ZAMD_ZIP_INTERNALERROR;
+            }
+        }
+    }
+    /* the file, in the callers' order; a member too large for a segment is compressed at its turn */
+    for (size_t k = 0; k < n && err == ZAMD_ZIP_OK; k++) {
+        const char *nm = name[k] ? name[k] : "-", *cm = comment ? comment[k] : NULL;
+        const size_t nname = strlen(nm), ncomm = cm ? strlen(cm) : 0;
+        const unsigned long flag = level_flag(level);
+        if (!method) err = write_member(z, nm, nname, cm, ncomm, 0, flag, dos_date[k], citems[at[k]].crc32, (const uint8_t *)data[k], len[k], len[k], Z_UNKNOWN);
+        else if (len[k] <= SEG_MAX) {
+            const zgpu_deflate_item *it = &ditems[at[k]];
+            err = write_member(z, nm, nname, cm, ncomm, method, flag, dos_date[k], it->crc32, out + it->out_lo, (size_t)it->out_bytes, len[k], (int)it->data_type);
+        } else {
+            uint8_t *gz = NULL; size_t gz_len = 0; unsigned long crc = 0; int data_type = Z_UNKNOWN;
+            err = deflate_member((const uint8_t *)data[k], len[k], level, &gz, &gz_len, &crc, &data_type);
+            if (err == ZAMD_ZIP_OK) err = write_member(z, nm, nname, cm, ncomm, method, flag, dos_date[k], crc, gz + 10, gz_len - 18, len[k], data_type);
+            free(gz);
+        }
+    }
+    free(in); free(out); free(seg); free(at); free(ditems); free(citems);
+    return err;
+}
+#endif
 
 EXPORT int zamd_zip_close(zamd_zip *z, const char *global_comment)
 {
@@ -236,6 +321,119 @@ EXPORT long zamd_unzip_read(zamd_unzip *u, int i, void *out, unsigned long cap)
     if (rc == Z_STREAM_END && opos == t->uncompressed_size) return (long)opos;
     return rc == Z_DATA_ERROR ? ZAMD_ZIP_CRCERROR : ZAMD_ZIP_BADZIPFILE;
 }
+#ifndef ZAMD_SAN_NO_ENGINE
+#define BATCH_IN_MAX (1ul << 29) /* the batch decoder's limit of compressed bytes per item */
+/* the directory and local-header checks of zamd_unzip_read for entry t, in its order; on ZAMD_ZIP_OK the file stands at the member's body */
+static int member_seek(zamd_unzip *u, const zamd_zip_entry *t, unsigned long cap)
+{
+    if (t->uncompressed_size > cap) return ZAMD_ZIP_PARAMERROR;
+    if (t->method != 0 && t->method != Z_DEFLATED) return ZAMD_ZIP_BADZIPFILE;
+    if ((unsigned long)u->fsize < 30ul || t->local_header_offset > (unsigned long)u->fsize - 30ul || t->compressed_size > (unsigned long)u->fsize - t->local_header_offset - 30ul) return ZAMD_ZIP_BADZIPFILE;
+    uint8_t lh[30];
+    if (fseek(u->fp, (long)t->local_header_offset, SEEK_SET) || fread(lh, 1, 30, u->fp) != 30) return ZAMD_ZIP_ERRNO;
+    if (get32(lh) != 0x04034b50ul || (int)get16(lh + 8) != t->method) return ZAMD_ZIP_BADZIPFILE;
+    if (fseek(u->fp, (long)(get16(lh + 26) + get16(lh + 28)), SEEK_CUR)) return ZAMD_ZIP_ERRNO;
+    return ZAMD_ZIP_OK;
+}
+
+EXPORT int zamd_unzip_read_batch(zamd_unzip *u, const int *index, size_t n, void *const *out, const unsigned long *cap, long *result)
+{
+    enum { ONE = 0, STORED = 1, DEFLATED = 2, DONE = 3 }; /* how item k is served */
+    if (!u || (n && (!out || !cap || !result))) return ZAMD_ZIP_PARAMERROR;
+    if (n == 0) return ZAMD_ZIP_OK;
+    uint8_t *kind = (uint8_t *)calloc(n, 1);
+    size_t *at = (size_t *)malloc(n * sizeof *at); /* at[k]: item k's place in its engine call */
+    long *body = (long *)malloc(n * sizeof *body); /* body[k]: where a deflated member's data starts in the file */
+    if (!kind || !at || !body) { free(kind); free(at); free(body); return ZAMD_ZIP_INTERNALERROR; }
+    /* pass 1: every item's checks; what the two engine calls will hold */
+    uint64_t nd = 0, d_in = 0, d_out = 0, ns = 0, s_in = 0;
+    for (size_t k = 0; k < n; k++) {
+        const int i = index ? index[k] : (int)k;
+        if (i < 0 || i >= u->n || (!out[k] && cap[k])) { result[k] = ZAMD_ZIP_PARAMERROR; kind[k] = DONE; continue; }
+        const zamd_zip_entry *t = &u->ent[i];
+        const int rc = member_seek(u, t, cap[k]);
+        if (rc != ZAMD_ZIP_OK) { result[k] = rc; kind[k] = DONE; continue; }
+        if (t->method == 0) {
+            if (t->compressed_size != t->uncompressed_size) { result[k] = ZAMD_ZIP_BADZIPFILE; kind[k] = DONE; continue; }
+            if (fread(out[k], 1, t->uncompressed_size, u->fp) != t->uncompressed_size) { result[k] = ZAMD_ZIP_ERRNO; kind[k] = DONE; continue; }
+            kind[k] = STORED; at[k] = (size_t)ns++; s_in += t->uncompressed_size;
+        } else if (t->compressed_size < BATCH_IN_MAX) {
+            if ((body[k] = ftell(u->fp)) < 0) { result[k] = ZAMD_ZIP_ERRNO; kind[k] = DONE; continue; }
+            kind[k] = DEFLATED; at[k] = (size_t)nd++; d_in += 18 + (uint64_t)t->compressed_size; d_out += t->uncompressed_size;
+        } /* else ONE */
+    }
+    /* stored members: the bytes are in place; their CRC-32s in one call */
+    if (ns) {
+        uint8_t *in = (uint8_t *)malloc(s_in + 1);
+        uint64_t *off = (uint64_t *)malloc((ns + 1) * sizeof *off);
+        zgpu_check_item *items = (zgpu_check_item *)malloc(ns * sizeof *items);
+        int ok = in && off && items;
+        if (ok) {
+            uint64_t pos = 0;
+            for (size_t k = 0; k < n; k++)
+                if (kind[k] == STORED) {
+                    const unsigned long sz = u->ent[index ? index[k] : (int)k].uncompressed_size;
+                    off[at[k]] = pos;
+                    if (sz) memcpy(in + pos, out[k], sz);
+                    pos += sz;
+                }
+            off[ns] = pos;
+            zgpu_engine *e = zamd_batch_engine_lock();
+            ok = e != NULL;
+            if (e) { ok = zgpu_checksum_batch_host(e, in, s_in, off, ns, ZGPU_CHECK_CRC32, items) == ZGPU_OK; zamd_batch_engine_unlock(); }
+        }
+        for (size_t k = 0; k < n; k++)
+            if (kind[k] == STORED) {
+                const zamd_zip_entry *t = &u->ent[index ? index[k] : (int)k];
+                result[k] = !ok ? ZAMD_ZIP_INTERNALERROR : items[at[k]].crc32 == (uint32_t)t->crc32 ? (long)t->uncompressed_size : ZAMD_ZIP_CRCERROR;
+            }
+        free(in); free(off); free(items);
+    }
+    /* deflated members: each framed as zamd_unzip_read frames it -- gzip header, the raw data, the directory's CRC-32 and size -- all in one call */
+    if (nd) {
+        uint8_t *in = (uint8_t *)malloc(d_in + 1), *dec = (uint8_t *)malloc(d_out + 1);
+        uint64_t *ioff = (uint64_t *)malloc((nd + 1) * sizeof *ioff), *ooff = (uint64_t *)malloc((nd + 1) * sizeof *ooff);
+        zgpu_inflate_item *items = (zgpu_inflate_item *)malloc(nd * sizeof *items);
+        int ok = in && dec && ioff && ooff && items;
+        if (ok) {
+            static const uint8_t gh[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3};
+            uint64_t pi = 0, po = 0;
+            for (size_t k = 0; k < n; k++)
+                if (kind[k] == DEFLATED) {
+                    const zamd_zip_entry *t = &u->ent[index ? index[k] : (int)k];
+                    ioff[at[k]] = pi; ooff[at[k]] = po;
+                    memcpy(in + pi, gh, 10);
+                    if (fseek(u->fp, body[k], SEEK_SET) || fread(in + pi + 10, 1, t->compressed_size, u->fp) != t->compressed_size) {
+                        result[k] = ZAMD_ZIP_ERRNO; kind[k] = DONE; memset(in + pi + 10, 0, t->compressed_size); /* (its item decodes to an error nobody reads) */
+                    }
+                    put32(in + pi + 10 + t->compressed_size, t->crc32); put32(in + pi + 14 + t->compressed_size, t->uncompressed_size);
+                    pi += 18 + (uint64_t)t->compressed_size; po += t->uncompressed_size;
+                }
+            ioff[nd] = pi; ooff[nd] = po;
+            zgpu_engine *e = zamd_batch_engine_lock();
+            ok = e != NULL;
+            if (e) { ok = zgpu_inflate_batch_host(e, in, d_in, ioff, nd, ZGPU_WRAP_GZIP, 0, dec, d_out, ooff, items, NULL) == ZGPU_OK; zamd_batch_engine_unlock(); }
+        }
+        for (size_t k = 0; k < n; k++)
+            if (kind[k] == DEFLATED) {
+                const zamd_zip_entry *t = &u->ent[index ? index[k] : (int)k];
+                if (!ok) result[k] = ZAMD_ZIP_INTERNALERROR;
+                else if (items[at[k]].code == ZGPU_OK) { /* (CRC-32 and size have been checked on the device: out_bytes is the directory's size) */
+                    if (t->uncompressed_size) memcpy(out[k], dec + ooff[at[k]], t->uncompressed_size);
+                    result[k] = (long)t->uncompressed_size;
+                } else kind[k] = ONE; /* refused: the code is zamd_unzip_read's own */
+            }
+        free(in); free(dec); free(ioff); free(ooff); free(items);
+    }
+    for (size_t k = 0; k < n; k++)
+        if (kind[k] == ONE) result[k] = zamd_unzip_read(u, index ? index[k] : (int)k, out[k], cap[k]);
+    free(kind); free(at); free(body);
+    for (size_t k = 0; k < n; k++)
+        if (result[k] < 0) return (int)result[k];
+    return ZAMD_ZIP_OK;
+}
+#endif
+
 EXPORT int zamd_unzip_close(zamd_unzip *u)
 {
     if (!u) return ZAMD_ZIP_PARAMERROR;
