@@ -244,8 +244,9 @@ uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t 
  * end block is appended; empty input gives the end block alone.  level 1..9 (the segment engine has no level 0: stored blocks are not written here),
  * strategy as in zgpu_deflate_params.  out_offsets (optional; nblocks + 2 entries, device memory for the device entry): where every block begins, where
  * the end block begins, the file's length.  res->nchunks = nblocks (the end block not counted), res->crc32 / adler32 cover the whole input.
- * Out of scope: level 0, general multi-member gzip whose members carry no size, preset dictionaries, htslib's .gzi file I/O (the two arrays of
- * zgpu_bgzf_index_device hold its content; writing the file of 8-byte pairs is a caller's loop), BAM / VCF record awareness. */
+ * Out of scope: level 0, preset dictionaries, htslib's .gzi file I/O (the two arrays of
+ * zgpu_bgzf_index_device hold its content; writing the file of 8-byte pairs is a caller's loop), BAM / VCF record awareness.  General multi-member
+ * gzip, whose members carry no size, is zgpu_gzip_inflate_* below. */
 uint64_t zgpu_bgzf_bound(uint64_t in_bytes, uint32_t block_size); /* output capacity that is enough */
 int zgpu_bgzf_deflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, int level, int strategy, uint32_t block_size, void *d_out, uint64_t out_cap,
                              uint64_t *d_out_offsets, zgpu_deflate_result *res, void *hip_stream);
@@ -328,7 +329,7 @@ int zgpu_inflate_set_checks(zgpu_engine *e, uint32_t mask);
  * stream of its own and gets its own record in d_items[k].  wrap says what the items carry, as inflateInit2's windowBits does
  * (qcsrc/inflate.c:589-760): ZGPU_WRAP_RAW -15, ZGPU_WRAP_ZLIB 15, ZGPU_WRAP_GZIP 31, ZGPU_WRAP_AUTO 47 (zlib or gzip by the magic).  An item must
  * reach its final block; what follows its trailer (or, raw, its final block) is left alone.  Limits per item: < 512 MiB compressed, < 4 GiB
- * decoded (an item past them gets ZGPU_DATA_ERROR with "segment table out of range" / "segment decodes to more than chunk_size bytes").  No preset dictionary (zgpu_inflate_set_dictionary does not apply); multi-member gzip items decode their first member.
+ * decoded (an item past them gets ZGPU_DATA_ERROR with "segment table out of range" / "segment decodes to more than chunk_size bytes").  No preset dictionary (zgpu_inflate_set_dictionary does not apply); multi-member gzip items decode their first member (a whole multi-member file: zgpu_gzip_inflate_* below).
  * Record of item k:
  *   code       ZGPU_OK, ZGPU_DATA_ERROR, ZGPU_BUF_ERROR (out_bytes = the size that would have been needed) or 2 (Z_NEED_DICT: FDICT set)
  *   msg        index for zgpu_inflate_message() (the reference's text for a header or trailer failure)
@@ -380,6 +381,34 @@ int zgpu_bgzf_index_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, 
 int zgpu_bgzf_inflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, zgpu_inflate_item *d_items,
                              zgpu_inflate_result *res, void *hip_stream);
 int zgpu_bgzf_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, void *out, uint64_t out_cap, zgpu_inflate_item *items, zgpu_inflate_result *res);
+
+/* ---- multi-member gzip (RFC 1952 2.2: `cat a.gz b.gz`, logs appended to one .gz, .warc.gz), all members in one batch (zlib_amd/csrc/zgpu_gzip.hip) ----
+ * out receives the members' decoded bytes, concatenated in file order.  Member k reads in[in_offsets[k] .. in_offsets[k+1]) and writes
+ * out[out_offsets[k] .. out_offsets[k+1]); items[k] is what zgpu_inflate_batch_* gives for it with ZGPU_WRAP_GZIP (the same header rules, CRC-32 and
+ * ISIZE checked on the device, the same message indices).  The three arrays are optional (device memory for the device entry); cap_members is their
+ * room: cap_members + 1 entries for the two offset tables, cap_members records.  in_bytes / 20 is always enough (10 bytes of header, 2 of deflate
+ * data, 8 of trailer).  More members than cap_members: ZGPU_BUF_ERROR with *nmembers set and nothing written to the arrays.
+ * A member's end is known only once it is decoded: every position that looks like a member header (1f 8b 08, no reserved flag bit) is decoded as a
+ * candidate, and the members are the candidates that the chain from byte 0 visits -- a signature inside a stored block, even a complete valid member
+ * held as payload (a .tar.gz of .gz files), is none.  A file without such payload is decoded once; otherwise the members are decoded a second time
+ * into their final places (zgpu_gzip_members_count).  A false candidate costs one wasted decode; the workspace is proportional to the number of
+ * candidates, and a file of signatures whose tables cannot be held gives ZGPU_MEM_ERROR.
+ *   empty input                  ZGPU_OK, a valid file of no members: *nmembers = 0, res->out_bytes = 0
+ *   no member header at byte 0   ZGPU_DATA_ERROR, res->first_bad_chunk = 0, res->error_msg = "incorrect header check" (there is no transparent mode here)
+ *   a member that fails          (header, damaged data, input cut short, CRC-32, ISIZE) ZGPU_DATA_ERROR: res->first_bad_chunk its index, res->error_msg
+ *                                its message, res->out_bytes the total of the members in front of it, whose bytes are in place, res->in_used where the
+ *                                failed member begins, *nmembers the good ones (the arrays describe those; items[*nmembers] is the failed member's
+ *                                record when cap_members has room for it).  Nothing behind the failed member is delivered: that is where gzread() stops.
+ *   bytes behind the last member that begin no member header (padding, zeros)
+ *                                ZGPU_OK, ignored as gzread() ignores them; res->in_used = the end of the last member, in_used < in_bytes tells
+ *   out_cap too small            ZGPU_BUF_ERROR, res->out_bytes = the size needed; the contents of out are unspecified
+ * Limits per member are a batch item's: < 512 MiB compressed, < 4 GiB decoded (a member of 4 GiB or more, whose ISIZE wraps, is refused).  No preset
+ * dictionary.  res->adler32 / crc32 are not computed (1 / 0).  The device entry blocks until the result is known; the host entry uploads the file once. */
+int zgpu_gzip_inflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, uint64_t *d_in_offsets, uint64_t *d_out_offsets,
+                             zgpu_inflate_item *d_items, uint64_t cap_members, uint64_t *nmembers, zgpu_inflate_result *res, void *hip_stream);
+int zgpu_gzip_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, void *out, uint64_t out_cap, uint64_t *in_offsets, uint64_t *out_offsets,
+                           zgpu_inflate_item *items, uint64_t cap_members, uint64_t *nmembers, zgpu_inflate_result *res);
+uint64_t zgpu_gzip_members_count(int which); /* diagnostics: 0 = calls that decoded every member once, 1 = calls that needed the second decode */
 
 /* ---- checksums (qcsrc/adler32.c:57-149) ---- */
 int zgpu_adler32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *adler_out, void *hip_stream);

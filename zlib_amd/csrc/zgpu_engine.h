@@ -94,6 +94,10 @@ struct zgpu_engine {
     DevBuf<uint32_t> bz_cnt, bz_isize, bz_jump_a, bz_jump_b, bz_reach, bz_res;
     DevBuf<uint64_t> bz_base, bz_pos, bz_next, bz_in_off, bz_out_off;
     DevBuf<zgpu_inflate_item> bz_items;
+    // multi-member gzip (zgpu_gzip.hip): the finder's bz_* buffers serve it too; per candidate the input end, the ISIZE guess, the trial layout
+    // (one more), where the member ends; the candidates' records of the first decode (bz_items holds the members')
+    DevBuf<uint64_t> gz_in_end, gz_trial, gz_next; DevBuf<uint32_t> gz_guess;
+    DevBuf<zgpu_inflate_item> gz_items;
     // batch checksums (zgpu_checksum.hip): pieces in front of every item (n + 1), the bad-table flag, three words per piece (a, b, crc)
     DevBuf<uint64_t> ck_piece0; DevBuf<uint32_t> ck_flag, ck_part;
     // profiling
@@ -195,6 +199,9 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
 
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,
                       const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st);
+int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,
+                             uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_lo, const uint64_t *d_out_hi, zgpu_inflate_item *d_items, uint64_t *nfailed,
+                             const BatchItemState **states, hipStream_t st);
 
 // ---- zgpu_checksum.hip ----
 int checksum_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t n, uint32_t checks, zgpu_check_item *d_items, hipStream_t st);

@@ -1183,13 +1183,15 @@ __device__ inline uint32_t crc_bytes(uint32_t c, const uint8_t *p, uint64_t n) /
 
 // one lane per item: the wrapper in front of the deflate data (HEAD .. HCRC / DICTID of inflate(), inflate.c:589-760, windowBits -15 / 15 / 31 / 47).
 // bad[0] |= 1: an offsets table that runs backwards or leaves its buffer (a bad argument of the call; such an item is made empty here).
-__global__ void __launch_bounds__(256) batch_header_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ in_off, uint64_t n,
-                                                           uint32_t wrap, uint64_t out_cap, const uint64_t *__restrict__ out_off, uint64_t *seg,
+// Item k reads in[in_lo[k], in_hi[k]) and owns out[out_lo[k], out_hi[k]): four tables, so that a caller whose items overlap (zgpu_gzip.hip) can say
+// so; an offsets table of n + 1 entries is (off, off + 1).
+__global__ void __launch_bounds__(256) batch_header_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *in_lo, const uint64_t *in_hi, uint64_t n,
+                                                           uint32_t wrap, uint64_t out_cap, const uint64_t *out_lo, const uint64_t *out_hi, uint64_t *seg,
                                                            BatchItemState *items, uint32_t *bad)
 {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    uint64_t lo = in_off[k], hi = in_off[k + 1], ol = out_off[k], oh = out_off[k + 1];
+    uint64_t lo = in_lo[k], hi = in_hi[k], ol = out_lo[k], oh = out_hi[k];
     if (lo > hi || hi > in_bytes || ol > oh || oh > out_cap) { atomicOr(bad, 1u); lo = hi = 0; ol = oh = 0; }
     const uint8_t *p = in + lo;
     const uint64_t len = hi - lo;
@@ -1285,10 +1287,22 @@ __global__ void __launch_bounds__(256) batch_piece_fill_kernel(const BatchItemSt
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks,
                       uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st)
 {
+    return inflate_batch_run_ranges(e, d_in, in_bytes, d_in_off, d_in_off ? d_in_off + 1 : nullptr, n, wrap, checks, d_out, out_cap, d_out_off,
+                                    d_out_off ? d_out_off + 1 : nullptr, d_items, nfailed, nullptr, st);
+}
+
+// The same with every item's input end and output end given on their own (device tables of n entries each): items may overlap in the input.
+// *states (optional): the items' BatchItemState records in the engine's scratch, good until the next inflate call -- `used` and `out_bytes` of an
+// item whose range was too small (ZGPU_BUF_ERROR) are there.
+int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,
+                             uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_lo, const uint64_t *d_out_hi, zgpu_inflate_item *d_items, uint64_t *nfailed,
+                             const BatchItemState **states, hipStream_t st)
+{
     if (!e) return ZGPU_STREAM_ERROR;
     if (nfailed) *nfailed = 0;
-    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (checks & ~3u) || (n && (!d_in_off || !d_out_off || !d_items)) || (n && in_bytes && !d_in) || (n && out_cap && !d_out) ||
-        n >= (1ull << 32))
+    if (states) *states = nullptr;
+    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (checks & ~3u) || (n && (!d_in_lo || !d_in_hi || !d_out_lo || !d_out_hi || !d_items)) || (n && in_bytes && !d_in) ||
+        (n && out_cap && !d_out) || n >= (1ull << 32))
         return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
     if (n == 0) return ZGPU_OK;
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
@@ -1311,7 +1325,7 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
     ChunkMeta *meta = reinterpret_cast<ChunkMeta *>(scr + o_meta);
     ZGPU_HIP_CHECK(hipMemsetAsync(cnt, 0, 256, st));
     const uint32_t ngrid = (uint32_t)((n + 255) / 256);
-    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, n, (uint32_t)wrap, out_cap, d_out_off, seg, items,
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_lo, d_in_hi, n, (uint32_t)wrap, out_cap, d_out_lo, d_out_hi, seg, items,
                        reinterpret_cast<uint32_t *>(cnt + 2));
     int ring_kb = ZGPU_INF_RING_DEFAULT_KB; // (items go straight to their place: the small rings serve them as they serve chunks)
     if (const char *v = getenv("ZGPU_INF_RING_KB")) ring_kb = atoi(v);
@@ -1351,6 +1365,7 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     collect_spans(e);
     if (nfailed) *nfailed = h[1];
+    if (states) *states = items;
     return ZGPU_OK;
 }
 } // namespace zgpu

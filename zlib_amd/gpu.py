@@ -118,6 +118,10 @@ def load_library():
     L.zgpu_bgzf_index_device.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), vp]
     L.zgpu_bgzf_inflate_device.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(InflateResult), vp]
     L.zgpu_bgzf_inflate_host.argtypes = [vp, vp, u64, vp, u64, vp, C.POINTER(InflateResult)]
+    L.zgpu_gzip_inflate_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(InflateResult), vp]
+    L.zgpu_gzip_inflate_host.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(InflateResult)]
+    L.zgpu_gzip_members_count.argtypes = [C.c_int]
+    L.zgpu_gzip_members_count.restype = u64
     L.zgpu_inflate_find_chunks_host.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64)]
     L.zgpu_inflate_stream_host2.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(InflateResult)]
     L.zgpu_inflate_stream_host3.argtypes = [vp, vp, u64, u32, u32, vp, u64, C.POINTER(InflateResult)]
@@ -406,6 +410,44 @@ class Engine:
         res = DeflateResult()
         self._check(self.L.zgpu_bgzf_deflate_device(self.h, d_in, n, level, strategy, block_size, d_out, out_cap, d_offsets, C.byref(res), stream))
         return res
+
+    # ---- multi-member gzip ----
+    def gzip_inflate_host(self, data, out_cap=None, cap_members=None):
+        """A multi-member gzip file -> (rc, bytes, in_offsets, out_offsets, items): rc the call's code (0, -3 when a member failed, -5 when out_cap or
+        cap_members is too small), the tables of the good members (zgpu_gzip_inflate_host), bytes what was delivered.  self.last_inflate has out_bytes
+        (-5: the size needed), in_used and the first failing member; self.last_members the number of good members."""
+        import numpy as np
+        arr = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+        n = int(arr.size) - 1
+        cm = n // 20 if cap_members is None else cap_members  # (no member is shorter than 20 bytes)
+        items = (InflateItem * (cm + 1))()
+        ioffs = np.zeros(cm + 1, dtype=np.uint64)
+        ooffs = np.zeros(cm + 1, dtype=np.uint64)
+        res, nm = InflateResult(), C.c_uint64(0)
+        cap = out_cap
+        if cap is None:  # ask for the size first: a call with no room says what is needed
+            cap = 0
+            if self.L.zgpu_gzip_inflate_host(self.h, arr.ctypes.data, n, None, 0, None, None, None, 0, C.byref(nm), C.byref(res)) == -5:
+                cap = res.out_bytes
+        out = np.zeros(cap + 1, dtype=np.uint8)
+        rc = self.L.zgpu_gzip_inflate_host(self.h, arr.ctypes.data, n, out.ctypes.data, cap, ioffs.ctypes.data, ooffs.ctypes.data, items, cm, C.byref(nm), C.byref(res))
+        self.last_inflate, self.last_members = res, nm.value
+        if rc not in (0, -3, -5):
+            self._check(rc)
+        k = nm.value if rc in (0, -3) and nm.value <= cm else 0
+        return rc, out[: res.out_bytes].tobytes() if rc in (0, -3) else b"", [int(x) for x in ioffs[: k + 1]], [int(x) for x in ooffs[: k + 1]], items
+
+    def gzip_inflate_device(self, d_in, in_bytes, d_out, out_cap, d_in_offsets=None, d_out_offsets=None, d_items=None, cap_members=0, stream=None):
+        """Device pointers as ints; the offset tables hold cap_members + 1 uint64 each, d_items cap_members records.  Returns (rc, nmembers, InflateResult)."""
+        res, nm = InflateResult(), C.c_uint64(0)
+        rc = self.L.zgpu_gzip_inflate_device(self.h, d_in, in_bytes, d_out, out_cap, d_in_offsets, d_out_offsets, d_items, cap_members, C.byref(nm), C.byref(res), stream)
+        if rc not in (0, -3, -5):
+            self._check(rc)
+        return rc, nm.value, res
+
+    def gzip_members_count(self):
+        """(calls that decoded every member once, calls that needed the second decode) since the library was loaded"""
+        return int(self.L.zgpu_gzip_members_count(0)), int(self.L.zgpu_gzip_members_count(1))
 
     def deflate_device(self, d_in, n, level, d_out, out_cap, flags=F_FINAL | F_ZLIB_WRAP, chunk_size=CHUNK, lz_impl=LZ_AUTO,
                        d_offsets=None, stream=None):
