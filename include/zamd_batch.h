@@ -27,6 +27,24 @@ int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const
 int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits,
                           int *status);
 
+/* When the decoded sizes are not known (a zlib or raw-deflate stream carries none, a gzip ISIZE is a claim modulo 2^32).  windowBits as above.
+ *
+ * zamd_uncompress_sizes_batch: destLen[k] = the size item k decodes to (0 when it does not); status[k] Z_OK or Z_DATA_ERROR (damaged, truncated,
+ * in need of a dictionary).  Nothing is decoded into memory (zgpu_inflate_batch_sizes_host), and so the trailers are not checked: an item whose
+ * Adler-32, CRC-32 or ISIZE is wrong is Z_OK here and Z_DATA_ERROR when it is decoded.  Items of 512 MiB of input or more are sized one by one
+ * through inflate(), their output discarded (those do have their trailers checked).
+ *
+ * zamd_uncompress_batch_packed: all items into dest, back to back: item k is dest[destOffsets[k] .. destOffsets[k+1]), destOffsets has n + 1
+ * entries.  *destCap in: the room of dest; out: the bytes used, or needed.  status[k] as zamd_uncompress_batch gives it; an item that fails has an
+ * empty range.  Z_BUF_ERROR when the room is too small: destOffsets and *destCap are valid (call zamd_uncompress_batch or this again with that
+ * much room), status holds the sizing pass's verdicts and nothing is decoded.  One engine call (zgpu_inflate_batch_packed_host) when every item
+ * has less than 512 MiB of input; otherwise the large ones are sized and decoded one by one.
+ *
+ * Both: the return value is the first failing item's code; Z_STREAM_ERROR for bad arguments touches nothing; n == 0 is Z_OK and creates no engine. */
+int zamd_uncompress_sizes_batch(uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status);
+int zamd_uncompress_batch_packed(Bytef *dest, uLongf *destCap, uLong *destOffsets, const Bytef *const *source, const uLong *sourceLen, size_t n,
+                                 int windowBits, int *status);
+
 /* crc32() / adler32() of many buffers, all items in one engine call (zgpu_checksum_batch_host).  crc[k] / adler[k] hold the running value on
  * entry, as the first argument of crc32() / adler32() (0 / 1 for a fresh one), and crc32(crc[k], buf[k], len[k]) / adler32(...) on return: the
  * items' own checksums come from the device, the running values are folded in on the host with crc32_combine / adler32_combine.  Items of any

@@ -358,6 +358,33 @@ int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, c
                             uint32_t checks, void *out, uint64_t out_cap, const uint64_t *out_offsets, zgpu_inflate_item *items,
                             uint64_t *nfailed);
 
+/* ---- batch inflate without known sizes: the sizing pass and the packed decode ----
+ * A zlib or raw-deflate stream carries no decoded size, and a gzip ISIZE is a claim modulo 2^32.  The sizing pass reads every item the way the batch
+ * decoder reads it -- the same wrapper rules, the same deflate decoder -- and counts the bytes its symbols stand for instead of producing them: no
+ * destination is needed, none is touched.  Record k: code ZGPU_OK, ZGPU_DATA_ERROR or 2 (FDICT); msg the index zgpu_inflate_batch_* gives the same
+ * item; out_bytes the decoded size; in_used the end of the final block plus the wrapper's trailer length (an item that ends inside its trailer is
+ * "segment ends inside a block", as in the decoder); adler32 = 1, crc32 = 0.  A failed item has out_bytes = in_used = 0.
+ * What it cannot say: it computes no Adler-32 or CRC-32 and compares no ISIZE -- its verdict is the decoder's minus the trailer checks.  An item
+ * whose check value or length field is wrong is ZGPU_OK here and ZGPU_DATA_ERROR ("incorrect data check" / "incorrect length check") in a decode.
+ * Arguments, limits (< 512 MiB compressed, < 4 GiB decoded per item, no preset dictionary), ZGPU_STREAM_ERROR for offsets that run backwards or
+ * leave the buffer and *nfailed are zgpu_inflate_batch_*'s.  One read-back, at the end; the device entry blocks until the records are in d_items. */
+int zgpu_inflate_batch_sizes_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                                    zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream);
+int zgpu_inflate_batch_sizes_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,
+                                  zgpu_inflate_item *items, uint64_t *nfailed);
+/* The packed decode: the sizing pass, the layout made on the device, then zgpu_inflate_batch_* into that layout.  d_out_offsets (out, n + 1 entries):
+ * item k starts at the sizes in front of it, every start rounded up to `align` (a power of two from 1 to 256, else ZGPU_STREAM_ERROR);
+ * d_out_offsets[n] = *total = the end of the last item.  An item whose sizing failed has an empty range and keeps the sizing pass's record; the
+ * records of the others are the decoder's (adler32 / crc32 as `checks` asks, trailer mismatches reported as in zgpu_inflate_batch_*).
+ * *total > out_cap: ZGPU_BUF_ERROR -- *total and d_out_offsets are written, d_items holds the sizing records, nothing is decoded; allocate and call
+ * zgpu_inflate_batch_* with that table.  n == 0: ZGPU_OK, *total = 0.  The host entry writes only the bytes of the items that succeed. */
+int zgpu_inflate_batch_packed_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                                     uint32_t checks, uint32_t align, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                     zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, void *hip_stream);
+int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,
+                                   uint32_t checks, uint32_t align, void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_inflate_item *items,
+                                   uint64_t *total, uint64_t *nfailed);
+
 /* ---- BGZF decode (the encode side and the format: zgpu_bgzf_deflate_* above) ---- */
 /* The block index of a BGZF file in device memory, found on the device from the headers alone (zlib_amd/csrc/zgpu_bgzf.hip): d_in_offsets[0..n] =
  * where every block begins, entry n = in_bytes; d_out_offsets[0..n] = the exclusive sum of the blocks' ISIZE (entry n = *out_bytes).  Both arrays

@@ -98,6 +98,8 @@ struct zgpu_engine {
     // (one more), where the member ends; the candidates' records of the first decode (bz_items holds the members')
     DevBuf<uint64_t> gz_in_end, gz_trial, gz_next; DevBuf<uint32_t> gz_guess;
     DevBuf<zgpu_inflate_item> gz_items;
+    // packed batch decode (zgpu_inflate_batch_packed_*): where every item's range ends, the decoder's records until they are merged with the sizing pass's
+    DevBuf<uint64_t> pk_hi; DevBuf<zgpu_inflate_item> pk_items;
     // batch checksums (zgpu_checksum.hip): pieces in front of every item (n + 1), the bad-table flag, three words per piece (a, b, crc)
     DevBuf<uint64_t> ck_piece0; DevBuf<uint32_t> ck_flag, ck_part;
     // profiling
@@ -202,6 +204,11 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
 int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,
                              uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_lo, const uint64_t *d_out_hi, zgpu_inflate_item *d_items, uint64_t *nfailed,
                              const BatchItemState **states, hipStream_t st);
+int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, uint64_t *nfailed,
+                            hipStream_t st);
+int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, hipStream_t st,
+                             bool stage_out = false);
 
 // ---- zgpu_checksum.hip ----
 int checksum_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t n, uint32_t checks, zgpu_check_item *d_items, hipStream_t st);

@@ -45,6 +45,9 @@ constexpr uint32_t kLBits = 9, kDBits = 9, kStageDwords = 256;
 #ifndef ZGPU_INF_RING_DEFAULT_KB
 #define ZGPU_INF_RING_DEFAULT_KB 8 // the ring of chunks decoded straight into place (zgpu_inflate_device); ZGPU_INF_RING_KB at run time
 #endif
+#ifndef ZGPU_INF_SIZES_WAVES
+#define ZGPU_INF_SIZES_WAVES 6 // waves per SIMD the sizing pass is compiled for: its LDS lets 24 one-wave workgroups share a CU, six per SIMD (80 registers)
+#endif
 constexpr uint32_t kOutRing = ZGPU_INF_RING, kOutHalf = kOutRing / 2; // the last 32 KiB of output live in LDS (the farthest a distance reaches)
 
 // Decoding table entries of the literal/length and distance codes carry everything the symbol loop needs:
@@ -68,6 +71,20 @@ template <typename RingT, uint32_t kRing = kOutRing> struct InflateLdsT {
     uint32_t end_final, pad1;     // reader -> writer: the segment ended with a final block
 };
 using InflateLds = InflateLdsT<uint8_t>;
+// The sizing pass (inflate_kernel_t<..., SIZES>) keeps what the reader needs and nothing else: no output ring, and no token ring either, because the
+// one wave that decodes the tokens also counts them
+struct InflateLdsSizes {
+    uint32_t ltab[1 << kLBits];
+    uint32_t dtab[1 << kDBits];
+    uint32_t stage[kStageDwords];
+    uint32_t abort_flag, end_bits;
+    uint16_t lens[320];
+    uint16_t lsym[288], dsym[32];
+    uint16_t lcount[16], dcount[16];
+    uint16_t work_offs[16], work_first[16], work_start[16];
+    uint32_t build_rc, build_n;
+    uint32_t end_final, pad1;
+};
 using InflateLdsSpec = InflateLdsT<uint16_t>;
 constexpr uint32_t kScanBytes = 4096; // the block finder reads the input through LDS in pieces of this size (+ the 16 bytes a bit offset at the end reaches into)
 constexpr uint32_t kFindList = 1024; // candidates listed between two rounds of the second sieve (a group of 2048 offsets yields 683 at most: one in three)
@@ -76,6 +93,7 @@ static_assert(sizeof(InflateLdsFind) <= 14336, "eleven finder waves per CU");
 static_assert(sizeof(InflateLds) <= 40448, "four segments per CU");
 static_assert(10 * sizeof(InflateLdsT<uint8_t, 8192>) <= 160 * 1024, "ten segments per CU with the 8 KiB ring (five waves per SIMD: 96 registers)");
 static_assert(sizeof(InflateLdsSpec) <= 81920, "two workgroups per CU");
+static_assert(24 * sizeof(InflateLdsSizes) <= 160 * 1024, "the sizing pass: twenty-four one-wave workgroups per CU (six waves per SIMD)");
 
 // Wave-uniform bit reader over a ring of input dwords in LDS.
 struct BitSrc {
@@ -446,14 +464,23 @@ struct SpecArgs {
 // when their half of the token ring is handed over, all at once, and the copy takes them from registers when its turn comes.
 // BATCH (zgpu_inflate_batch_*): segment gc is one independent stream, offsets[4 gc ..] = {body start, input end, output start, output end}; it must
 // reach its final block, whatever follows is its trailer (stream_mode), and it goes straight to its own range of the destination with no dictionary.
-template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false>
-__global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_kernel_t(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ offsets,
+// SIZES (zgpu_inflate_batch_sizes_*, BATCH only): the sizing pass.  The decoded size of a deflate stream is a function of its symbols alone, so the workgroup is
+// the reader wave and nothing else: where the reader would hand tokens to the writer it takes their lengths itself (a prefix sum per hand-over) and applies
+// the limits that depend on the output position -- distance too far back, the 4 GiB item limit -- in the order the writer does.  There is no output ring, no
+// token ring, no barrier, no match copy and no access to the destination: `out`, the output half of the segment table and `dict` are never touched.
+// status[] is what the BATCH decoder writes for the same item into a range of exactly its size.  What this pass cannot say: it computes no Adler-32 or
+// CRC-32 and compares no ISIZE, so its verdict is the decoder's verdict minus the trailer checks.
+// Termination: SIZES adds no loop.  The block loop and the token loop are the reader's, and every iteration of either consumes input bits or ends with
+// an error (or with `stop`, which the counting sets together with its error); the counting itself is straight-line code.
+template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false>
+__global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES : (!SPEC && RING <= 8192) ? 5 : 4) inflate_kernel_t(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ offsets,
                                                         uint64_t chunk0, uint32_t nchunks, uint64_t last_chunk, uint32_t chunk_size_arg,
                                                         uint8_t *__restrict__ out, uint64_t out_cap, InfStatus *status, ChunkMeta *meta,
                                                         const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t stream_mode, SpecArgs sp)
 {
     typedef typename std::conditional<SPEC, uint16_t, uint8_t>::type ring_t;
-    typedef InflateLdsT<ring_t, RING> Lds;
+    typedef typename std::conditional<SIZES, InflateLdsSizes, InflateLdsT<ring_t, RING>>::type Lds;
+    static_assert(!SIZES || (BATCH && !SPEC), "the sizing pass serves batch items");
     constexpr uint32_t kOutRing = RING, kOutHalf = RING / 2; // (this kernel's ring, not the file's default)
     constexpr bool FAR = RING < 32768;
     static_assert(!(SPEC && FAR) && RING >= 4096 && (RING & (RING - 1)) == 0, "ring size");
@@ -504,6 +531,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
         uint32_t err = bad_table ? (uint32_t)kMsgTable : (uint32_t)kMsgNone;
         uint32_t wr = 0;   // tokens put into the ring so far
         bool stop = false; // the writer gave up (its error comes first in stream order)
+        uint32_t size_o = 0, size_err = kMsgNone; // SIZES: bytes the tokens so far stand for; the error of the first token that breaks a limit of the output position
         auto publish = [&]() { // the current half is complete: hand it over, the other half is free from here on
             INF_T(9);
             block_sync();
@@ -512,6 +540,15 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
         };
         // the marked lanes' token words, in lane order
         auto emit_tokens = [&](uint64_t marks, uint32_t word) {
+            if constexpr (SIZES) { // what the writer does with a run of tokens, minus the bytes (the marked lanes are in stream order)
+                const uint32_t k2 = sel_mask(marks, word & 3u, 0u), len = (word >> 2) & 511u, ol = k2 == 1 ? 1u : k2 == 2 ? len : 0u;
+                const uint32_t incl = wave_prefix_sum(ol), offv = size_o + incl - ol;
+                const bool far = k2 == 2 && (word >> 11) >= offv + reach, over = offv + ol > chunk_size; // (size_o <= 0xFFFF0000 and a run adds 64 * 258 at most: no wrap)
+                const uint64_t bad = __ballot(far || over);
+                if (stop) { } // (the second window of a step whose first one broke a limit: the first error stands, as the writer takes no token behind its error)
+                else if (bad) { size_err = ((__ballot(far) >> (uint32_t)__builtin_ctzll(bad)) & 1) ? kMsgTooFar : kMsgOutput; stop = true; }
+                else size_o += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            } else {
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(marks >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)marks, 0u));
             const uint32_t t = (uint32_t)__builtin_popcountll(marks), bound = (wr | 63u) + 1, at = wr + rank;
             const bool mine = sel_mask(marks, 1u, 0u) != 0;
@@ -521,9 +558,17 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
                 if (mine && at >= bound) L.tok[at & 127u] = word;
             }
             wr += t;
+            }
         };
         // n <= 3 words that must sit in one half (lane i holds word i); `final`: pad the half and hand it over
         auto emit_command = [&](uint32_t word, uint32_t n, bool final) {
+            if constexpr (SIZES) { // a stored block counts its bytes (lane 0 holds the command word); the end command has nobody to go to
+                if (!final) {
+                    const uint32_t slen = (uni(word) >> 4) & 0x1FFFFu;
+                    if (size_o + slen > chunk_size) { size_err = kMsgOutput; stop = true; }
+                    else size_o += slen;
+                }
+            } else {
             if ((wr & 63u) + n > 64u) { // no room: pad this half with nothing-tokens
                 const uint32_t bound = (wr | 63u) + 1;
                 if (wr + lane < bound) L.tok[(wr + lane) & 127u] = 0u;
@@ -538,6 +583,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
                 wr = bound;
                 publish();
             } else if ((wr & 63u) == 0) publish();
+            }
         };
         BitSrc b;
         const uint64_t in_addr = reinterpret_cast<uint64_t>(in);
@@ -744,6 +790,15 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
         if (err && lane == 0) printf("chunk %u reader err %u consumed %u seg_bits %u rd %u filled %u bits %u\n", c, err, consumed_bits(b), b.seg_bits, b.rd, b.filled, b.bits);
 #endif
         emit_command(3u | (kCmdEnd << 2) | (err << 4), 1, true);
+        if constexpr (SIZES) { // the record the writer ends with: an error of the counting lies in front of whatever the reader found behind it
+            if (size_err) err = size_err;
+            wave_sync(); // (lane 0's end_bits / end_final)
+            if (lane == 0) {
+                status[c].code = err ? ZGPU_DATA_ERROR : ZGPU_OK;
+                status[c].msg = err ? err : ((L.end_bits & 7u) << 24); status[c].out_bytes = err ? 0 : size_o;
+                status[c].used = err ? 0u : (((L.end_bits + 7u) >> 3) | (L.end_final << 31));
+            }
+        }
 #ifdef ZGPU_INF_TIME
         if (lane == 0) { t_acc[5] = n_lit; t_acc[7] = n_slow; for (int i_ = 0; i_ < 16; i_++) if (t_acc[i_]) atomicAdd(&inf_time[i_], t_acc[i_]); }
 #endif
@@ -751,6 +806,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
     }
 
     // =========================================== writer ===========================================
+    if constexpr (!SIZES) {
     uint32_t err = kMsgNone;
     uint32_t o = 0;       // bytes produced
     if (SPEC) {
@@ -983,6 +1039,7 @@ __global__ void __launch_bounds__(128, (!SPEC && RING <= 8192) ? 5 : 4) inflate_
 #endif
         if (meta) { meta[c].out_bytes = err ? 0 : o; meta[c].ntok = 0; meta[c].adler_a = 1; meta[c].adler_b = 0; meta[c].in_bytes = 0; meta[c].data_type = 2; }
     }
+    } // !SIZES
 }
 
 // first failing chunk + total bytes (one workgroup; chunk order matters for "first")
@@ -1366,6 +1423,166 @@ int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     collect_spans(e);
     if (nfailed) *nfailed = h[1];
     if (states) *states = items;
+    return ZGPU_OK;
+}
+
+// ---- sizing pass and packed decode (zgpu_inflate_batch_sizes_* / zgpu_inflate_batch_packed_*) ----
+// the record of a sizes call: the header's verdict, behind it the sizing kernel's, behind that the one thing batch_finish_kernel says without having
+// seen the decoded bytes -- an item whose trailer does not fit behind its final block is truncated
+__global__ void __launch_bounds__(256) batch_sizes_finish_kernel(const BatchItemState *__restrict__ items, const InfStatus *__restrict__ status, uint64_t n,
+                                                                 zgpu_inflate_item *out, unsigned long long *nfailed)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const BatchItemState s = items[k];
+    zgpu_inflate_item r{};
+    r.code = s.code; r.msg = s.msg; r.adler32 = 1; r.crc32 = 0;
+    if (s.code == ZGPU_OK) {
+        const InfStatus t = status[k];
+        r.code = t.code; r.msg = t.code == ZGPU_DATA_ERROR ? t.msg : 0u;
+        if (t.code == ZGPU_OK) {
+            const uint64_t end = s.body_lo + (t.used & 0x7fffffffu), tl = s.kind == kWrapZlib ? 4 : s.kind == kWrapGzip ? 8 : 0;
+            if (end + tl > s.in_hi) { r.code = ZGPU_DATA_ERROR; r.msg = kMsgTruncated; }
+            else { r.out_bytes = t.out_bytes; r.in_used = end + tl - s.in_lo; }
+        }
+    }
+    out[k] = r;
+    if (r.code != ZGPU_OK) atomicAdd(nfailed, 1ull);
+}
+
+// one workgroup (the pattern of batch_piece_scan_kernel): lo[k] = the sizes in front of item k, each start rounded up to `align` (a power of two; starts
+// that are all multiples of it: an exclusive scan of the rounded sizes), hi[k] = lo[k] + size[k], lo[n] = total[0] = the end of the last item.  An item
+// whose sizing failed has size 0.
+__global__ void __launch_bounds__(1024) batch_layout_kernel(const zgpu_inflate_item *__restrict__ items, uint64_t n, uint64_t align, uint64_t *lo, uint64_t *hi,
+                                                            unsigned long long *total)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (n + 1023) / 1024, a = tid * per < n ? tid * per : n, z = (tid + 1) * per < n ? (tid + 1) * per : n;
+    auto size_of = [&](uint64_t i) { return items[i].code == ZGPU_OK ? items[i].out_bytes : 0ull; };
+    unsigned long long sum = 0;
+    for (uint64_t i = a; i < z; i++) sum += (size_of(i) + align - 1) & ~(align - 1);
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const unsigned long long add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    unsigned long long o = part[tid] - sum;
+    for (uint64_t i = a; i < z; i++) {
+        const uint64_t sz = size_of(i);
+        lo[i] = o; hi[i] = o + sz;
+        if (i + 1 == n) { lo[n] = o + sz; total[0] = o + sz; }
+        o += (sz + align - 1) & ~(align - 1);
+    }
+}
+
+// behind the decode of a packed call: an item that was sized takes the decoder's record, one whose sizing failed keeps the sizing pass's
+__global__ void __launch_bounds__(256) batch_packed_merge_kernel(const zgpu_inflate_item *__restrict__ decoded, uint64_t n, zgpu_inflate_item *items, unsigned long long *nfailed)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    if (items[k].code == ZGPU_OK) items[k] = decoded[k];
+    if (items[k].code != ZGPU_OK) atomicAdd(nfailed, 1ull);
+}
+
+// The sizing pass over items in[d_in_off[k], d_in_off[k + 1]): records into d_items.  The counters stay in the engine's scratch (*cnt_out: [1] failed
+// items, [2] bad offsets) and nothing is read back here: the caller's one read-back fetches them.
+static int inflate_batch_sizes_launch(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items,
+                                      unsigned long long **cnt_out, hipStream_t st)
+{
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_seg = 0, o_items = o_seg + al(n * 32), o_status = o_items + al(n * sizeof(BatchItemState)), o_cnt = o_status + al(n * sizeof(InfStatus)), total = o_cnt + 256;
+    if (e->inf_status.reserve(e, total)) return ZGPU_MEM_ERROR;
+    uint8_t *scr = e->inf_status;
+    uint64_t *seg = reinterpret_cast<uint64_t *>(scr + o_seg);
+    BatchItemState *items = reinterpret_cast<BatchItemState *>(scr + o_items);
+    InfStatus *status = reinterpret_cast<InfStatus *>(scr + o_status);
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(scr + o_cnt);
+    ZGPU_HIP_CHECK(hipMemsetAsync(cnt, 0, 256, st));
+    const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    // (there is no destination: the header kernel is given the input tables a second time in its place, so that its range check passes what the first passes)
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, d_in_off + 1, n, (uint32_t)wrap, in_bytes, d_in_off, d_in_off + 1, seg, items,
+                       reinterpret_cast<uint32_t *>(cnt + 2));
+    hipEvent_t ev{};
+    prof_span_begin(e, st, &ev);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        hipLaunchKernelGGL((inflate_kernel_t<false, ZGPU_INF_RING, true, true>), dim3(nb), dim3(64), sizeof(InflateLdsSizes), st, d_in, in_bytes, seg, c0, nb, ~0ull,
+                           kWholeStream, nullptr, 0ull, status + c0, nullptr, nullptr, 0u, 1u, SpecArgs{});
+    }
+    prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+    hipLaunchKernelGGL(batch_sizes_finish_kernel, dim3(ngrid), dim3(256), 0, st, items, status, n, d_items, cnt + 1);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    *cnt_out = cnt;
+    return ZGPU_OK;
+}
+
+static int batch_sizes_args(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, const void *d_items)
+{
+    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (n && (!d_in_off || !d_items)) || (n && in_bytes && !d_in) || n >= (1ull << 32))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    return ZGPU_OK;
+}
+
+int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, uint64_t *nfailed,
+                            hipStream_t st)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (int rc = batch_sizes_args(e, d_in, in_bytes, d_in_off, n, wrap, d_items)) return rc;
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    unsigned long long *cnt = nullptr, h[3] = {0, 0, 0};
+    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &cnt, st)) return rc;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    collect_spans(e);
+    if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    if (nfailed) *nfailed = h[1];
+    return ZGPU_OK;
+}
+
+// sizing pass, layout, decode.  ZGPU_BUF_ERROR (*total > out_cap): d_out_offsets, *total and the sizing records stand, nothing is decoded.
+// stage_out (the host entry): the destination is the engine's output staging buffer, made large enough once the total is known -- d_out is not used
+int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, hipStream_t st, bool stage_out)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (align == 0 || align > 256 || (align & (align - 1)) || (checks & ~3u) || !total || (n && !d_out_off) || (n && out_cap && !d_out && !stage_out))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_sizes_args(e, d_in, in_bytes, d_in_off, n, wrap, d_items)) return rc;
+    *total = 0;
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    if (e->pk_hi.reserve(e, n + 1) || e->pk_items.reserve(e, n)) return ZGPU_MEM_ERROR;
+    unsigned long long *cnt = nullptr, h[3] = {0, 0, 0};
+    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &cnt, st)) return rc;
+    hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(1024), 0, st, d_items, n, (uint64_t)align, d_out_off, e->pk_hi.p, cnt);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    collect_spans(e);
+    if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    *total = h[0];
+    if (nfailed) *nfailed = h[1];
+    if (h[0] > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    if (stage_out) {
+        if (int rc = ensure_stage(e, 0, h[0])) return rc;
+        d_out = e->stage_out; out_cap = h[0];
+    }
+    // (the decode takes the engine's scratch over: the layout lives in the caller's table and pk_hi, the decoder's records go to pk_items)
+    if (int rc = inflate_batch_run_ranges(e, d_in, in_bytes, d_in_off, d_in_off + 1, n, wrap, checks, d_out, out_cap, d_out_off, e->pk_hi.p, e->pk_items.p, nullptr, nullptr, st)) return rc;
+    unsigned long long *fin = reinterpret_cast<unsigned long long *>(e->pk_hi.p + n);
+    ZGPU_HIP_CHECK(hipMemsetAsync(fin, 0, sizeof *fin, st));
+    hipLaunchKernelGGL(batch_packed_merge_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, e->pk_items.p, n, d_items, fin);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, fin, sizeof h[0], hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    if (nfailed) *nfailed = h[0];
     return ZGPU_OK;
 }
 } // namespace zgpu
@@ -2202,6 +2419,92 @@ int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, c
     if (hi > lo) ZGPU_HIP_CHECK(hipMemcpy(tmp.data(), sout + lo, hi - lo, hipMemcpyDeviceToHost));
     for (uint64_t k = 0; k < n; k++)
         if (items[k].code == ZGPU_OK && items[k].out_bytes) memcpy(o + out_offsets[k], tmp.data() + (out_offsets[k] - lo), items[k].out_bytes);
+    return ZGPU_OK;
+}
+
+__attribute__((visibility("default")))
+int zgpu_inflate_batch_sizes_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, zgpu_inflate_item *d_items,
+                                    uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_batch_sizes_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, d_items, nfailed, st);
+}
+
+__attribute__((visibility("default")))
+int zgpu_inflate_batch_packed_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                                     void *d_out, uint64_t out_cap, uint64_t *d_out_offsets, zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_batch_packed_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, checks, align, static_cast<uint8_t *>(d_out), out_cap, d_out_offsets,
+                                    d_items, total, nfailed, st, false);
+}
+
+// host arrays: the input and its offsets table staged in the engine's input buffer, the records (and a packed call's offsets table) behind them
+static int batch_stage_input(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, uint64_t out_bytes, uint64_t **d_in_off, uint64_t **d_out_off,
+                             zgpu_inflate_item **d_items)
+{
+    for (uint64_t k = 0; k < n; k++)
+        if (in_offsets[k] > in_offsets[k + 1] || in_offsets[k + 1] > in_bytes) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    const uint64_t tab_bytes = (n + 1) * sizeof(uint64_t), tab_room = (tab_bytes + 255) & ~255ull, o_tab = (in_bytes + 255) & ~255ull, o_items = o_tab + 2 * tab_room;
+    if (int rc = ensure_stage(e, o_items + n * sizeof(zgpu_inflate_item), out_bytes)) return rc;
+    uint8_t *sin = e->stage_in;
+    *d_in_off = reinterpret_cast<uint64_t *>(sin + o_tab); *d_out_off = reinterpret_cast<uint64_t *>(sin + o_tab + tab_room);
+    *d_items = reinterpret_cast<zgpu_inflate_item *>(sin + o_items);
+    if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(sin, in, in_bytes, hipMemcpyHostToDevice, e->stream));
+    ZGPU_HIP_CHECK(hipMemcpyAsync(*d_in_off, in_offsets, tab_bytes, hipMemcpyHostToDevice, e->stream));
+    return ZGPU_OK;
+}
+
+__attribute__((visibility("default")))
+int zgpu_inflate_batch_sizes_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, zgpu_inflate_item *items, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (int rc = batch_sizes_args(e, in, in_bytes, in_offsets, n, wrap, items)) return rc;
+    if (n == 0) return ZGPU_OK;
+    uint64_t *d_in_off, *d_out_off;
+    zgpu_inflate_item *d_items;
+    if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, 0, &d_in_off, &d_out_off, &d_items)) return rc;
+    if (int rc = inflate_batch_sizes_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, d_items, nfailed, e->stream)) return rc;
+    ZGPU_HIP_CHECK(hipMemcpy(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost));
+    return ZGPU_OK;
+}
+
+__attribute__((visibility("default")))
+int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                                   void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_inflate_item *items, uint64_t *total, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (align == 0 || align > 256 || (align & (align - 1)) || (checks & ~3u) || !total || (n && !out_offsets) || (n && out_cap && !out))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_sizes_args(e, in, in_bytes, in_offsets, n, wrap, items)) return rc;
+    *total = 0;
+    if (n == 0) return ZGPU_OK;
+    uint64_t *d_in_off, *d_out_off;
+    zgpu_inflate_item *d_items;
+    if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, 0, &d_in_off, &d_out_off, &d_items)) return rc;
+    const int rc = inflate_batch_packed_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, checks, align, nullptr, out_cap, d_out_off, d_items, total, nfailed, e->stream, true);
+    if (rc != ZGPU_OK && rc != ZGPU_BUF_ERROR) return rc;
+    ZGPU_HIP_CHECK(hipMemcpy(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost));
+    ZGPU_HIP_CHECK(hipMemcpy(out_offsets, d_out_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rc == ZGPU_BUF_ERROR) return rc;
+    // only the bytes of the items that succeeded go to the caller (the others' ranges are empty; the gaps of an alignment stay as the caller left them)
+    const uint64_t hi = *total;
+    bool dense = align == 1;
+    for (uint64_t k = 0; k < n && dense; k++) dense = items[k].code == ZGPU_OK;
+    uint8_t *o = static_cast<uint8_t *>(out);
+    if (dense) {
+        if (hi) ZGPU_HIP_CHECK(hipMemcpy(o, e->stage_out, hi, hipMemcpyDeviceToHost));
+        return ZGPU_OK;
+    }
+    std::vector<uint8_t> tmp(hi);
+    if (hi) ZGPU_HIP_CHECK(hipMemcpy(tmp.data(), e->stage_out, hi, hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < n; k++)
+        if (items[k].code == ZGPU_OK && items[k].out_bytes) memcpy(o + out_offsets[k], tmp.data() + out_offsets[k], items[k].out_bytes);
     return ZGPU_OK;
 }
 }

@@ -13,6 +13,7 @@ LZ_AUTO, LZ_SERIAL, LZ_PARALLEL, LZ_SORTED, LZ_WALK, LZ_FAST, LZ_FASTWIN = 0, 1,
 CHECK_ADLER32, CHECK_CRC32 = 1, 2  # zgpu_inflate_set_checks
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP, WRAP_AUTO = 0, 1, 2, 3  # zgpu_inflate_batch_*
 _WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP, "auto": WRAP_AUTO}
+BUF_ERROR = -5  # ZGPU_BUF_ERROR: what a packed batch decode answers when its output is too small
 STAGES = ["chain", "match", "parse", "lz_serial", "huffman", "stitch", "inflate"]
 CHUNK = 65536
 
@@ -111,6 +112,10 @@ def load_library():
     L.zgpu_deflate_segments_bound.restype = u64
     L.zgpu_inflate_batch_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.zgpu_inflate_batch_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, C.POINTER(u64)]
+    L.zgpu_inflate_batch_sizes_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, vp, C.POINTER(u64), vp]
+    L.zgpu_inflate_batch_sizes_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, vp, C.POINTER(u64)]
+    L.zgpu_inflate_batch_packed_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, u32, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
+    L.zgpu_inflate_batch_packed_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, u32, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.zgpu_bgzf_bound.argtypes = [u64, u32]
     L.zgpu_bgzf_bound.restype = u64
     L.zgpu_bgzf_deflate_device.argtypes = [vp, vp, u64, C.c_int, C.c_int, u32, vp, u64, vp, C.POINTER(DeflateResult), vp]
@@ -353,6 +358,69 @@ class Engine:
         self._check(self.L.zgpu_inflate_batch_device(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks,
                                                      d_out, out_cap, d_out_offsets, d_items, C.byref(failed), stream))
         return failed.value
+
+    # ---- batch inflate without known sizes ----
+    @staticmethod
+    def _pack_streams(streams):
+        import numpy as np
+        ioffs = np.zeros(len(streams) + 1, dtype=np.uint64)
+        ioffs[1:] = np.cumsum([len(s) for s in streams])
+        return np.frombuffer(b"".join(bytes(s) for s in streams) + b"\0", dtype=np.uint8), ioffs
+
+    def inflate_batch_sizes_host(self, streams, wrap="zlib"):
+        """The sizing pass (zgpu_inflate_batch_sizes_host): what every item decodes to, nothing decoded into memory and no trailer checked.
+        Returns one (code, msg, out_bytes, in_used) per item."""
+        n = len(streams)
+        blob, ioffs = self._pack_streams(streams)
+        items = (InflateItem * max(n, 1))()
+        failed = C.c_uint64(0)
+        self._check(self.L.zgpu_inflate_batch_sizes_host(self.h, blob.ctypes.data, int(ioffs[-1]), ioffs.ctypes.data, n, _WRAPS[wrap], items, C.byref(failed)))
+        self.last_failed = failed.value
+        return [(items[k].code, self.L.zgpu_inflate_message(items[k].msg).decode(), items[k].out_bytes, items[k].in_used) for k in range(n)]
+
+    def inflate_batch_packed_host(self, streams, wrap="zlib", checks=0, align=1):
+        """Sizing pass, layout and decode in one call (zgpu_inflate_batch_packed_host); the output buffer is made here, as large as the items need
+        (a second call once the first has said how much that is).  Returns (list of bytes, records): records as inflate_batch_host gives them without
+        the data; self.last_offsets holds the n + 1 offsets of the layout."""
+        import numpy as np
+        n = len(streams)
+        blob, ioffs = self._pack_streams(streams)
+        items = (InflateItem * max(n, 1))()
+        ooffs = np.zeros(n + 1, dtype=np.uint64)
+        failed, total = C.c_uint64(0), C.c_uint64(0)
+        cap = 4 * int(ioffs[-1]) + 4096
+        for _ in range(2):
+            out = np.zeros(cap + 1, dtype=np.uint8)
+            rc = self.L.zgpu_inflate_batch_packed_host(self.h, blob.ctypes.data, int(ioffs[-1]), ioffs.ctypes.data, n, _WRAPS[wrap], checks, align,
+                                                       out.ctypes.data, cap, ooffs.ctypes.data, items, C.byref(total), C.byref(failed))
+            if rc != BUF_ERROR:
+                break
+            cap = total.value
+        self._check(rc)
+        self.last_failed, self.last_offsets = failed.value, [int(o) for o in ooffs]
+        datas, recs = [], []
+        for k in range(n):
+            it = items[k]
+            datas.append(out[int(ooffs[k]): int(ooffs[k]) + it.out_bytes].tobytes() if it.code == 0 else b"")
+            recs.append((it.code, self.L.zgpu_inflate_message(it.msg).decode(), it.out_bytes, it.in_used, it.adler32, it.crc32))
+        return datas, recs
+
+    def inflate_batch_sizes_device(self, d_in, in_bytes, d_in_offsets, n, d_items, wrap="zlib", stream=None):
+        """Device pointers as ints, as inflate_batch_device takes them.  Blocks until the records are written; returns the number of items that failed."""
+        failed = C.c_uint64(0)
+        self._check(self.L.zgpu_inflate_batch_sizes_device(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, d_items,
+                                                           C.byref(failed), stream))
+        return failed.value
+
+    def inflate_batch_packed_device(self, d_in, in_bytes, d_in_offsets, n, d_out, out_cap, d_out_offsets, d_items, wrap="zlib", checks=0, align=1, stream=None):
+        """d_out_offsets receives n + 1 uint64.  Returns (code, total, failed): code is 0, or BUF_ERROR when total > out_cap (the offsets and the sizing
+        records are written, nothing is decoded)."""
+        failed, total = C.c_uint64(0), C.c_uint64(0)
+        rc = self.L.zgpu_inflate_batch_packed_device(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks, align,
+                                                     d_out, out_cap, d_out_offsets, d_items, C.byref(total), C.byref(failed), stream)
+        if rc != BUF_ERROR:
+            self._check(rc)
+        return rc, total.value, failed.value
 
     # ---- BGZF (blocked gzip) ----
     def bgzf_deflate_host(self, data, level=6, block_size=0, strategy=0, want_offsets=False):

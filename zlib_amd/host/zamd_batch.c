@@ -191,6 +191,178 @@ EXPORT int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Byte
     return first_failure(status, n);
 }
 
+static int window_wrap(int windowBits)
+{
+    return windowBits == 15 ? ZGPU_WRAP_ZLIB : windowBits == 31 ? ZGPU_WRAP_GZIP : windowBits == 47 ? ZGPU_WRAP_AUTO : windowBits == -15 ? ZGPU_WRAP_RAW : -1;
+}
+
+/* the decoded size of one item through inflate(), the output discarded piece by piece (items too large for the engine's batch).  Every round of
+ * the loop takes input in, delivers output or ends it: a round that does neither is the stream having stopped short. */
+static int size_one(uLongf *size, const Bytef *src, uLong len, int wbits)
+{
+    enum { ROOM = 1 << 20 };
+    z_stream st;
+    memset(&st, 0, sizeof st);
+    int err = inflateInit2_(&st, wbits, ZLIB_VERSION, (int)sizeof st);
+    if (err != Z_OK) return err;
+    Bytef *room = malloc(ROOM);
+    if (!room) { inflateEnd(&st); return Z_MEM_ERROR; }
+    st.next_in = (Bytef *)src;
+    uLong left = len, total = 0;
+    for (;;) {
+        uInt fed = 0;
+        if (st.avail_in == 0 && left) { fed = left > 0x40000000ul ? 0x40000000u : (uInt)left; st.avail_in = fed; left -= fed; }
+        st.next_out = room; st.avail_out = ROOM;
+        err = inflate(&st, left ? Z_NO_FLUSH : Z_FINISH);
+        const uInt got = ROOM - st.avail_out;
+        total += got;
+        if (err == Z_OK || (err == Z_BUF_ERROR && (got || fed))) continue;
+        break;
+    }
+    free(room);
+    inflateEnd(&st);
+    if (err != Z_STREAM_END) return err == Z_MEM_ERROR ? Z_MEM_ERROR : Z_DATA_ERROR; /* damaged, stopped short, or in need of a dictionary */
+    *size = total;
+    return Z_OK;
+}
+
+/* the items the engine's batch takes (less than 512 MiB of input), packed into one buffer: in, ioff[0..nb], idx[j] = the item's index in the call */
+struct packed_in { uint8_t *in; uint64_t *ioff; size_t *idx; zgpu_inflate_item *items; uint64_t nb, in_total; };
+static void packed_in_free(struct packed_in *p) { free(p->in); free(p->ioff); free(p->idx); free(p->items); }
+static int packed_in_make(struct packed_in *p, const Bytef *const *source, const uLong *sourceLen, size_t n)
+{
+    memset(p, 0, sizeof *p);
+    for (size_t k = 0; k < n; k++)
+        if (sourceLen[k] < BATCH_IN_MAX) { p->nb++; p->in_total += sourceLen[k]; }
+    if (!p->nb) return ZGPU_OK;
+    p->in = malloc(p->in_total + 1); p->ioff = malloc((p->nb + 1) * sizeof *p->ioff); p->idx = malloc(p->nb * sizeof *p->idx); p->items = malloc(p->nb * sizeof *p->items);
+    if (!p->in || !p->ioff || !p->idx || !p->items) return ZGPU_MEM_ERROR;
+    uint64_t j = 0, at = 0;
+    for (size_t k = 0; k < n; k++)
+        if (sourceLen[k] < BATCH_IN_MAX) {
+            p->ioff[j] = at; p->idx[j++] = k;
+            if (sourceLen[k]) memcpy(p->in + at, source[k], sourceLen[k]);
+            at += sourceLen[k];
+        }
+    p->ioff[p->nb] = at;
+    return ZGPU_OK;
+}
+
+/* sizes of all items: the engine's sizing pass for those it takes, size_one for the others.  size[k] = 0 where status[k] is not Z_OK */
+static void sizes_all(struct packed_in *p, int rc, uLongf *size, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status)
+{
+    if (p->nb && rc == ZGPU_OK) {
+        zgpu_engine *e = zamd_batch_engine_lock();
+        if (!e) rc = ZGPU_ERRNO;
+        else {
+            rc = zgpu_inflate_batch_sizes_host(e, p->in, p->in_total, p->ioff, p->nb, window_wrap(windowBits), p->items, NULL);
+            zamd_batch_engine_unlock();
+        }
+    }
+    for (uint64_t i = 0; i < p->nb; i++) {
+        const size_t k = p->idx[i];
+        if (rc != ZGPU_OK) status[k] = rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : engine_code(rc);
+        else status[k] = p->items[i].code == ZGPU_OK ? Z_OK : Z_DATA_ERROR;
+        size[k] = status[k] == Z_OK ? (uLongf)p->items[i].out_bytes : 0;
+    }
+    for (size_t k = 0; k < n; k++)
+        if (sourceLen[k] >= BATCH_IN_MAX) {
+            size[k] = 0;
+            status[k] = size_one(&size[k], source[k], sourceLen[k], windowBits);
+        }
+}
+
+EXPORT int zamd_uncompress_sizes_batch(uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status)
+{
+    if (n && (!destLen || !source || !sourceLen || !status)) return Z_STREAM_ERROR;
+    if (window_wrap(windowBits) < 0) return Z_STREAM_ERROR;
+    for (size_t k = 0; k < n; k++)
+        if (!source[k] && sourceLen[k]) return Z_STREAM_ERROR;
+    if (n == 0) return Z_OK;
+    struct packed_in p;
+    const int rc = packed_in_make(&p, source, sourceLen, n);
+    sizes_all(&p, rc, destLen, source, sourceLen, n, windowBits, status);
+    packed_in_free(&p);
+    return first_failure(status, n);
+}
+
+EXPORT int zamd_uncompress_batch_packed(Bytef *dest, uLongf *destCap, uLong *destOffsets, const Bytef *const *source, const uLong *sourceLen, size_t n,
+                                        int windowBits, int *status)
+{
+    if (!destCap || (n && (!destOffsets || !source || !sourceLen || !status)) || (n && !dest && *destCap)) return Z_STREAM_ERROR;
+    const int wrap = window_wrap(windowBits);
+    if (wrap < 0) return Z_STREAM_ERROR;
+    for (size_t k = 0; k < n; k++)
+        if (!source[k] && sourceLen[k]) return Z_STREAM_ERROR;
+    if (n == 0) { *destCap = 0; return Z_OK; }
+    struct packed_in p;
+    int rc = packed_in_make(&p, source, sourceLen, n);
+    int ret;
+    if (rc == ZGPU_OK && p.nb == n) {
+        /* the usual case, every item in the engine's reach: sizing pass, layout and decode in one engine call, one upload (idx is the identity) */
+        uint64_t *ooff = malloc((n + 1) * sizeof *ooff), total = 0;
+        zgpu_engine *e = ooff ? zamd_batch_engine_lock() : NULL;
+        if (!ooff) rc = ZGPU_MEM_ERROR;
+        else if (!e) rc = ZGPU_ERRNO;
+        else {
+            rc = zgpu_inflate_batch_packed_host(e, p.in, p.in_total, p.ioff, n, wrap, 0, 1, dest, *destCap, ooff, p.items, &total, NULL);
+            zamd_batch_engine_unlock();
+        }
+        if (rc == ZGPU_OK || rc == ZGPU_BUF_ERROR) {
+            for (size_t k = 0; k < n; k++) { destOffsets[k] = (uLong)ooff[k]; status[k] = p.items[k].code == ZGPU_OK ? Z_OK : Z_DATA_ERROR; }
+            destOffsets[n] = (uLong)ooff[n];
+            *destCap = (uLongf)total;
+            ret = rc == ZGPU_BUF_ERROR ? Z_BUF_ERROR : first_failure(status, n);
+        } else {
+            for (size_t k = 0; k < n; k++) status[k] = rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : engine_code(rc);
+            ret = status[0];
+        }
+        free(ooff);
+        packed_in_free(&p);
+        return ret;
+    }
+    /* items the batch does not take among them: sizes first, then the layout, then the batch decode of the small ones into their places and the
+     * large ones one by one */
+    uLongf *size = malloc(n * sizeof *size);
+    uint64_t *ooff = malloc((p.nb + 1) * sizeof *ooff);
+    if (!size || !ooff) rc = ZGPU_MEM_ERROR;
+    if (rc != ZGPU_OK) {
+        for (size_t k = 0; k < n; k++) status[k] = Z_MEM_ERROR;
+        free(size); free(ooff); packed_in_free(&p);
+        return Z_MEM_ERROR;
+    }
+    sizes_all(&p, rc, size, source, sourceLen, n, windowBits, status);
+    uint64_t total = 0;
+    for (size_t k = 0; k < n; k++) { destOffsets[k] = (uLong)total; total += size[k]; }
+    destOffsets[n] = (uLong)total;
+    const int too_small = total > *destCap;
+    *destCap = (uLongf)total;
+    if (!too_small) {
+        for (uint64_t i = 0; i < p.nb; i++) ooff[i] = destOffsets[p.idx[i]];
+        ooff[p.nb] = total;
+        if (p.nb) {
+            zgpu_engine *e = zamd_batch_engine_lock();
+            if (!e) rc = ZGPU_ERRNO;
+            else {
+                rc = zgpu_inflate_batch_host(e, p.in, p.in_total, p.ioff, p.nb, wrap, 0, dest, total, ooff, p.items, NULL);
+                zamd_batch_engine_unlock();
+            }
+            for (uint64_t i = 0; i < p.nb; i++) {
+                const size_t k = p.idx[i];
+                if (status[k] != Z_OK) continue; /* (its range is empty: the sizing pass's verdict stands) */
+                status[k] = rc != ZGPU_OK ? engine_code(rc) : p.items[i].code == ZGPU_OK ? Z_OK : Z_DATA_ERROR;
+            }
+        }
+        for (size_t k = 0; k < n; k++)
+            if (sourceLen[k] >= BATCH_IN_MAX && status[k] == Z_OK) {
+                uLongf len = size[k];
+                status[k] = uncompress_one(dest + destOffsets[k], &len, source[k], sourceLen[k], windowBits);
+            }
+    }
+    free(size); free(ooff); packed_in_free(&p);
+    return too_small ? Z_BUF_ERROR : first_failure(status, n);
+}
+
 /* crc32() / adler32() of many buffers: the items' own checksums from one zgpu_checksum_batch_host, the caller's running values folded in here */
 static int checksum_batch(uLong *val, const Bytef *const *buf, const uLong *len, size_t n, int want_crc)
 {
