@@ -111,5 +111,12 @@ template <bool FUSED> __device__ inline uint32_t p2_ld(const uint32_t *p) { retu
 constexpr uint32_t kP2OffJ = 0, kP2OffHAS = kP2Win * 2, kP2OffMARK = kP2OffHAS + kP2Words * 4, kP2OffCOV = kP2OffMARK + kP2Words * 4, kP2OffMAT = kP2OffCOV + kP2Words * 4,
                    kP2OffWbase = kP2OffMAT + kP2Words * 4, kP2OffVIS = kP2OffWbase + (kP2Words + 4) * 4, kP2OffEXITS = kP2OffVIS + kP2Win / 32 * 4, kP2OffWtot = kP2OffEXITS + 256,
                    kP2OffEntry = kP2OffWtot + 64, kP2LdsBytes = kP2OffEntry + 16;
+// LOG (walk_kernel<1> only): the games arrive as one log per window of kP2Win positions instead of gm / gs -- entry s of window w is the pair
+// lpos[w * kP2Win + s] (the game's start, a position of the chunk) and lrec[w * kP2Win + s] (the word gm holds), in the order the walkers finished
+// them; the entries of a window are counted in LDS (lcnt[w]).  A neutral position is claimed by one walker and starts at most one game, so kP2Win
+// entries hold every game of a window.  The tail then looks at games, not at positions, wherever games are all it needs, and keeps the end of
+// each game of the window in END (u16, window-relative; at most kP2Win - 1 + 255 + 258), which lies behind the parse's other arrays.
+constexpr uint32_t kP2Wins = kChunkMax / kP2Win, kP2OffEND = kP2LdsBytes, kP2LogLdsBytes = kP2OffEND + kP2Win * 2;
+static_assert(kChunkMax % kP2Win == 0 && kP2Win - 1 + 255 + 258 <= 0xffffu, "whole windows; a game's end fits END");
 
 } // namespace zgpu

@@ -14,7 +14,8 @@ __global__ void __launch_bounds__(1024, 8) parse2_kernel(ChunkGeom g, LevelCfg c
                                                          const uint32_t *__restrict__ gsv_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg)
 {
     constexpr uint32_t kP2Threads = 1024;
-    constexpr bool FUSED = false;
+    constexpr bool FUSED = false, LOG = false;
+    const uint16_t *const lpos = nullptr; const uint32_t *const lrec = nullptr, *const lcnt = nullptr; uint16_t *const END = nullptr; // (the logs: walk_kernel<1> only)
     __shared__ __attribute__((aligned(16))) uint16_t J[kP2Win]; // successor of a has-position, window-relative (0xffff: leaves the window)
     __shared__ uint32_t HAS[kP2Words], MARK[kP2Words], COV[kP2Words], MAT[kP2Words]; // per position: has a match / on the path / inside a match
                                                                                     // (later: is a token) / starts an emitted match

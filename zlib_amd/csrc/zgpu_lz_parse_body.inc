@@ -2,7 +2,8 @@
 //   parse2_kernel (zgpu_lz_parse.hip)   a kernel of its own, the arrays below static __shared__
 //   walk_kernel   (zgpu_lz_sorted.hip)  behind its walkers, the arrays carved out of the LDS the chunk bytes lived in
 // The includer defines: the arrays J, HAS, MARK, COV, MAT, wbase, VIS, EXITS, wave_tot and the word sh_entry (LDS); g, c, cfg, recs,
-// gmv_all, gsv_all, tokens, meta; the compile-time constants LITE, FUSED, TILE, kP2Threads; the LDS word sh_exit and the TileGeom tg (used when TILE).
+// gmv_all, gsv_all, tokens, meta; the compile-time constants LITE, FUSED, TILE, LOG, kP2Threads; the LDS word sh_exit and the TileGeom tg (used when TILE);
+// the chunk's logs lpos, lrec (global), their counts lcnt and the array END (LDS) -- used when LOG (zgpu_lz_parse.h), which implies LITE and not TILE.
 // TILE (continuous stream, zgpu_cont.hip): the chunk is a tile's 64 KiB; the path starts at the tile's entry (tg.entry, found by the chain over the tiles'
 // exit functions), the tokens are the positions from the entry to the end of the last game that starts below h1 (at most 512 behind it), and the block
 // cuts are not the tile's business (blocks are counted from the start of the stream).
@@ -33,9 +34,29 @@
         t_e = h0_ + tg.entry[g.chunk0 + c];
     }
 
+    static_assert(!LOG || (LITE && !TILE), "the logs are what a chunk's walkers leave");
     P2_T0();
     // ---- 1. has(p) ----
-    for (uint32_t i = tid; i < kP2Words; i += kP2Threads) { MARK[i] = 0; COV[i] = 0; MAT[i] = 0; if (LITE) HAS[i] = p2_ld<FUSED>(gsv + i); }
+    for (uint32_t i = tid; i < kP2Words; i += kP2Threads) { MARK[i] = 0; COV[i] = 0; MAT[i] = 0; if (LOG) HAS[i] = 0; else if (LITE) HAS[i] = p2_ld<FUSED>(gsv + i); }
+    // (the logs' positions are read two to a dword, and nothing is done to a loaded value before every load of its batch is out: a 16-bit load is
+    // widened, and so waited for, where it stands)
+    const uint32_t *lpos2 = reinterpret_cast<const uint32_t *>(lpos);
+    if (LOG) { // a bit per logged game start: the logs' positions, read once and densely
+        constexpr uint32_t kRounds = kP2Win / 2 / kP2Threads;
+        __syncthreads();
+        for (uint32_t w = 0; w < kP2Wins; w++) {
+            const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[w]); // (uniform: the rounds are cut off by scalar branches)
+            uint32_t pv[kRounds];
+#pragma unroll
+            for (uint32_t r = 0; r < kRounds; r++) { pv[r] = 0; if (r * kP2Threads * 2 < cw) pv[r] = p2_ld<FUSED>(lpos2 + w * (kP2Win / 2) + r * kP2Threads + tid); }
+#pragma unroll
+            for (uint32_t r = 0; r < kRounds; r++) {
+                const uint32_t e = (r * kP2Threads + tid) * 2, p0 = pv[r] & 0xffffu, p1 = pv[r] >> 16;
+                if (e < cw) atomicOr(&HAS[p0 >> 5], 1u << (p0 & 31u));
+                if (e + 1 < cw) atomicOr(&HAS[p1 >> 5], 1u << (p1 & 31u));
+            }
+        }
+    }
     if (!LITE) for (uint32_t p0 = 0; p0 < kChunkMax; p0 += kP2Threads * kP2Batch) {
         uint2 rv[kP2Batch];
 #pragma unroll
@@ -70,15 +91,40 @@
         const uint32_t wend = w0 + kP2Win;
         const uint32_t entry = sh_entry;
         uint32_t gm[kP2Own]; // the game of this lane's has-positions: (m - p) << 24 | len << 15 | dist; 0: none
+        uint32_t gp[kP2Own]; // LOG: where the game gm[i] starts (otherwise a lane's positions follow from i)
         uint32_t onp = 0;    // bit i: gm[i] is a game on the path (stage B)
 #pragma unroll
-        for (uint32_t i = 0; i < kP2Own; i++) gm[i] = 0;
+        for (uint32_t i = 0; i < kP2Own; i++) { gm[i] = 0; gp[i] = 0; }
+        auto pos_of = [&](uint32_t i) { return LOG ? gp[i] : w0 + i * kP2Threads + tid; };
         if (entry != kNone && entry < wend) { // (uniform) the path has nodes in this window
             // A1. successors of all has-positions of the window.  A lane's game reads the records of the positions right behind
             // its own: those are its neighbours' records (lanes = consecutive positions), fetched with lane shuffles; the first
             // kP2Over positions behind the wave's 64 are loaded by lanes 0..kP2Over-1 as well.  (A dependent global load per step of
             // the game -- some lane of the wave always needs one -- was 45% of this kernel.)
-            if (LITE) {
+            if (LOG) {
+                // the window's log entries are shared out, entry e to lane e % kP2Threads: the loads of all of a lane's entries are in flight
+                // together (the rounds are cut off by the count, which is uniform), and nothing but the games is looked at -- J and END are
+                // written, and later read, at game starts only
+                const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[w0 / kP2Win]);
+                const uint32_t *lp2 = lpos2 + w0 / 2, *lr = lrec + w0; // (w0 / kP2Win * kP2Win == w0)
+                uint32_t gv[kP2Own], gq[kP2Own];
+#pragma unroll
+                for (uint32_t i = 0; i < kP2Own; i++) {
+                    gv[i] = 0; gq[i] = 0;
+                    if (i * kP2Threads < cw) { const uint32_t e = i * kP2Threads + tid; gq[i] = p2_ld<FUSED>(lp2 + (e >> 1)); gv[i] = p2_ld<FUSED>(lr + e); } // (e < kP2Win: inside the log, whatever the count)
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < kP2Own; i++) {
+                    const bool v = i * kP2Threads + tid < cw;
+                    const uint32_t p = (gq[i] >> ((tid & 1u) << 4)) & 0xffffu; // (kP2Threads is even: entry e's half is lane's)
+                    gm[i] = v ? gv[i] : 0u; gp[i] = v ? p : 0u;
+                    if (v) {
+                        const uint32_t end = p + (gv[i] >> 24) + ((gv[i] >> 15) & 511u), t = next_bit(HAS, end, nwords);
+                        J[p - w0] = (uint16_t)(t < wend ? t - w0 : 0xffffu);
+                        END[p - w0] = (uint16_t)(end - w0);
+                    }
+                }
+            } else if (LITE) {
                 uint32_t gv[kP2Own];
 #pragma unroll
                 for (uint32_t i = 0; i < kP2Own; i++) {
@@ -262,7 +308,8 @@
                 }
                 if (lane == 0) { // the last path node of the window leads to the entry of the next one
                     uint32_t m, L, D;
-                    if (LITE) { const uint32_t gv = p2_ld<FUSED>(gmv + last); m = last + (gv >> 24); L = (gv >> 15) & 511u; D = gv & 32767u; }
+                    if (LOG) { m = w0 + END[last - w0]; L = 0; } // (the end of the game, from stage A1: no trip to memory)
+                    else if (LITE) { const uint32_t gv = p2_ld<FUSED>(gmv + last); m = last + (gv >> 24); L = (gv >> 15) & 511u; D = gv & 32767u; }
                     else cx.game(last, cx.rec[last], cx.rec[last + 1], m, L, D);
                     sh_entry = next_bit(HAS, m + L, nwords);
                     if (TILE) sh_exit = m + L;
@@ -273,7 +320,7 @@
             // B. matches of the path: MAT bit at the match start, COV bits on the bytes behind it (they may reach into the next window)
 #pragma unroll
             for (uint32_t i = 0; i < kP2Own; i++) {
-                const uint32_t p = w0 + i * kP2Threads + tid;
+                const uint32_t p = pos_of(i);
                 // (gm[] is not touched here: `if (on the path) {...} else gm[i] = 0` made hipcc of ROCm 7.2 keep two copies of the array and, in some register
                 // allocations of this kernel, copy gm[6] and gm[7] back as ONE 64-bit pair (v_mov_b64 v[10:11], v[18:19]) behind the zeroing of gm[7]:
                 // games that are not on the path then wrote match tokens in stage D -- round 2's "wrong tokens" whenever this file was touched,
@@ -339,10 +386,21 @@
             for (uint32_t u = 0; u < kP2Batch; u++) {
                 const uint32_t p = w0 + (ib + u) * kP2Threads + tid;
                 if (li[u]) tok[index_of(p)] = tok_lit(lit[u]);
-                const uint32_t gv = ((onp >> (ib + u)) & 1u) ? gm[ib + u] : 0u;
+                const uint32_t gv = (!LOG && ((onp >> (ib + u)) & 1u)) ? gm[ib + u] : 0u;
                 if (gv) {
                     const uint32_t m = p + (gv >> 24), t = tok_match(gv & 32767u, ((gv >> 15) & 511u) - kMinMatch);
                     if (m < wend) tok[index_of(m)] = t; else { def_m = m; def_tok = t; } // (at most one per lane: m - p < 1024)
+                }
+            }
+        }
+        if (LOG) { // the match tokens, by game.  A lane's games lie anywhere in the window, but a game on the path whose match starts at or behind wend
+                   // is the path's last in this window (the next node lies behind the match): one per window, so one deferred token per lane is enough
+#pragma unroll
+            for (uint32_t i = 0; i < kP2Own; i++) {
+                const uint32_t gv = ((onp >> i) & 1u) ? gm[i] : 0u;
+                if (gv) {
+                    const uint32_t m = gp[i] + (gv >> 24), t = tok_match(gv & 32767u, ((gv >> 15) & 511u) - kMinMatch);
+                    if (m < wend) tok[index_of(m)] = t; else { def_m = m; def_tok = t; }
                 }
             }
         }

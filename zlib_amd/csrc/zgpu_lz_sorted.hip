@@ -56,11 +56,13 @@ constexpr uint32_t kGPad = 32, kGStride = kChunkMax + 2 * kGPad;  // fast_kernel
 //   heads: bucket-head bits, heads_below | recs: match3's records (uint2 by position) | ir: idx | rank << 16 by position (u32; what the walkers
 //   and the levels 1-3 kernels look a position up with)
 // The records' memory serves whichever search runs: match3's records, the walkers' games gm (u32 by position) with the bitmaps gs (a bit by
-// position) behind them, or fast_kernel's flag bytes G.
+// position) behind them (tiles), the logs a chunk's walkers hand their games to the fused parse in (lrec: u32, lpos: u16 behind them; kP2Win
+// entries per window, zgpu_lz_parse.h), or fast_kernel's flag bytes G.
 struct SortedWs {
     static constexpr size_t kHeaderBytes = 256, kSBytes = kSStride * 2, kRkBytes = kChunkMax * 2, kHeadBytes = kHeadStride * 4, kRecBytes = kChunkMax * 8, kIrBytes = kChunkMax * 4;
     static constexpr size_t kSlack = 1024; // S's end is rounded up to 256 bytes; the rest is margin
     static_assert(kChunkMax * 4 + kChunkMax / 8 <= kRecBytes && kGStride <= kRecBytes, "gm + gs, and G, lie in the records' memory");
+    static_assert(kChunkMax * (4 + 2) <= kRecBytes, "and so do the logs: the workspace, and with it the batch a device holds, is what it was");
     static size_t bytes(size_t nchunks) { return kHeaderBytes + nchunks * (kSBytes + kRkBytes + kHeadBytes + kRecBytes + kIrBytes) + kSlack; }
 
     size_t nch;
@@ -78,6 +80,8 @@ struct SortedWs {
     }
     uint32_t *gm() const { return reinterpret_cast<uint32_t *>(recs); }
     uint32_t *gs() const { return gm() + nch * kChunkMax; }
+    uint32_t *lrec() const { return reinterpret_cast<uint32_t *>(recs); }
+    uint16_t *lpos() const { return reinterpret_cast<uint16_t *>(lrec() + nch * kChunkMax); }
     uint8_t *G() const { return reinterpret_cast<uint8_t *>(recs); }
 };
 
@@ -750,6 +754,9 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
 //     game ends with, and bit r of the chunk's bitmap gs: what parse2_kernel's stage A1 derives from match3's records,
 //     restricted to the positions some walker stood on (which include the whole path).  The lite form of the parse (zgpu_lz_parse_body.inc)
 //     does the rest: behind the walkers in the same workgroup (chunks), or as parse2_kernel<true, true> once the tiles' entries are known.
+//     A chunk's walkers (MODE 1) do not write gm / gs: a finished game is appended to the log of its window of kP2Win positions (lrec, lpos; slots
+//     from a counter in LDS), which is what the fused parse reads -- dense, and only the games (zgpu_lz_parse.h, LOG).  A store into gm dirtied
+//     a partial line somewhere in 256 KiB, and the parse read all of gm back, a window at a time, to throw three words in four away.
 #ifndef ZGPU_WTRIG
 #define ZGPU_WTRIG 48 // lanes waiting for a pass that make the wave run one
 #endif
@@ -765,7 +772,8 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
 constexpr uint32_t kWFoldAt = ZGPU_WFOLD_AT;
 constexpr uint32_t kWThreads = 512, kWWaves = kWThreads / 64, kWBlk = ZGPU_WBLK, kWTrig = ZGPU_WTRIG, kWNeuShift = ZGPU_WNEU_SHIFT;
 constexpr uint32_t kWNeuBytes = (kChunkMax >> kWNeuShift) / 8;
-constexpr uint32_t kWLds = kM3DataLds + 16 + kWNeuBytes + kWWaves * kM3WaveLds;
+constexpr uint32_t kWOffLcnt = kM3DataLds + 16 + kWNeuBytes + kWWaves * kM3WaveLds; // entries in each window's log (a chunk's walkers; they outlive them)
+constexpr uint32_t kWLds = kWOffLcnt + kP2Wins * 4;
 static_assert(2 * kWLds <= 160 * 1024, "two walker workgroups per CU");
 enum : uint32_t { W_NEED = 0, W_LIMBO = 1, W_READY = 2, W_SEARCH = 3, W_DONE = 4 };
 #ifdef ZGPU_WALK_STATS // debug build only: 0 bodies, 1 active lane-steps, 2 passes, 3 lanes served by passes, 4 searches, 5 folds, 6 parked, 7 limbo starts
@@ -777,6 +785,13 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_stats(uns
     if (reset) hipMemcpyToSymbol(HIP_SYMBOL(walk_stats), z, sizeof z);
 }
 #define W_STAT(i, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane == 0) atomicAdd(&walk_stats[i], v_); } while (0)
+__device__ unsigned long long walk_log_stats[2]; // walk_kernel<1> (scripts/walk_log_stats.py): 0 games logged, 1 the fullest log of a window
+extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_log_stats(unsigned long long *out, int reset)
+{
+    unsigned long long z[2] = {};
+    hipMemcpyFromSymbol(out, HIP_SYMBOL(walk_log_stats), sizeof z);
+    if (reset) hipMemcpyToSymbol(HIP_SYMBOL(walk_log_stats), z, sizeof z);
+}
 #else
 #define W_STAT(i, v) do { } while (0)
 #endif
@@ -904,19 +919,24 @@ __device__ inline void tile_exits(uint8_t *pl, const uint32_t *gm, const uint32_
 // FUSE: when its walkers are done the workgroup goes on with the rest of the parse itself (parse_chunk, zgpu_lz_parse.h, in the LDS the
 // chunk bytes lived in).  That part is all latency -- a window at a time, one wave threading the path -- and leaves the CU's vector
 // units to the other workgroup's walkers, which are bound by exactly those; as a kernel of its own it cost as much as a third of the walk.
-static_assert(kP2LdsBytes <= kM3DataLds, "the parse works in the memory of the chunk bytes");
+// Once the walkers are done the neutral bitmap and the waves' rings and slots are dead as well: the parse's arrays lie over all of the workgroup's LDS
+// but the logs' counts -- J .. sh_entry in the first kP2LdsBytes, END behind them.
+static_assert(kP2LogLdsBytes <= kWOffLcnt, "the parse works in the memory of the chunk bytes, the neutral bitmap and the rings");
 // MODE 1: a chunk, the rest of the parse behind its walkers (FUSE); 2: a TILE of a continuous stream (zgpu_cont.hip) -- walkers start at every possible
 // entry of the tile and at every 64th position of its range [h0, h1), stop at h1, and the workgroup ends with the tile's exit as a function of its entry.
 template <int MODE>
 __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkGeom g, LevelCfg cfg, const uint16_t *__restrict__ S_all, const uint32_t *__restrict__ ir_all,
                                                             uint32_t *__restrict__ gm_all, uint32_t *__restrict__ gs_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg)
 {
+    // (gm_all, gs_all: MODE 2 -- the games by position and their bitmaps; MODE 1 -- the logs' records, lrec, and positions, lpos)
     static_assert(MODE == 1 || MODE == 2, "a chunk or a tile");
     constexpr bool FUSE = MODE == 1, TILE = MODE == 2;
+    static_assert(!FUSE || kWNeuShift == 0, "a log holds kP2Win games: a position must start one game at most, so every neutral position is claimed");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t *d32 = lds;
     uint32_t *ctrl = lds + kM3DataLds / 4; // [0]: next block to hand out
     uint32_t *NEU = ctrl + 4;              // bit p: some walker stands, or stood, at p with nothing in hand
+    uint32_t *lcnt = lds + kWOffLcnt / 4;  // FUSE: games in the log of each window of kP2Win positions
     const uint8_t *d8 = reinterpret_cast<const uint8_t *>(d32);
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t ring = (uint32_t)__builtin_amdgcn_readfirstlane(lds_off(lds) + kM3DataLds + 16 + kWNeuBytes + wave * kM3WaveLds), slot = ring + kRing * 4, pw = slot + 64 * 4;
@@ -926,6 +946,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     const uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
     const uint32_t *ir = ir_all + (size_t)c * kChunkMax;
     uint32_t *gm = gm_all + (size_t)c * kChunkMax, *gs = gs_all + (size_t)c * (kChunkMax / 32);
+    uint32_t *lrec = gm; uint16_t *lpos = reinterpret_cast<uint16_t *>(gs_all) + (size_t)c * kChunkMax; // (FUSE)
     uint32_t th0 = 0, th1 = n, tnent = 0, tnent_all = 0, nil_local = ~0u; // TILE: the range the tile parses, its entries, the position whose first candidate at MAX_DIST is NIL
     uint32_t base = chunk_base(g, c);
     if (TILE) {
@@ -938,9 +959,10 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     }
     const uint32_t npos = n >= 3 ? n - 2 : 0;
     stage_chunk<kWThreads>(src, n, d32, tid);
-    for (uint32_t i = tid; i < kChunkMax / 32; i += kWThreads) { if (i < kWNeuBytes / 4) NEU[i] = 0; gs[i] = 0; }
+    for (uint32_t i = tid; i < kChunkMax / 32; i += kWThreads) { if (i < kWNeuBytes / 4) NEU[i] = 0; if (!FUSE) gs[i] = 0; }
     if (tid < 8) d32[(kChunkMax + 64) / 4 + tid] = 0xffffffffu; // the word the quick check reads where a zero word would look like a hit
     if (tid == 0) ctrl[0] = 0;
+    if (FUSE && tid < kP2Wins) lcnt[tid] = 0;
     __syncthreads();
     int slide_at; // visited positions >= slide_at see the slid window (ParseCtx::slide_at, zgpu_lz_parse.hip)
     {
@@ -1035,8 +1057,14 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             } else if (handL >= kMinMatch) emit = true;            // the match in hand stands (deflate.c:1611-1634)
             else { y = x + 1; irY = irn; toN = haveIr = true; }    // a literal
             if (emit) {
-                gm[gstart] = ((handM - gstart) << 24) | (handL << 15) | handD;
-                atomicOr(&gs[gstart >> 5], 1u << (gstart & 31u));
+                const uint32_t rec = ((handM - gstart) << 24) | (handL << 15) | handD;
+                if (FUSE) { // appended to the log of the game's window: slots go out in time order, so the stores in flight fill a few lines side by side
+                    const uint32_t w = gstart / kP2Win, at = w * kP2Win + atomicAdd(&lcnt[w], 1u); // (at most one game per position: the slot is below kP2Win)
+                    lrec[at] = rec; lpos[at] = (uint16_t)gstart;
+                } else {
+                    gm[gstart] = rec;
+                    atomicOr(&gs[gstart >> 5], 1u << (gstart & 31u));
+                }
                 y = handM + handL; irY = irE; haveIr = haveE; toN = true;
                 handL = kMinMatch - 1;
             }
@@ -1227,17 +1255,21 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         tile_exits<kWThreads>(reinterpret_cast<uint8_t *>(lds), gm, gs, th0, th1, tnent_all, tg.exits + (size_t)c * kTileExitStride, tid);
     }
     if (FUSE) {
-        __syncthreads(); // every walker of the chunk is done: gm / gs are complete (and written: the barrier waits for the stores)
+        __syncthreads(); // every walker of the chunk is done: the logs and their counts are complete (and written: the barrier waits for the stores)
+#ifdef ZGPU_WALK_STATS
+        if (tid < kP2Wins) { atomicAdd(&walk_log_stats[0], (unsigned long long)lcnt[tid]); atomicMax(&walk_log_stats[1], (unsigned long long)lcnt[tid]); }
+#endif
         constexpr uint32_t kP2Threads = kWThreads;
-        constexpr bool LITE = true, FUSED = true, TILE = false;
+        constexpr bool LITE = true, FUSED = true, TILE = false, LOG = true;
         const uint2 *recs = nullptr;
-        const uint32_t *gmv_all = gm_all, *gsv_all = gs_all;
+        const uint32_t *gmv_all = nullptr, *gsv_all = nullptr; // (the position-indexed form: tiles only)
         uint8_t *pl = reinterpret_cast<uint8_t *>(lds);
         uint16_t *const J = reinterpret_cast<uint16_t *>(pl + kP2OffJ);
         uint32_t *const HAS = reinterpret_cast<uint32_t *>(pl + kP2OffHAS), *const MARK = reinterpret_cast<uint32_t *>(pl + kP2OffMARK), *const COV = reinterpret_cast<uint32_t *>(pl + kP2OffCOV),
                  *const MAT = reinterpret_cast<uint32_t *>(pl + kP2OffMAT), *const wbase = reinterpret_cast<uint32_t *>(pl + kP2OffWbase), *const VIS = reinterpret_cast<uint32_t *>(pl + kP2OffVIS),
                  *const EXITS = reinterpret_cast<uint32_t *>(pl + kP2OffEXITS), *const wave_tot = reinterpret_cast<uint32_t *>(pl + kP2OffWtot);
         uint32_t &sh_entry = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry), &sh_exit = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry + 4);
+        uint16_t *const END = reinterpret_cast<uint16_t *>(pl + kP2OffEND);
 #include "zgpu_lz_parse_body.inc"
     }
 }
@@ -1466,7 +1498,8 @@ template <int MODE> static void launch_walk(const ChunkGeom &g, LevelCfg cfg, co
 {
     static bool opt_in = false; // (one per MODE)
     if (!opt_in) { hipFuncSetAttribute(reinterpret_cast<const void *>(walk_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWLds); opt_in = true; }
-    hipLaunchKernelGGL(walk_kernel<MODE>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, ws.S, ws.ir, ws.gm(), ws.gs(), tokens, meta, tg);
+    uint32_t *games = MODE == 1 ? ws.lrec() : ws.gm(), *starts = MODE == 1 ? reinterpret_cast<uint32_t *>(ws.lpos()) : ws.gs();
+    hipLaunchKernelGGL(walk_kernel<MODE>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, ws.S, ws.ir, games, starts, tokens, meta, tg);
 }
 
 // A batch of chunks: the sort, then the search and parse `impl` names -- ZGPU_LZ_WALK: walk_kernel<1>; ZGPU_LZ_SORTED: the all-position search

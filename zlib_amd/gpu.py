@@ -95,6 +95,7 @@ def load_library():
     L.zgpu_deflate_bound_geometry.argtypes = [u64, u32, C.c_int, C.c_int]
     L.zgpu_deflate_bound_geometry.restype = u64
     L.zgpu_deflate_set_geometry.argtypes = [vp, C.c_int, C.c_int]
+    L.zgpu_deflate_set_tuning.argtypes = [vp, C.c_int, u32, u32, u32, u32]
     L.zgpu_deflate_device.argtypes = [vp, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp]
     L.zgpu_deflate_host.argtypes = [vp, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult)]
     L.zgpu_deflate_cont_bound.argtypes = [u64]
@@ -258,7 +259,12 @@ class Engine:
         self._check(self.L.zgpu_deflate_set_geometry(self.h, window_bits, mem_level))
         self.geometry = (window_bits, mem_level)
 
-    def deflate_segments_host(self, buffers, level, flags=0, lz_impl=LZ_AUTO, want_items=False):
+    def set_tuning(self, tune=None):
+        """deflateTune for the deflate calls that follow: tune = (good_length, max_lazy, nice_length, max_chain) instead of the level's row; None: the level's row again."""
+        g, l, n, c = tune if tune else (0, 0, 0, 0)
+        self._check(self.L.zgpu_deflate_set_tuning(self.h, 1 if tune else 0, g, l, n, c))
+
+    def deflate_segments_host(self, buffers, level, flags=0, lz_impl=LZ_AUTO, want_items=False, strategy=0):
         """Batch of independent buffers (each <= 65536 bytes) -> list of raw-deflate segments, one launch.  want_items: also the per-segment
         records (zgpu_deflate_segments_items_host) as a list of (out_lo, out_bytes, in_bytes, data_type, adler32, crc32)."""
         import numpy as np
@@ -271,7 +277,7 @@ class Engine:
             cap = int(offs[-1]) + len(buffers) * (12288 + 5 * 520)
         out = np.empty(cap, dtype=np.uint8)
         ooffs = np.zeros(len(buffers) + 1, dtype=np.uint64)
-        p = _Params(level, 0, flags, lz_impl)
+        p = _Params(level, 0, flags, lz_impl, strategy, 0)
         res = DeflateResult()
         if want_items:
             cap += 26 * len(buffers)  # (room for any wrapper)
