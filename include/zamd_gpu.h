@@ -305,7 +305,7 @@ int zgpu_inflate_stream_host3(zgpu_engine *e, const void *in, uint64_t in_bytes,
                               zgpu_inflate_result *res);
 /* A body that does not split at flush markers and holds at least 128 KiB (ZGPU_SPEC_MIN_BYTES) is decoded in pieces all the same: block starts
  * are searched behind every 1/4096 of the input (at least 32 KiB apart), every piece is decoded with the 32 KiB in front of it unknown,
- * the chain of pieces is checked and the unknowns filled in afterwards (zgpu_inflate.hip, spec_*).  A stream whose pieces do
+ * the chain of pieces is checked and the unknowns filled in afterwards (zgpu_inflate_stream.hip, spec_*).  A stream whose pieces do
  * not chain -- damaged, cut short, or one false block start -- goes through the one-workgroup decoder and gets its verdict.
  * Diagnostics: how many streams this process decoded in pieces / sent to the one-workgroup decoder. */
 /* Test hook: the next launch of the fast position sort reports that its self-check failed (the LDS did not serve an atomic's lanes in

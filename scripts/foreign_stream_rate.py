@@ -1,5 +1,5 @@
 """GPU box: rate of the decode of a stream that was not produced in chunks (system zlib, level 6), through zgpu_inflate_stream_host2 (host
-buffers in and out, PCIe included) -- decoded in pieces (spec_* in zgpu_inflate.hip) -- against the system zlib on one host core.
+buffers in and out, PCIe included) -- decoded in pieces (spec_* in zgpu_inflate_stream.hip) -- against the system zlib on one host core.
   python scripts/foreign_stream_rate.py [MiB of input, default 1024]"""
 import os
 import sys

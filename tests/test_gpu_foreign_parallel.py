@@ -1,6 +1,6 @@
 """SURVEY.md 8f N4 -- streams that were not produced in chunks (the system zlib's output) decoded in pieces: block starts found by
 search, every piece decoded with the window in front of it unknown, the chain of pieces checked, the unknowns filled in
-(zgpu_inflate.hip, spec_*).  Bytes must equal the input; verdicts on damaged and cut streams must be the one-workgroup decoder's
+(zgpu_inflate_stream.hip, spec_*).  Bytes must equal the input; verdicts on damaged and cut streams must be the one-workgroup decoder's
 (which the round-1 tests pin against the reference and the system zlib); the counter says which way a stream went."""
 import zlib
 

@@ -63,6 +63,19 @@ struct BatchItemState {
     uint32_t msg, used;          // used: body bytes up to the end of the final block
     uint32_t out_bytes, npieces;
 };
+// What the decoder (inflate_kernel_t, zgpu_inflate.hip) says of one segment
+struct InfStatus { int32_t code; uint32_t msg; uint32_t out_bytes; uint32_t used; }; // used: input bytes up to the end of the last block | final block seen << 31
+constexpr uint32_t kWholeStream = 0xFFFFFFFFu; // the decoder's chunk_size argument: the one segment is a whole stream of any size
+// ... and of one piece of a stream decoded in pieces (zgpu_inflate_stream.hip), with where the pieces' 16-bit symbols go
+struct SpecEnd { uint64_t end_bit; uint32_t out_bytes, flags; }; // flags: bit 0 the segment ended with the final block, bit 1 the page pool ran dry
+struct SpecArgs {
+    uint16_t *mid;        // pages of kOutHalf symbols
+    uint64_t *page_owner; // per page: segment << 32 | index of the page within the segment
+    uint32_t *page_count; // pages taken so far
+    uint32_t page_cap;
+    uint16_t *tails;      // per segment: the ring when it ended, oldest symbol first = the last 32 KiB of the segment's output
+    SpecEnd *ends;
+};
 
 // the header every segment of a wrapped segment call starts with (zgpu_stitch.hip, frame_kernel); bgzf: the last two of its bytes are BSIZE,
 // the block's total length - 1, which frame_kernel fills in per segment

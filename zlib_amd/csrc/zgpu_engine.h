@@ -37,6 +37,12 @@ template <typename T> struct DevBuf {
     }
 };
 
+// Offsets of the pieces of one allocation, in the order they are asked for: every piece rounded up to 256 bytes; `off` is the size so far
+struct Carve {
+    size_t off = 0;
+    size_t operator()(size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; }
+};
+
 } // namespace zgpu
 
 struct StageSpan { int stage; hipEvent_t a, b; };
@@ -196,9 +202,23 @@ void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const 
                         uint32_t nblk_cap, const uint32_t *T, uint32_t *carry, uint64_t seg_end, hipStream_t s);
 
 // ---- zgpu_inflate.hip ----
+// One launch of the decoder, inflate_kernel_t: segments [chunk0, chunk0 + nchunks) of `offsets`, one workgroup each, records to status[0, nchunks).  The
+// defaults are those of a stream that stands alone (batch items, the sizing pass, the pieces of a foreign stream)
+struct InfLaunch {
+    const uint8_t *in; uint64_t in_bytes; const uint64_t *offsets; uint64_t chunk0; uint32_t nchunks;
+    uint8_t *out; uint64_t out_cap; InfStatus *status;
+    uint64_t last_chunk = ~0ull; uint32_t chunk_size = kWholeStream; ChunkMeta *meta = nullptr;
+    const uint8_t *dict = nullptr; uint32_t dict_len = 0; uint32_t stream_mode = 1;
+};
+enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces }; // kInfPieces: always the 32 KiB ring of 16-bit symbols; kInfSizes: no ring at all
+constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes or kInfPieces launch: the kind fixes the ring, the launcher does not look at the value
+int inflate_ring_kb(); // ZGPU_INF_RING_KB, read at EVERY call (the tests run the same streams through all three): 8, 16, anything else 32; not set: the build's default
+void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const SpecArgs &sp, hipStream_t st);
+int output_checksums(zgpu_engine *e, const uint8_t *d_out, uint64_t nbytes, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st);
 int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t nchunks, uint32_t chunk_size, uint8_t *d_out, uint64_t out_cap,
                 zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode = 0, const uint64_t *h_offsets = nullptr, bool open_end = false, uint8_t *h_dst = nullptr, uint64_t h_cap = 0);
 
+// ---- zgpu_inflate_batch.hip ----
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,
                       const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st);
 int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,

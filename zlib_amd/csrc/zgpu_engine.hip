@@ -1263,7 +1263,7 @@ hipEvent_t engine_copy_event(zgpu_engine *e, size_t i)
     while (e->copy_ev.size() <= i) { hipEvent_t ev; if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr; e->copy_ev.push_back(ev); }
     return e->copy_ev[i];
 }
-// stage timing for the launches of the other files (zgpu_lz_parallel.hip, zgpu_lz_sorted.hip, zgpu_inflate.hip) with the engine's event pool
+// stage timing for the launches of the other files (zgpu_lz_parallel.hip, zgpu_lz_sorted.hip, zgpu_inflate*.hip) with the engine's event pool
 void prof_span_begin(zgpu_engine *e, hipStream_t st, hipEvent_t *a)
 {
     if (e && e->prof) { *a = next_event(e); hipEventRecord(*a, st); }

@@ -1,0 +1,489 @@
+// zgpu_inflate_batch.hip -- batch of independent streams (zgpu_inflate_batch_*): item k = in[in_off[k], in_off[k+1]) -> out[out_off[k], out_off[k+1]), every
+// item a stream of its own with its own verdict.  The header kernel reads each item's wrapper (qcsrc/inflate.c:589-760), the decoder (zgpu_inflate.hip) runs
+// in BATCH mode (one workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and
+// the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.
+#include "zgpu_common.h"
+#include "zgpu_engine.h"
+#include "../../include/zamd_gpu.h"
+#include <cstring>
+#include <vector>
+
+namespace zgpu {
+__device__ inline uint32_t crc_bytes(uint32_t c, const uint8_t *p, uint64_t n) // crc32() of the reference (crc32.c:219), bit by bit: headers are short
+{
+    c = ~c;
+    for (uint64_t i = 0; i < n; i++) {
+        c ^= p[i];
+#pragma unroll
+        for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xedb88320u : c >> 1;
+    }
+    return ~c;
+}
+
+// one lane per item: the wrapper in front of the deflate data (HEAD .. HCRC / DICTID of inflate(), inflate.c:589-760, windowBits -15 / 15 / 31 / 47).
+// bad[0] |= 1: an offsets table that runs backwards or leaves its buffer (a bad argument of the call; such an item is made empty here).
+// Item k reads in[in_lo[k], in_hi[k]) and owns out[out_lo[k], out_hi[k]): four tables, so that a caller whose items overlap (zgpu_gzip.hip) can say
+// so; an offsets table of n + 1 entries is (off, off + 1).
+__global__ void __launch_bounds__(256) batch_header_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *in_lo, const uint64_t *in_hi, uint64_t n,
+                                                           uint32_t wrap, uint64_t out_cap, const uint64_t *out_lo, const uint64_t *out_hi, uint64_t *seg,
+                                                           BatchItemState *items, uint32_t *bad)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    uint64_t lo = in_lo[k], hi = in_hi[k], ol = out_lo[k], oh = out_hi[k];
+    if (lo > hi || hi > in_bytes || ol > oh || oh > out_cap) { atomicOr(bad, 1u); lo = hi = 0; ol = oh = 0; }
+    const uint8_t *p = in + lo;
+    const uint64_t len = hi - lo;
+    uint32_t kind = wrap, msg = kMsgNone;
+    int32_t code = ZGPU_OK;
+    uint64_t pos = 0;
+    if (wrap == kWrapAuto) kind = (len >= 2 && p[0] == 0x1f && p[1] == 0x8b) ? kWrapGzip : kWrapZlib;
+    auto fail = [&](uint32_t m) { if (code == ZGPU_OK) { code = ZGPU_DATA_ERROR; msg = m; } };
+    if (kind == kWrapZlib) {
+        if (len < 2) fail(kMsgTruncated);
+        else if (((uint32_t)p[0] << 8 | p[1]) % 31) fail(kMsgHeaderCheck);
+        else if ((p[0] & 15u) != 8) fail(kMsgMethod);
+        else if ((p[0] >> 4) + 8 > 15) fail(kMsgWindow);
+        else if (p[1] & 0x20) { if (len < 6) fail(kMsgTruncated); else code = 2; } // FDICT: the dictionary's Adler-32 follows, inflate() returns Z_NEED_DICT
+        pos = 2;
+    } else if (kind == kWrapGzip) {
+        if (len < 2) fail(kMsgTruncated);
+        else if (p[0] != 0x1f || p[1] != 0x8b) fail(kMsgHeaderCheck);
+        else if (len < 10) fail(kMsgTruncated);
+        else if (p[2] != 8) fail(kMsgMethod);
+        else if (p[3] & 0xe0) fail(kMsgHeaderFlags);
+        else {
+            const uint32_t flg = p[3];
+            pos = 10;
+            if (flg & 4) { // FEXTRA
+                if (pos + 2 > len) fail(kMsgTruncated);
+                else { pos += 2 + (p[pos] | (uint32_t)p[pos + 1] << 8); if (pos > len) fail(kMsgTruncated); }
+            }
+            for (uint32_t f = 8; f <= 16 && code == ZGPU_OK; f <<= 1) // FNAME, FCOMMENT: zero-terminated
+                if (flg & f) { while (pos < len && p[pos]) pos++; if (pos >= len) fail(kMsgTruncated); else pos++; }
+            if ((flg & 2) && code == ZGPU_OK) { // FHCRC: the low 16 bits of the CRC-32 of the header in front of it
+                if (pos + 2 > len) fail(kMsgTruncated);
+                else if ((crc_bytes(0, p, pos) & 0xffffu) != (p[pos] | (uint32_t)p[pos + 1] << 8)) fail(kMsgHeaderCrc);
+                pos += 2;
+            }
+        }
+    }
+    if (code != ZGPU_OK) pos = 0;
+    const uint64_t body = code == ZGPU_OK ? lo + pos : 0, end = code == ZGPU_OK ? hi : 0; // (an item whose header failed decodes as an empty segment)
+    seg[4 * k] = body; seg[4 * k + 1] = end; seg[4 * k + 2] = ol; seg[4 * k + 3] = oh;
+    BatchItemState s{};
+    s.in_lo = lo; s.in_hi = hi; s.body_lo = lo + pos; s.out_lo = ol; s.kind = kind; s.code = code; s.msg = msg;
+    items[k] = s;
+}
+
+// the decoder's verdict behind the header's; how many 64 KiB pieces of output the item's checks read
+__global__ void __launch_bounds__(256) batch_merge_kernel(const InfStatus *__restrict__ status, uint64_t n, uint32_t any_check, BatchItemState *items)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    BatchItemState s = items[k];
+    if (s.code == ZGPU_OK) {
+        const InfStatus t = status[k];
+        s.code = t.code; s.msg = t.code == ZGPU_DATA_ERROR ? t.msg : 0u; s.out_bytes = t.out_bytes; s.used = t.used & 0x7fffffffu;
+    }
+    s.npieces = (s.code == ZGPU_OK && any_check) ? (uint32_t)(((uint64_t)s.out_bytes + kChunkMax - 1) / kChunkMax) : 0u;
+    items[k].code = s.code; items[k].msg = s.msg; items[k].out_bytes = s.out_bytes; items[k].used = s.used; items[k].npieces = s.npieces;
+}
+
+// one workgroup: piece0 = exclusive scan of npieces; total[0] = all pieces
+__global__ void __launch_bounds__(1024) batch_piece_scan_kernel(BatchItemState *items, uint64_t n, unsigned long long *total)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (n + 1023) / 1024, a = tid * per < n ? tid * per : n, z = (tid + 1) * per < n ? (tid + 1) * per : n;
+    unsigned long long sum = 0;
+    for (uint64_t i = a; i < z; i++) sum += items[i].npieces;
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const unsigned long long add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    unsigned long long o = part[tid] - sum;
+    for (uint64_t i = a; i < z; i++) { items[i].piece0 = o; o += items[i].npieces; }
+    if (tid == 1023) total[0] = part[1023];
+}
+
+// the piece table: item k owns boundaries [piece0 + k, piece0 + k + npieces] (its pieces, then the gap up to the next item's range, which no
+// launch reads); map lists the pieces themselves, in item order
+__global__ void __launch_bounds__(256) batch_piece_fill_kernel(const BatchItemState *__restrict__ items, uint64_t n, uint64_t *tab, uint32_t *map)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const BatchItemState s = items[k];
+    const uint64_t base = s.piece0 + k;
+    for (uint32_t i = 0; i < s.npieces; i++) { tab[base + i] = s.out_lo + (uint64_t)i * kChunkMax; map[s.piece0 + i] = (uint32_t)(base + i); }
+    tab[base + s.npieces] = s.out_lo + s.out_bytes;
+}
+
+// The scratch of a batch call, one allocation (the engine's inf_status).  The sizing pass has the prefix; the decode adds the pieces of the output its
+// checks read.  A packed call runs one behind the other over the same items: the decode takes the scratch over, its prefix lies where the sizing pass's lay.
+struct BatchScratch {
+    uint64_t *seg; BatchItemState *items; InfStatus *status;
+    unsigned long long *cnt; // 256 bytes: [0] pieces (a packed call: the layout's total), [1] failed items, [2] bad offsets
+    uint64_t *tab; uint32_t *map; ChunkMeta *meta; // decode only: the piece boundaries, the piece list, the pieces' checksums
+};
+static int batch_scratch(zgpu_engine *e, uint64_t n, bool decode, uint64_t max_pieces, BatchScratch *s) // decode false: the sizing pass, the prefix alone
+{
+    Carve at;
+    const size_t o_seg = at(n * 32), o_items = at(n * sizeof(BatchItemState)), o_status = at(n * sizeof(InfStatus)), o_cnt = at(256);
+    size_t o_tab = 0, o_map = 0, o_meta = 0;
+    if (decode) { o_tab = at((max_pieces + n + 1) * 8); o_map = at(max_pieces * 4); o_meta = at(max_pieces * sizeof(ChunkMeta)); }
+    if (e->inf_status.reserve(e, at.off)) return ZGPU_MEM_ERROR;
+    uint8_t *scr = e->inf_status;
+    *s = BatchScratch{};
+    s->seg = reinterpret_cast<uint64_t *>(scr + o_seg); s->items = reinterpret_cast<BatchItemState *>(scr + o_items);
+    s->status = reinterpret_cast<InfStatus *>(scr + o_status); s->cnt = reinterpret_cast<unsigned long long *>(scr + o_cnt);
+    if (decode) { s->tab = reinterpret_cast<uint64_t *>(scr + o_tab); s->map = reinterpret_cast<uint32_t *>(scr + o_map); s->meta = reinterpret_cast<ChunkMeta *>(scr + o_meta); }
+    return ZGPU_OK;
+}
+
+int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks,
+                      uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st)
+{
+    return inflate_batch_run_ranges(e, d_in, in_bytes, d_in_off, d_in_off ? d_in_off + 1 : nullptr, n, wrap, checks, d_out, out_cap, d_out_off,
+                                    d_out_off ? d_out_off + 1 : nullptr, d_items, nfailed, nullptr, st);
+}
+
+// The same with every item's input end and output end given on their own (device tables of n entries each): items may overlap in the input.
+// *states (optional): the items' BatchItemState records in the engine's scratch, good until the next inflate call -- `used` and `out_bytes` of an
+// item whose range was too small (ZGPU_BUF_ERROR) are there.
+int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,
+                             uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_lo, const uint64_t *d_out_hi, zgpu_inflate_item *d_items, uint64_t *nfailed,
+                             const BatchItemState **states, hipStream_t st)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (states) *states = nullptr;
+    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (checks & ~3u) || (n && (!d_in_lo || !d_in_hi || !d_out_lo || !d_out_hi || !d_items)) || (n && in_bytes && !d_in) ||
+        (n && out_cap && !d_out) || n >= (1ull << 32))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    // the check each item's wrapper needs is always computed (AUTO: both), the others when asked for
+    const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
+    const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    BatchScratch s;
+    if (int rc = batch_scratch(e, n, true, (out_cap >> 16) + n, &s)) return rc;
+    ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
+    const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_lo, d_in_hi, n, (uint32_t)wrap, out_cap, d_out_lo, d_out_hi, s.seg, s.items,
+                       reinterpret_cast<uint32_t *>(s.cnt + 2));
+    const int ring_kb = inflate_ring_kb(); // (items go straight to their place: the small rings serve them as they serve chunks)
+    hipEvent_t ev{};
+    prof_span_begin(e, st, &ev);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        launch_inflate_decode(kInfBatch, ring_kb, InfLaunch{d_in, in_bytes, s.seg, c0, nb, d_out, out_cap, s.status + c0}, SpecArgs{}, st);
+    }
+    prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+    hipLaunchKernelGGL(batch_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
+    hipLaunchKernelGGL(batch_piece_scan_kernel, dim3(1), dim3(1024), 0, st, s.items, n, s.cnt);
+    hipLaunchKernelGGL(batch_piece_fill_kernel, dim3(ngrid), dim3(256), 0, st, s.items, n, s.tab, s.map);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[2]) { collect_spans(e); return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range"); }
+    if (h[0]) {
+        ChunkGeom g{}; g.in = d_out; g.in_bytes = out_cap; g.seg_off = s.tab; g.chunk0 = 0; g.final_chunk = ~0ull; g.chunk_size = kChunkMax;
+        g.nchunks = (uint32_t)h[0]; g.chunk_map = s.map;
+        if (do_adler) launch_adler(g, s.meta, st);
+        if (do_crc) launch_crc(g, s.meta, st);
+    }
+    launch_batch_finish(s.items, n, s.meta, d_in, do_adler, do_crc, d_items, s.cnt + 1, st);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    collect_spans(e);
+    if (nfailed) *nfailed = h[1];
+    if (states) *states = s.items;
+    return ZGPU_OK;
+}
+
+// ---- sizing pass and packed decode (zgpu_inflate_batch_sizes_* / zgpu_inflate_batch_packed_*) ----
+// the record of a sizes call: the header's verdict, behind it the sizing kernel's, behind that the one thing batch_finish_kernel says without having
+// seen the decoded bytes -- an item whose trailer does not fit behind its final block is truncated
+__global__ void __launch_bounds__(256) batch_sizes_finish_kernel(const BatchItemState *__restrict__ items, const InfStatus *__restrict__ status, uint64_t n,
+                                                                 zgpu_inflate_item *out, unsigned long long *nfailed)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const BatchItemState s = items[k];
+    zgpu_inflate_item r{};
+    r.code = s.code; r.msg = s.msg; r.adler32 = 1; r.crc32 = 0;
+    if (s.code == ZGPU_OK) {
+        const InfStatus t = status[k];
+        r.code = t.code; r.msg = t.code == ZGPU_DATA_ERROR ? t.msg : 0u;
+        if (t.code == ZGPU_OK) {
+            const uint64_t end = s.body_lo + (t.used & 0x7fffffffu), tl = s.kind == kWrapZlib ? 4 : s.kind == kWrapGzip ? 8 : 0;
+            if (end + tl > s.in_hi) { r.code = ZGPU_DATA_ERROR; r.msg = kMsgTruncated; }
+            else { r.out_bytes = t.out_bytes; r.in_used = end + tl - s.in_lo; }
+        }
+    }
+    out[k] = r;
+    if (r.code != ZGPU_OK) atomicAdd(nfailed, 1ull);
+}
+
+// one workgroup (the pattern of batch_piece_scan_kernel): lo[k] = the sizes in front of item k, each start rounded up to `align` (a power of two; starts
+// that are all multiples of it: an exclusive scan of the rounded sizes), hi[k] = lo[k] + size[k], lo[n] = total[0] = the end of the last item.  An item
+// whose sizing failed has size 0.
+__global__ void __launch_bounds__(1024) batch_layout_kernel(const zgpu_inflate_item *__restrict__ items, uint64_t n, uint64_t align, uint64_t *lo, uint64_t *hi,
+                                                            unsigned long long *total)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (n + 1023) / 1024, a = tid * per < n ? tid * per : n, z = (tid + 1) * per < n ? (tid + 1) * per : n;
+    auto size_of = [&](uint64_t i) { return items[i].code == ZGPU_OK ? items[i].out_bytes : 0ull; };
+    unsigned long long sum = 0;
+    for (uint64_t i = a; i < z; i++) sum += (size_of(i) + align - 1) & ~(align - 1);
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const unsigned long long add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    unsigned long long o = part[tid] - sum;
+    for (uint64_t i = a; i < z; i++) {
+        const uint64_t sz = size_of(i);
+        lo[i] = o; hi[i] = o + sz;
+        if (i + 1 == n) { lo[n] = o + sz; total[0] = o + sz; }
+        o += (sz + align - 1) & ~(align - 1);
+    }
+}
+
+// behind the decode of a packed call: an item that was sized takes the decoder's record, one whose sizing failed keeps the sizing pass's
+__global__ void __launch_bounds__(256) batch_packed_merge_kernel(const zgpu_inflate_item *__restrict__ decoded, uint64_t n, zgpu_inflate_item *items, unsigned long long *nfailed)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    if (items[k].code == ZGPU_OK) items[k] = decoded[k];
+    if (items[k].code != ZGPU_OK) atomicAdd(nfailed, 1ull);
+}
+
+// The sizing pass over items in[d_in_off[k], d_in_off[k + 1]): records into d_items.  The counters stay in the engine's scratch (*cnt_out: [1] failed
+// items, [2] bad offsets) and nothing is read back here: the caller's one read-back fetches them.
+static int inflate_batch_sizes_launch(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items,
+                                      unsigned long long **cnt_out, hipStream_t st)
+{
+    BatchScratch s;
+    if (int rc = batch_scratch(e, n, false, 0, &s)) return rc;
+    ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
+    const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    // (there is no destination: the header kernel is given the input tables a second time in its place, so that its range check passes what the first passes)
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, d_in_off + 1, n, (uint32_t)wrap, in_bytes, d_in_off, d_in_off + 1, s.seg, s.items,
+                       reinterpret_cast<uint32_t *>(s.cnt + 2));
+    hipEvent_t ev{};
+    prof_span_begin(e, st, &ev);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        launch_inflate_decode(kInfSizes, kInfNoRing, InfLaunch{d_in, in_bytes, s.seg, c0, nb, nullptr, 0, s.status + c0}, SpecArgs{}, st);
+    }
+    prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+    hipLaunchKernelGGL(batch_sizes_finish_kernel, dim3(ngrid), dim3(256), 0, st, s.items, s.status, n, d_items, s.cnt + 1);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    *cnt_out = s.cnt;
+    return ZGPU_OK;
+}
+
+static int batch_sizes_args(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, const void *d_items)
+{
+    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (n && (!d_in_off || !d_items)) || (n && in_bytes && !d_in) || n >= (1ull << 32))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    return ZGPU_OK;
+}
+
+int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, uint64_t *nfailed,
+                            hipStream_t st)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (int rc = batch_sizes_args(e, d_in, in_bytes, d_in_off, n, wrap, d_items)) return rc;
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    unsigned long long *cnt = nullptr, h[3] = {0, 0, 0};
+    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &cnt, st)) return rc;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    collect_spans(e);
+    if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    if (nfailed) *nfailed = h[1];
+    return ZGPU_OK;
+}
+
+// sizing pass, layout, decode.  ZGPU_BUF_ERROR (*total > out_cap): d_out_offsets, *total and the sizing records stand, nothing is decoded.
+// stage_out (the host entry): the destination is the engine's output staging buffer, made large enough once the total is known -- d_out is not used
+int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, hipStream_t st, bool stage_out)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (align == 0 || align > 256 || (align & (align - 1)) || (checks & ~3u) || !total || (n && !d_out_off) || (n && out_cap && !d_out && !stage_out))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_sizes_args(e, d_in, in_bytes, d_in_off, n, wrap, d_items)) return rc;
+    *total = 0;
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    if (e->pk_hi.reserve(e, n + 1) || e->pk_items.reserve(e, n)) return ZGPU_MEM_ERROR;
+    unsigned long long *cnt = nullptr, h[3] = {0, 0, 0};
+    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &cnt, st)) return rc;
+    hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(1024), 0, st, d_items, n, (uint64_t)align, d_out_off, e->pk_hi.p, cnt);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    collect_spans(e);
+    if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    *total = h[0];
+    if (nfailed) *nfailed = h[1];
+    if (h[0] > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    if (stage_out) {
+        if (int rc = ensure_stage(e, 0, h[0])) return rc;
+        d_out = e->stage_out; out_cap = h[0];
+    }
+    // (the decode takes the engine's scratch over: the layout lives in the caller's table and pk_hi, the decoder's records go to pk_items)
+    if (int rc = inflate_batch_run_ranges(e, d_in, in_bytes, d_in_off, d_in_off + 1, n, wrap, checks, d_out, out_cap, d_out_off, e->pk_hi.p, e->pk_items.p, nullptr, nullptr, st)) return rc;
+    unsigned long long *fin = reinterpret_cast<unsigned long long *>(e->pk_hi.p + n);
+    ZGPU_HIP_CHECK(hipMemsetAsync(fin, 0, sizeof *fin, st));
+    hipLaunchKernelGGL(batch_packed_merge_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, e->pk_items.p, n, d_items, fin);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, fin, sizeof h[0], hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    if (nfailed) *nfailed = h[0];
+    return ZGPU_OK;
+}
+} // namespace zgpu
+
+using namespace zgpu;
+
+// host arrays: the input and its offsets table staged in the engine's input buffer, the records and a second table behind them -- a packed call's
+// layout, or (out_offsets) the caller's output table, checked like the first and uploaded; out_bytes: the room the output staging buffer needs
+static int batch_stage_input(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, uint64_t out_bytes, uint64_t **d_in_off, uint64_t **d_out_off,
+                             zgpu_inflate_item **d_items, const uint64_t *out_offsets = nullptr, uint64_t out_cap = 0)
+{
+    for (uint64_t k = 0; k < n; k++)
+        if (in_offsets[k] > in_offsets[k + 1] || in_offsets[k + 1] > in_bytes || (out_offsets && (out_offsets[k] > out_offsets[k + 1] || out_offsets[k + 1] > out_cap)))
+            return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    const uint64_t tab_bytes = (n + 1) * sizeof(uint64_t), tab_room = (tab_bytes + 255) & ~255ull, o_tab = (in_bytes + 255) & ~255ull, o_items = o_tab + 2 * tab_room;
+    if (int rc = ensure_stage(e, o_items + n * sizeof(zgpu_inflate_item), out_bytes)) return rc;
+    uint8_t *sin = e->stage_in;
+    *d_in_off = reinterpret_cast<uint64_t *>(sin + o_tab); *d_out_off = reinterpret_cast<uint64_t *>(sin + o_tab + tab_room);
+    *d_items = reinterpret_cast<zgpu_inflate_item *>(sin + o_items);
+    if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(sin, in, in_bytes, hipMemcpyHostToDevice, e->stream));
+    ZGPU_HIP_CHECK(hipMemcpyAsync(*d_in_off, in_offsets, tab_bytes, hipMemcpyHostToDevice, e->stream));
+    if (out_offsets) ZGPU_HIP_CHECK(hipMemcpyAsync(*d_out_off, out_offsets, tab_bytes, hipMemcpyHostToDevice, e->stream));
+    return ZGPU_OK;
+}
+
+// Bytes [lo, hi) of the output staging buffer to the caller's buffer `o`, only those of the items that succeeded (the others' bytes, any room an item
+// did not fill and the gaps of an alignment stay as the caller left them).  dense: there is nothing to leave out, the range goes in one copy
+static int batch_copy_back(zgpu_engine *e, bool dense, uint64_t lo, uint64_t hi, const uint64_t *out_offsets, const zgpu_inflate_item *items, uint64_t n, uint8_t *o)
+{
+    if (dense) {
+        if (hi > lo) ZGPU_HIP_CHECK(hipMemcpy(o + lo, e->stage_out.p + lo, hi - lo, hipMemcpyDeviceToHost));
+        return ZGPU_OK;
+    }
+    std::vector<uint8_t> tmp(hi - lo);
+    if (hi > lo) ZGPU_HIP_CHECK(hipMemcpy(tmp.data(), e->stage_out.p + lo, hi - lo, hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < n; k++)
+        if (items[k].code == ZGPU_OK && items[k].out_bytes) memcpy(o + out_offsets[k], tmp.data() + (out_offsets[k] - lo), items[k].out_bytes);
+    return ZGPU_OK;
+}
+
+extern "C" {
+#pragma GCC visibility push(default)
+int zgpu_inflate_batch_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks,
+                              void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_batch_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, checks, static_cast<uint8_t *>(d_out), out_cap,
+                             d_out_offsets, d_items, nfailed, st);
+}
+
+// host arrays: input, both offset tables and the records staged in the engine's buffers; the decoded range comes back in one copy and each item
+// that succeeded is placed from there
+int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, uint32_t checks,
+                            void *out, uint64_t out_cap, const uint64_t *out_offsets, zgpu_inflate_item *items, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (n && (!in_offsets || !out_offsets || !items || (in_bytes && !in) || (out_cap && !out))) return fail(e, ZGPU_STREAM_ERROR, "null argument");
+    if (n == 0) return ZGPU_OK;
+    const uint64_t lo = out_offsets[0], hi = out_offsets[n];
+    uint64_t *d_in_off, *d_out_off;
+    zgpu_inflate_item *d_items;
+    if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, hi, &d_in_off, &d_out_off, &d_items, out_offsets, out_cap)) return rc;
+    hipStream_t st = e->stream;
+    if (int rc = inflate_batch_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, checks, e->stage_out, hi, d_out_off, d_items, nfailed, st)) return rc;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    bool all = true; // every item succeeded and filled its room exactly: the range goes straight to the caller
+    for (uint64_t k = 0; k < n && all; k++) all = items[k].code == ZGPU_OK && items[k].out_bytes == out_offsets[k + 1] - out_offsets[k];
+    return batch_copy_back(e, all, lo, hi, out_offsets, items, n, static_cast<uint8_t *>(out));
+}
+
+int zgpu_inflate_batch_sizes_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, zgpu_inflate_item *d_items,
+                                    uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_batch_sizes_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, d_items, nfailed, st);
+}
+
+int zgpu_inflate_batch_packed_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                                     void *d_out, uint64_t out_cap, uint64_t *d_out_offsets, zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_batch_packed_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, checks, align, static_cast<uint8_t *>(d_out), out_cap, d_out_offsets,
+                                    d_items, total, nfailed, st, false);
+}
+
+int zgpu_inflate_batch_sizes_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, zgpu_inflate_item *items, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (int rc = batch_sizes_args(e, in, in_bytes, in_offsets, n, wrap, items)) return rc;
+    if (n == 0) return ZGPU_OK;
+    uint64_t *d_in_off, *d_out_off;
+    zgpu_inflate_item *d_items;
+    if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, 0, &d_in_off, &d_out_off, &d_items)) return rc;
+    if (int rc = inflate_batch_sizes_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, d_items, nfailed, e->stream)) return rc;
+    ZGPU_HIP_CHECK(hipMemcpy(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost));
+    return ZGPU_OK;
+}
+
+int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, uint32_t checks, uint32_t align,
+                                   void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_inflate_item *items, uint64_t *total, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (align == 0 || align > 256 || (align & (align - 1)) || (checks & ~3u) || !total || (n && !out_offsets) || (n && out_cap && !out))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_sizes_args(e, in, in_bytes, in_offsets, n, wrap, items)) return rc;
+    *total = 0;
+    if (n == 0) return ZGPU_OK;
+    uint64_t *d_in_off, *d_out_off;
+    zgpu_inflate_item *d_items;
+    if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, 0, &d_in_off, &d_out_off, &d_items)) return rc;
+    const int rc = inflate_batch_packed_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, checks, align, nullptr, out_cap, d_out_off, d_items, total, nfailed, e->stream, true);
+    if (rc != ZGPU_OK && rc != ZGPU_BUF_ERROR) return rc;
+    ZGPU_HIP_CHECK(hipMemcpy(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost));
+    ZGPU_HIP_CHECK(hipMemcpy(out_offsets, d_out_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (rc == ZGPU_BUF_ERROR) return rc;
+    bool dense = align == 1; // every item succeeded and no alignment leaves gaps between them
+    for (uint64_t k = 0; k < n && dense; k++) dense = items[k].code == ZGPU_OK;
+    return batch_copy_back(e, dense, 0, *total, out_offsets, items, n, static_cast<uint8_t *>(out));
+}
+#pragma GCC visibility pop
+}
