@@ -467,18 +467,16 @@ size_t ora_deflate_chunk_s(const uint8_t *in, size_t n, int level, int strategy,
     return ora_deflate_chunk_d(in, n, 0, level, strategy, pos0_matchable, is_last, out, cap, tokens, info);
 }
 
-/* The same with a preset dictionary (deflateSetDictionary, deflate.c:315-354): `in` holds the dictionary bytes the window
- * receives (at most MAX_DIST of them, at least MIN_MATCH) followed by the data, n counts both; every dictionary position
- * but the last two is in the hash chains before the first byte of data is looked at, and strstart = block_start = dict_len. */
-size_t ora_deflate_chunk_d(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, int pos0_matchable, int is_last,
-                           uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info)
+/* One chunk with the level's own row (row == NULL) or another one in its place; in[0 .. dict_len) is a preset dictionary (0: none). */
+static size_t chunk_with_row(const uint8_t *in, size_t n, size_t dict_len, int level, const level_cfg *row, int strategy, int pos0_matchable, int is_last,
+                             uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info)
 {
     if (dict_len > n || (dict_len != 0 && (dict_len < MINM || dict_len > MAXDIST || pos0_matchable))) return 0;
     if (n > ORA_CHUNK_MAX || level < 0 || level > 9 || strategy < 0 || strategy > ORA_FIXED) return 0;
     make_tables();
     enc *e = (enc *)calloc(1, sizeof(enc));
     if (!e) return 0;
-    e->in = in; e->n = (uint32_t)n; e->base = pos0_matchable ? 3u : 0u; e->level = level; e->strategy = strategy; e->cfg = &LEVELS[level];
+    e->in = in; e->n = (uint32_t)n; e->base = pos0_matchable ? 3u : 0u; e->level = level; e->strategy = strategy; e->cfg = row ? row : &LEVELS[level];
     e->bs.out = out; e->bs.cap = cap; e->tok_out = tokens; e->info = info; e->data_type = 2;
     if (info) memset(info, 0, sizeof(*info));
     new_block(e);
@@ -493,6 +491,26 @@ size_t ora_deflate_chunk_d(const uint8_t *in, size_t n, size_t dict_len, int lev
     size_t len = e->bs.overflow ? 0 : e->bs.len;
     free(e);
     return len;
+}
+
+/* The same with a preset dictionary (deflateSetDictionary, deflate.c:315-354): `in` holds the dictionary bytes the window
+ * receives (at most MAX_DIST of them, at least MIN_MATCH) followed by the data, n counts both; every dictionary position
+ * but the last two is in the hash chains before the first byte of data is looked at, and strstart = block_start = dict_len. */
+size_t ora_deflate_chunk_d(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, int pos0_matchable, int is_last,
+                           uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info)
+{
+    return chunk_with_row(in, n, dict_len, level, NULL, strategy, pos0_matchable, is_last, out, cap, tokens, info);
+}
+
+/* ora_deflate_chunk_s behind deflateTune (deflate.c:454-470): the four parameters replace the level's row, the level keeps its compress function
+ * (deflate_fast for 1-3, deflate_slow for 4-9; level 0 stores and has no use for them). */
+size_t ora_deflate_chunk_t(const uint8_t *in, size_t n, int level, int strategy, int good_length, int max_lazy, int nice_length, int max_chain,
+                           int pos0_matchable, int is_last, uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info)
+{
+    if (level < 1 || level > 9 || good_length < 0 || max_lazy < 0 || nice_length < 0 || max_chain < 1 ||
+        good_length > 0xffff || max_lazy > 0xffff || nice_length > 0xffff || max_chain > 0xffff) return 0;
+    const level_cfg row = {(uint16_t)good_length, (uint16_t)max_lazy, (uint16_t)nice_length, (uint16_t)max_chain, LEVELS[level].mode};
+    return chunk_with_row(in, n, 0, level, &row, strategy, pos0_matchable, is_last, out, cap, tokens, info);
 }
 
 size_t ora_deflate_bound(size_t n, size_t chunk_size)
@@ -664,11 +682,26 @@ size_t ora_deflate_cont(const uint8_t *in, size_t n, size_t dict_len, int level,
     return ora_deflate_cont_p(in, n, dict_len, level, strategy, cuts, kinds, NULL, NULL, ncuts, out, cap);
 }
 
+static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
+                       const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens);
+
 /* The same with deflateParams() (deflate.c:416-451) in front of some calls: plevel[k] / pstrategy[k] >= 0 are set before call k (k == ncuts: before the
  * Z_FINISH call; the arrays hold ncuts + 1 entries; -1: no change).  A change of the compress function flushes what has been read with Z_PARTIAL_FLUSH
  * first, any other change takes effect where the loop stands. */
 size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
                           const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap)
+{
+    return cont_run(in, n, dict_len, level, strategy, cuts, kinds, plevel, pstrategy, ncuts, out, cap, NULL, NULL);
+}
+
+/* What compress2() emits (no dictionary, one Z_FINISH call), with the token stream: tokens has room for n entries, *ntokens receives their number. */
+size_t ora_deflate_cont_tokens(const uint8_t *in, size_t n, int level, int strategy, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens)
+{
+    return cont_run(in, n, 0, level, strategy, NULL, NULL, NULL, NULL, 0, out, cap, tokens, ntokens);
+}
+
+static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
+                       const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens)
 {
     if (n >= 0xfff00000u || dict_len > n || (dict_len != 0 && (dict_len < MINM || dict_len > MAXDIST))) return 0;
     if (level < 0 || level > 9 || strategy < 0 || strategy > ORA_FIXED) return 0;
@@ -676,7 +709,7 @@ size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int leve
     enc *e = (enc *)calloc(1, sizeof(enc));
     if (!e) return 0;
     e->in = in; e->n = (uint32_t)dict_len; e->level = level; e->strategy = strategy; e->cfg = &LEVELS[level];
-    e->bs.out = out; e->bs.cap = cap; e->data_type = 2; e->last_eob = 8;
+    e->bs.out = out; e->bs.cap = cap; e->data_type = 2; e->last_eob = 8; e->tok_out = tokens;
     new_block(e);
     e->start = (uint32_t)dict_len; e->block_start = e->start;
     for (uint32_t q = 0; q + MINM <= e->start; q++) insert_at(e, q);
@@ -713,6 +746,7 @@ size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int leve
         }
     }
     const size_t len = e->bs.overflow ? 0 : e->bs.len;
+    if (ntokens) *ntokens = e->tok_total;
     free(e);
     return len;
 }

@@ -58,6 +58,10 @@ size_t ora_deflate_stream_s(const uint8_t *in, size_t n, int level, int strategy
 size_t ora_deflate_chunk_d(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, int pos0_matchable, int is_last,
                            uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info);
 
+/* ora_deflate_chunk_s with deflateTune's four parameters in place of the level's row (the level still chooses deflate_fast / deflate_slow). */
+size_t ora_deflate_chunk_t(const uint8_t *in, size_t n, int level, int strategy, int good_length, int max_lazy, int nice_length, int max_chain,
+                           int pos0_matchable, int is_last, uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info);
+
 size_t ora_deflate_chunk(const uint8_t *in, size_t n, int level, int pos0_matchable, int is_last,
                          uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info);
 
@@ -74,6 +78,9 @@ size_t ora_deflate_bound(size_t n, size_t chunk_size);
  * deflateSetDictionary puts into the window (<= 32506 bytes); n counts both.  What plain compress2() emits is ncuts == 0. */
 size_t ora_deflate_cont(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds, size_t ncuts,
                         uint8_t *out, size_t cap);
+
+/* ora_deflate_cont without cuts or dictionary (compress2), with the tokens: room for n of them, *ntokens = how many. */
+size_t ora_deflate_cont_tokens(const uint8_t *in, size_t n, int level, int strategy, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens);
 
 size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
                           const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap);

@@ -34,6 +34,9 @@ def lib():
         L.ora_deflate_chunk_s.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p]
         L.ora_deflate_chunk_s.restype = C.c_size_t
+        L.ora_deflate_chunk_t.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p]
+        L.ora_deflate_chunk_t.restype = C.c_size_t
         L.ora_deflate_chunk_d.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p]
         L.ora_deflate_chunk_d.restype = C.c_size_t
@@ -45,6 +48,8 @@ def lib():
         L.ora_deflate_cont.restype = C.c_size_t
         L.ora_deflate_cont_p.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.ora_deflate_cont_p.restype = C.c_size_t
+        L.ora_deflate_cont_tokens.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ora_deflate_cont_tokens.restype = C.c_size_t
         L.ora_deflate_bound.argtypes = [C.c_size_t, C.c_size_t]
         L.ora_deflate_bound.restype = C.c_size_t
         L.ora_adler32.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t]
@@ -79,14 +84,18 @@ def tree_counters() -> dict:
     return dict(repairs=c[0:3], overflow=c[3:6], longest=c[6:9], blocks=c[9:12], tie_static=c[12], tie_stored=c[13])
 
 
-def deflate_chunk(chunk: bytes, level: int, is_last: bool, pos0_matchable: bool = False, want_tokens=False, strategy: int = 0):
+def deflate_chunk(chunk: bytes, level: int, is_last: bool, pos0_matchable: bool = False, want_tokens=False, strategy: int = 0, tune=None):
+    """tune: (good_length, max_lazy, nice_length, max_chain) as deflateTune would set them in place of the level's row."""
     L = lib()
     cap = len(chunk) + 512
     out = C.create_string_buffer(cap)
     info = ChunkInfo()
     toks = (Token * max(len(chunk), 1))() if want_tokens else None
-    n = L.ora_deflate_chunk_s(chunk, len(chunk), level, strategy, int(pos0_matchable), int(is_last), out, cap,
-                            C.cast(toks, C.c_void_p) if want_tokens else None, C.byref(info))
+    tp = C.cast(toks, C.c_void_p) if want_tokens else None
+    if tune:
+        n = L.ora_deflate_chunk_t(chunk, len(chunk), level, strategy, *tune, int(pos0_matchable), int(is_last), out, cap, tp, C.byref(info))
+    else:
+        n = L.ora_deflate_chunk_s(chunk, len(chunk), level, strategy, int(pos0_matchable), int(is_last), out, cap, tp, C.byref(info))
     if n == 0:
         raise RuntimeError("oracle deflate_chunk failed")
     if want_tokens:
@@ -196,6 +205,20 @@ def deflate_cont(data: bytes, level: int, calls=(), strategy: int = 0, dictionar
     if n == 0:
         raise RuntimeError("oracle deflate_cont failed")
     return out.raw[:n]
+
+
+def deflate_cont_tokens(data: bytes, level: int, strategy: int = 0):
+    """(the continuous raw stream of compress2, its tokens as a numpy record array with the fields dist and lc)."""
+    import numpy as np
+    cap = len(data) + (len(data) >> 3) + 1024
+    out = C.create_string_buffer(cap)
+    toks = (Token * max(len(data), 1))()
+    nt = C.c_uint32(0)
+    n = lib().ora_deflate_cont_tokens(data, len(data), level, strategy, out, cap, C.cast(toks, C.c_void_p), C.byref(nt))
+    if n == 0:
+        raise RuntimeError("oracle deflate_cont_tokens failed")
+    t = np.frombuffer(toks, dtype=np.dtype([("dist", "<u2"), ("lc", "u1"), ("pad", "u1")]), count=nt.value)
+    return out.raw[:n], t.copy()
 
 
 def cont_stream(data: bytes, level: int, calls=(), wbits: int = 15, strategy: int = 0, dictionary: bytes = None) -> bytes:

@@ -681,6 +681,11 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
         };
         uint64_t cq = group(0);
         uint32_t k = 0;
+        // the quarter budget need not be a multiple of the four candidates of a step (deflateTune: max_chain 13 or 100 give 3 and 25): the snapshot is
+        // taken in front of candidate chainQ, at the top of step snapK or, for snapJ != 0, between two candidates of it.
+        // NOT settled: a quarter of 0 (max_chain 1..3).  The reference's count-down passes zero there and the search with a good match in hand is
+        // unbounded (walk_kernel: budget 0xffff); here the snapshot at k == 0 is empty and the walk ends after chainF candidates
+        const uint32_t snapK = chainQ & ~3u, snapJ = chainQ & 3u;
         for (;; k += 4) {
             if (amask == 0) break;
             if (k == chainQ) {
@@ -692,6 +697,10 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
             for (uint32_t j = 0; j < 4; j++) {
                 // no divergent control flow in the step: every lane reads (idle ones a harmless in-range address), masks decide
                 const uint32_t q = (uint32_t)(cq >> (48 - 16 * j)) & 0xffffu;
+                if (j != 0 && j == snapJ && k == snapK) { // (wave-uniform; entries on the ring are candidates below k + j)
+                    while (tail) fold(k + j);
+                    snapkey = key_seen; snap_taken = true;
+                }
                 uint32_t b0, b1;
                 lds_ld2bytes(boff + q, b0, b1);
                 amask &= mask_le_i32(thr, (int)q); // beyond MAX_DIST (or the NIL position): the chain ends here (deflate.c:1163)
