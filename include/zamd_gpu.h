@@ -196,6 +196,13 @@ typedef struct {
 } zgpu_cont_state;
 uint64_t zgpu_deflate_cont_bound(uint64_t buf_bytes); /* output capacity that is enough for one feed */
 #define ZGPU_CONT_HIST_WORDS 1032
+/* deflate_fast behind deflate_slow (deflateParams 4..9 -> 1..3): longest_match seeds its best length with prev_length (qcsrc/deflate.c:1035), which deflate_fast never
+ * sets and deflate_slow leaves at 0 when its last token was a match (:1630-1636).  zgpu_deflate_cont_last_match: 1 / 0 when the engine's last level 4..9 ZGPU_CONT_FLUSH feed
+ * ended on a match / a literal, -1 when it made no token (nothing changes).  While prev0 is set, level 1..3 feeds search as the reference does with prev_length 0: the
+ * first candidate taken must also have the byte in front of it equal to the byte in front of the string; byte_before is the stream's byte in front of the feed's
+ * buffer (-1: none; it can be a candidate's neighbour only behind Z_FULL_FLUSH).  The caller resets both (0, -1) after its feed, like the tuning. */
+int zgpu_deflate_cont_set_stale(zgpu_engine *e, int prev0, int byte_before);
+int zgpu_deflate_cont_last_match(zgpu_engine *e);
 int zgpu_deflate_cont_host(zgpu_engine *e, const void *hist, uint64_t hist_bytes, const void *in, uint64_t in_bytes, uint64_t check_from, const zgpu_deflate_params *p,
                            int mode, zgpu_cont_state *cs, uint32_t *carry_tok, uint32_t *hist_bits, const uint64_t *excl, uint32_t nexcl, void *out, uint64_t out_cap,
                            zgpu_deflate_result *res);

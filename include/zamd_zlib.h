@@ -139,9 +139,9 @@ int deflateEnd(z_streamp strm);
 int deflateReset(z_streamp strm);
 uLong deflateBound(z_streamp strm, uLong sourceLen);
 int deflateSetDictionary(z_streamp strm, const Bytef *dictionary, uInt dictLength); /* before the first input byte */
-int deflateParams(z_streamp strm, int level, int strategy);
+int deflateParams(z_streamp strm, int level, int strategy); /* Z_BUF_ERROR for want of output space: nothing has changed, call again with space */
 int deflateCopy(z_streamp dest, z_streamp source);
-int deflateTune(z_streamp strm, int good_length, int max_lazy, int nice_length, int max_chain);
+int deflateTune(z_streamp strm, int good_length, int max_lazy, int nice_length, int max_chain); /* Z_STREAM_ERROR in the middle of a level 1-3 stream */
 int deflatePrime(z_streamp strm, int bits, int value);
 int deflateSetHeader(z_streamp strm, gz_headerp head);
 

@@ -332,3 +332,20 @@ def inflate_raw_dict(data: bytes, outcap: int, dictionary: bytes = b""):
     res = (rc, out.raw[:s.total_out], s.total_in, s.msg.decode() if s.msg else None)
     L.inflateEnd(C.byref(s))
     return res
+
+
+def play_steps(case):
+    """A row of oracle/paramcases.py on the compiled reference: deflate / deflateParams / deflateTune / deflateReset steps, calls with a given avail_out.
+    Returns (codes, streams, bound) as paramcases.play does, every stream with `valid`: the reference's own inflate gives the input back from it and
+    accepts its trailer."""
+    from oracle import paramcases as PC
+    codes, streams, bound = PC.play(lib(), ZStream, case)
+    keep = case.dictionary[-32506:] if case.dictionary is not None and len(case.dictionary) >= 3 else b""
+    for k, st in enumerate(streams):
+        data = case.data if k == 0 else case.data2
+        if case.wbits < 0:
+            rc, back = inflate_raw_dict(st["z"], len(data) + 8, keep)[:2]
+        else:
+            rc, back = inflate_wbits(st["z"], case.wbits, len(data) + 8)[:2]
+        st["valid"] = rc == Z_STREAM_END and back == data
+    return codes, streams, bound

@@ -112,11 +112,33 @@ def deflate_stream(data: bytes, level: int, plan, in_step=None, out_step=None, w
     return out.raw[:opos], codes, dict(total_in=total_in, total_out=total_out, adler=adler, data_type=dtype, end_rc=end_rc)
 
 
-def inflate_stream(z: bytes, cap: int, in_step=None, out_step=None, flush=Z_NO_FLUSH, window_bits=15):
+def play_steps(case):
+    """A row of oracle/paramcases.py on the product: the calls of its steps in order (deflate, deflateParams, deflateTune, deflateReset, some with a given
+    avail_out), with the row's ZAMD_FEED_BYTES.  Returns what paramcases.play returns: (return codes, streams, deflateBound's answer)."""
+    from oracle import paramcases as PC
+    old = os.environ.get("ZAMD_FEED_BYTES")
+    if case.feed is None:
+        os.environ.pop("ZAMD_FEED_BYTES", None)
+    else:
+        os.environ["ZAMD_FEED_BYTES"] = str(case.feed)
+    try:
+        return PC.play(lib(), ZStream, case)
+    finally:
+        if old is None:
+            os.environ.pop("ZAMD_FEED_BYTES", None)
+        else:
+            os.environ["ZAMD_FEED_BYTES"] = old
+
+
+def inflate_stream(z: bytes, cap: int, in_step=None, out_step=None, flush=Z_NO_FLUSH, window_bits=15, dictionary=None):
     L = lib()
     s = ZStream()
     rc = L.inflateInit2_(C.byref(s), window_bits, b"1.2.3", C.sizeof(ZStream))
     assert rc == Z_OK, rc
+    if dictionary is not None:  # (a raw stream takes one at any time, inflate.c:1200-1236)
+        L.inflateSetDictionary.argtypes = [C.POINTER(ZStream), C.c_char_p, C.c_uint]
+        rc = L.inflateSetDictionary(C.byref(s), dictionary, len(dictionary))
+        assert rc == Z_OK, rc
     src = C.create_string_buffer(z, max(len(z), 1))
     out = C.create_string_buffer(max(cap, 1))
     ipos, opos, rc, calls = 0, 0, Z_OK, 0

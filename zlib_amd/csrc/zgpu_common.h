@@ -186,6 +186,8 @@ struct FastTiles {
     // what a tile's current results were made from: the history's bits it used [tile][kInsWords] and where it entered; kept[tile]: this round's parse stopped
     // early because nothing it could reach had changed -- its results stand, its buffers are not flipped (nullptr: every active tile is parsed to its end)
     uint32_t *used_ins; uint16_t *entry_used; uint8_t *kept;
+    uint32_t prev0; int before;                    // prev0: longest_match starts with best_len = 0 (a stale prev_length, deflate.c:1035): until a candidate has been taken, one is
+                                                   // taken only if the byte in front of it equals the byte in front of the string; before: the byte in front of the buffer (-1: none)
     uint32_t *stat;                                // (ZGPU_FAST_TRACE) [0] active tiles with the entry they had, [1] parses stopped early, [2] ... that met a different token first, [3] ... with changes out of reach of nothing
 };
 

@@ -67,6 +67,8 @@ struct zgpu_engine {
     DevBuf<uint8_t> par_ws;      // parallel LZ only (bytes): the larger of the two implementations' workspaces for par_cap chunks
     uint32_t par_cap = 0;
     int tuned = 0; uint32_t tune[4] = {0, 0, 0, 0}; // zgpu_deflate_set_tuning: good, lazy, nice, chain instead of the level's
+    int fast_prev0 = 0, before_buf = -1;            // zgpu_deflate_cont_set_stale: deflate_fast feeds search with prev_length 0; the byte in front of the feed's buffer (-1: none)
+    int last_tok_match = -1;                        // zgpu_deflate_cont_last_match: the last deflate_slow feed that ended a segment ended on a match (1), a literal (0), made no token (-1)
     uint64_t handed_on = 0; // (diagnostic: chunks handed on since the engine was made)
     DevBuf<uint32_t> hand_list; // chunks the lane-per-chunk loop handed on: [0] their number, [1..] their indices in the batch
     int geo_w = 15, geo_m = 8;   // zgpu_deflate_set_geometry: deflateInit2's windowBits and memLevel

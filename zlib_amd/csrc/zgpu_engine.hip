@@ -480,6 +480,7 @@ static int lz_tiles_fast(zgpu_engine *e, const ChunkGeom &g, const TileGeom &tg,
     if (keep < 0) { const char *v = getenv("ZGPU_FAST_KEEP"); keep = v ? atoi(v) : 1; }
     auto fill = [&](FastTiles &ft, uint32_t round, const uint32_t *lst) {
         ft.exit_cur = e->cf_exit_a; ft.exit_new = e->cf_exit_b; ft.ins0 = ft.ins0w = e->cf_ins0; ft.ins1 = ft.ins1w = e->cf_ins1; ft.cur = e->cf_cur; ft.active = act; ft.changed = e->cf_changed;
+        ft.prev0 = e->fast_prev0 != 0; ft.before = e->before_buf;
         ft.prev_ins = e->cf_prev; ft.round = round; ft.list = lst; ft.low_out = e->cf_hist; // (cf_hist: free until the feed's hand-over is put together)
         if (keep) { ft.used_ins = e->cf_used; ft.entry_used = e->cf_entry_used; ft.kept = e->cf_kept; }
         ft.dbg = trace && nb <= 65536 ? dbg : nullptr;
@@ -727,6 +728,13 @@ static int deflate_cont(zgpu_engine *e, const ContFeed &f, const LevelCfg &cfg, 
     sort_fault |= sort_fault2;
     if (sort_fault) { e->exact_sort = 1; return deflate_cont(e, f, cfg, cs, d_carry_in, res, st); } // (nothing of cs or of the incoming carry has been touched yet)
     if (hs.overflow) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    e->last_tok_match = -1;
+    if (cfg.slow && f.mode == ZGPU_CONT_FLUSH && hs.total != 0 && hs.total <= e->ct_T.cap) { // what deflate_slow leaves in prev_length: 0 behind a match (deflate.c:1630-1636)
+        uint32_t t = 0;
+        ZGPU_HIP_CHECK(hipMemcpyAsync(&t, e->ct_T + (hs.total - 1), 4, hipMemcpyDeviceToHost, st));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+        e->last_tok_match = (t >> 8) != 0;
+    }
     // where the stream stands now
     if (ntiles) {
         const uint64_t wb_last = w0 + (ntiles - 1) * kTileStride, lim = end - wb_last, h1_last = lim < kTileH1 ? lim : kTileH1;
@@ -880,6 +888,14 @@ int zgpu_deflate_set_tuning(zgpu_engine *e, int on, uint32_t good_length, uint32
     e->tuned = on != 0; e->tune[0] = good_length; e->tune[1] = max_lazy; e->tune[2] = nice_length; e->tune[3] = max_chain;
     return ZGPU_OK;
 }
+
+int zgpu_deflate_cont_set_stale(zgpu_engine *e, int prev0, int byte_before)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    e->fast_prev0 = prev0 != 0; e->before_buf = (byte_before >= 0 && byte_before <= 255) ? byte_before : -1;
+    return ZGPU_OK;
+}
+int zgpu_deflate_cont_last_match(zgpu_engine *e) { return e ? e->last_tok_match : -1; }
 
 // ZGPU_F_CONTINUOUS: the whole input as ONE stream, in one feed that finishes it
 static int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const zgpu_deflate_params *p, uint8_t *d_out, uint64_t out_cap, zgpu_deflate_result *res, hipStream_t st)

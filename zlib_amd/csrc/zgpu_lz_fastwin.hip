@@ -504,6 +504,13 @@ __global__ void __launch_bounds__(64) fastwin_tile_kernel(ChunkGeom g, TileGeom 
         }
     }
 
+    // a stale prev_length of 0 (ft.prev0): the first candidate a search takes needs the byte in front of it equal to the byte in front of the string (deflate.c:1047-1060 with
+    // best_len 0: scan_end1 = scan[-1]); position 0 of the buffer has ft.before in front of it, if anything
+    auto pre_eq = [&](uint32_t q, uint32_t at) -> bool {
+        if (!ft.prev0) return true;
+        const int bq = (wb + q) != 0 ? (int)src[(int)q - 1] : ft.before, bp = (wb + at) != 0 ? (int)src[(int)at - 1] : ft.before;
+        return bq >= 0 && bq == bp;
+    };
     uint32_t filled = 0;
     auto fill_to = [&](uint32_t need) {
         while (RING && filled < need) {
@@ -628,7 +635,7 @@ __global__ void __launch_bounds__(64) fastwin_tile_kernel(ChunkGeom g, TileGeom 
 #pragma unroll
                                     for (int t = 0; t < NW; t++) if (l == 8u * t) l += fw_diff8(cb[u][t] ^ own[t]);
                                     l = l < cmp_max ? l : cmp_max;
-                                    if (l > best) { best = l; mstart = q[u]; if (l >= ni) { stopped = true; term = l < cap; } }
+                                    if (l > best && (best >= kMinMatch || pre_eq(q[u], p))) { best = l; mstart = q[u]; if (l >= ni) { stopped = true; term = l < cap; } }
                                     if (nsel == (uint32_t)CHAIN) stopped = true;
                                 }
                             }
@@ -740,13 +747,14 @@ __global__ void __launch_bounds__(64) fastwin_tile_kernel(ChunkGeom g, TileGeom 
                         l = l < cap0 ? l : cap0;
                     }
                     uint64_t im = __builtin_amdgcn_ballot_w64(ins);
+                    const uint64_t pem = __builtin_amdgcn_ballot_w64(ins && pre_eq(q, p0));
                     while (im) {
                         const uint32_t f = (uint32_t)__builtin_ctzll(im); im &= im - 1;
                         const uint32_t qf = __builtin_amdgcn_readlane(q, f), lf = __builtin_amdgcn_readlane(l, f);
                         const int wq = (int)(qf + base);
                         if (first ? (wq <= 0 || (uint32_t)(w00 - wq) > kMaxDist || (p0 == nil_local && (uint32_t)(w00 - wq) == kMaxDist)) : wq <= limit0) { done = true; break; }
                         first = false;
-                        if (lf > best) { best = lf; ms0 = qf; if (lf >= ni0) { done = true; break; } }
+                        if (lf > best && (best >= kMinMatch || ((pem >> f) & 1ull))) { best = lf; ms0 = qf; if (lf >= ni0) { done = true; break; } }
                         if (--ch == 0) { done = true; break; }
                     }
                 }

@@ -277,6 +277,10 @@ struct internal_state {
     uint64_t checked;     /* s->adler / s->crc cover the data up to here; tail_adler / tail_crc the bytes from here to fed */
     uint32_t tail_adler, tail_crc;
     int flush_done;       /* the flush value of the last call that went through the engine */
+    int prev0;            /* deflate_slow's last flushed part ended on a match: it left prev_length at 0 (deflate.c:1630-1636), which deflate_fast never sets but longest_match
+                             starts from (:1035) -- levels 1-3 search with it until a level 4-9 part ends otherwise or deflateReset */
+    int before_byte; uint64_t before_pos; /* the stream's byte in front of position before_pos (-1: none), kept when the window dropped it: with prev0 a search looks one byte
+                             in front of a candidate, and behind Z_FULL_FLUSH the window's first position can be one */
     uint64_t st_str, st_blk, st_off; /* level 0: deflate_stored's strstart, block_start and the window's first position (deflate.c:1390-1439, fill_window) */
     /* inflate */
     int mode;         /* IN_* */
@@ -316,7 +320,7 @@ EXPORT uLong deflateBound(z_streamp strm, uLong sourceLen)
     if (!ours || strm->state->cont) { /* deflate.c:489-511 */
         const uLong destLen = sourceLen + ((sourceLen + 7) >> 3) + ((sourceLen + 63) >> 6) + 11;
         if (!ours || strm->state->w_bits != 15) return destLen; /* (hash_bits is 15 at memLevel 8) */
-        return sourceLen + (sourceLen >> 12) + (sourceLen >> 14) + 11; /* compressBound() */
+        return sourceLen + (sourceLen >> 12) + (sourceLen >> 14) + 11 + (gz ? 12 : 0); /* compressBound(), which counts the 6 bytes of a zlib wrapper: a gzip member has 18 (the reference does not add them) */
     }
     if (ours && (strm->state->w_bits != 15 || strm->state->mem_level != 8)) /* short blocks, and blocks a small window cannot store (the arithmetic of deflate.c:513-515 per chunk) */
         return (uLong)zgpu_deflate_bound_geometry(sourceLen, CHUNK, strm->state->w_bits, strm->state->mem_level) + 18;
@@ -387,10 +391,13 @@ EXPORT int deflateReset(z_streamp strm)
     strm->total_in = strm->total_out = 0; strm->msg = Z_NULL; strm->data_type = Z_UNKNOWN;
     s->in.len = 0; s->out.len = 0; s->out_pos = 0; s->trailer_done = 0; s->any_block = 0; s->dict.len = 0; s->dict_pending = 0; s->dprime = 0; /* (_tr_init, trees.c:401-402) */
     s->tuned = 0; /* lm_init: the level's own parameters again (deflate.c:380, 1009-1012) */
+    /* ... and with them the stream is one continuous stream again where deflateTune had sent a level 1-3 stream to the chunks (as deflateInit2_ derives it;
+     * a stream that was not continuous at deflateInit2_ has no carry and stays as it is) */
+    if (s->carry) s->cont = !chunks_mode() && s->w_bits == 15 && s->mem_level == 8 && !(s->strategy == Z_RLE && s->level >= 1 && s->level <= 3);
     s->status = s->wrap ? ST_INIT : ST_BUSY; s->last_flush = Z_NO_FLUSH;
     s->adler = 1; s->crc = 0; strm->adler = s->wrap == 2 ? 0 : 1; /* deflate.c:374-378 */
     s->win.len = 0; s->win_abs0 = 0; s->nexcl = 0; s->floor_pos = 0; s->fed = 0; s->checked = 0; s->tail_adler = 1; s->tail_crc = 0;
-    s->st_str = s->st_blk = s->st_off = 0;
+    s->st_str = s->st_blk = s->st_off = 0; s->prev0 = 0; s->before_byte = -1; s->before_pos = 0; /* lm_init: prev_length = MIN_MATCH-1 (deflate.c:1003-1005) */
     if (s->carry) memset(s->carry + ZGPU_CONT_CARRY_TOKENS, 0, ((size_t)ZGPU_CONT_HIST_WORDS + 8) * 4);
     memset(&s->cs, 0, sizeof s->cs); s->cs.data_type = 2; s->cs.first_block = 1; s->cs.last_eob = 8; /* _tr_init, trees.c:382-406 */
     return Z_OK;
@@ -443,10 +450,24 @@ EXPORT int deflateParams(z_streamp strm, int level, int strategy)
         /* deflate.c:436-448: a change of the compress FUNCTION (stored / fast / slow) flushes what has been read with Z_PARTIAL_FLUSH first; other changes
          * take effect where the loop stands -- here: where the parse of the next feed begins, after what is waiting has been parsed as far as it goes */
         const int f_old = s->level == 0 ? 0 : s->level <= 3 ? 1 : 2, f_new = level == 0 ? 0 : level <= 3 ? 1 : 2;
-        if (f_old != f_new && strm->total_in != 0) rc = deflate(strm, Z_PARTIAL_FLUSH);
-        else if ((level != s->level || strategy != s->strategy) && s->level != 0 && s->fed - s->cs.entry > 1024 && s->status != ST_FINISH) rc = cont_feed(strm, NULL, 0, ZGPU_CONT_MORE);
-        if (level >= 1 && level <= 3 && strategy == Z_RLE) return Z_STREAM_ERROR; /* (not served on a continuous stream) */
-        if (rc == Z_OK && f_old == 1 && f_new == 2) {
+        if (level >= 1 && level <= 3 && strategy == Z_RLE) return Z_STREAM_ERROR; /* (not served on a continuous stream: refused before anything is touched) */
+        if (f_old != f_new && strm->total_in != 0) {
+            /* The switch itself -- the chains handed from one function to the other, the positions below -- needs everything that was received parsed and
+             * its blocks closed.  That is so when the flush ran (Z_OK, even where part of its output is still waiting for space), and also when deflate()
+             * refused it with Z_BUF_ERROR only because the call in front was a flush and nothing is left to do (deflate.c:774-777): the reference
+             * changes the parameters all the same there, and so does this.  A switch that is refused for want of output space (avail_out == 0), or that
+             * found older output blocking the way, CHANGES NOTHING: the caller makes room and calls again (the contract of later zlib versions; 1.2.3
+             * sets the new level over unflushed input). */
+            rc = deflate(strm, Z_PARTIAL_FLUSH);
+            if (rc != Z_OK && rc != Z_BUF_ERROR) return rc;
+            if (rc == Z_BUF_ERROR && strm->avail_out == 0) return rc;
+            const int flushed = s->cs.entry == s->fed && (s->level == 0 ? s->st_blk == s->fed : s->cs.carry_ntok == 0);
+            if (!flushed) { strm->msg = ERR_MSG(Z_BUF_ERROR); return Z_BUF_ERROR; }
+        } else if ((level != s->level || strategy != s->strategy) && s->level != 0 && s->fed - s->cs.entry > 1024 && s->status != ST_FINISH) {
+            rc = cont_feed(strm, NULL, 0, ZGPU_CONT_MORE);
+            if (rc != Z_OK) return rc;
+        }
+        if (f_old == 1 && f_new == 2) {
             /* deflate_slow inherits deflate_fast's chains: the positions of the history that are NOT in them, as a list */
             const uint64_t w0 = s->cs.entry > 32512 ? s->cs.entry - 32512 : 0, base0 = w0 > s->win_abs0 ? w0 : s->win_abs0;
             s->nexcl = 0;
@@ -454,7 +475,7 @@ EXPORT int deflateParams(z_streamp strm, int level, int strategy)
                 const uint64_t j = q - base0;
                 if (!((s->carry[ZGPU_CONT_CARRY_TOKENS + (j >> 5)] >> (j & 31u)) & 1u) && !excl_add(s, q)) return Z_MEM_ERROR;
             }
-        } else if (rc == Z_OK && f_old == 2 && f_new == 1) {
+        } else if (f_old == 2 && f_new == 1) {
             /* ... and deflate_fast deflate_slow's: every position of the history but the listed ones */
             const uint64_t w0 = s->cs.entry > 32512 ? s->cs.entry - 32512 : 0, base0 = w0 > s->win_abs0 ? w0 : s->win_abs0;
             memset(s->carry + ZGPU_CONT_CARRY_TOKENS, 0, (size_t)ZGPU_CONT_HIST_WORDS * 4);
@@ -483,9 +504,11 @@ EXPORT int deflateTune(z_streamp strm, int good_length, int max_lazy, int nice_l
 {
     if (strm == Z_NULL || strm->state == Z_NULL || strm->state->kind != KIND_DEFLATE) return Z_STREAM_ERROR;
     struct internal_state *s = strm->state;
-    s->tuned = 1; s->tune[0] = (uint32_t)good_length; s->tune[1] = (uint32_t)max_lazy; s->tune[2] = (uint32_t)nice_length; s->tune[3] = (uint32_t)max_chain;
     /* deflate_fast with parameters of the caller's is served by the lane-per-chunk loop, i.e. in independent chunks: a stream that has not begun goes there
-     * (one that has keeps its parameters' level row: the engine refuses the feed) */
+     * (below); one continuous level 1-3 stream that has begun cannot follow, and the engine has no tuned deflate_fast for it: the call is refused and the
+     * stream goes on with its level's row (the reference accepts the call, deflate.c:454-470) */
+    if (s->cont && s->level >= 1 && s->level <= 3 && !(s->fed == 0 && !s->any_block && s->out.len == s->out_pos)) return Z_STREAM_ERROR;
+    s->tuned = 1; s->tune[0] = (uint32_t)good_length; s->tune[1] = (uint32_t)max_lazy; s->tune[2] = (uint32_t)nice_length; s->tune[3] = (uint32_t)max_chain;
     if (s->cont && s->level >= 1 && s->level <= 3 && s->fed == 0 && !s->any_block && s->out.len == s->out_pos) { s->cont = 0; }
     return Z_OK;
 }
@@ -603,7 +626,8 @@ static int stored_chunks(bytebuf *out, const uint8_t *src, size_t n, int final, 
  * Where the reference parses while the input trickles in, this library collects: a Z_NO_FLUSH call hands its bytes to the engine once ZAMD_FEED_BYTES
  * (default 16 MiB) of unparsed input have gathered; flushes and Z_FINISH hand over everything.  The stream's bytes do not depend on that.
  * Not modelled: deflateParams() between two levels of the same compress function while unflushed input is waiting (the reference switches the
- * parameters at the position its loop happens to stand at, deflate.c:436-448; here they change where the parse of the next feed begins), and a
+ * parameters at the position its loop happens to stand at, deflate.c:436-448; here they change where the parse of the next feed begins), deflateTune on a level 1-3 stream (refused once the
+ * stream has begun, served in chunks before), and a
  * Z_NO_FLUSH slice that ends 5 .. 261 bytes behind a position 32768 k + 65274 whose first chain candidate lies exactly 32506 bytes back (the
  * reference's window slides one loop iteration earlier there). */
 static int tail_put(struct internal_state *s, uint32_t value, int nbits) /* send_bits + bi_flush (trees.c:217-229, 1161-1173): whole bytes go out, fewer than 8 bits wait */
@@ -653,6 +677,11 @@ static int cont_rewindow(struct internal_state *s, uint64_t lo, const uint8_t *i
 {
     const uint64_t old_end = s->win_abs0 + s->win.len;
     if (lo < s->win_abs0) lo = s->win_abs0;
+    if (lo > s->win_abs0) { /* the byte in front of what stays */
+        const uint64_t b = lo - 1;
+        s->before_byte = b < old_end ? (int)s->win.p[b - s->win_abs0] : (b - old_end < n ? (int)in[b - old_end] : -1);
+        s->before_pos = lo;
+    }
     if (lo >= old_end) { /* everything that stays comes from `in` */
         const size_t skip = (size_t)(lo - old_end);
         s->win.len = 0; s->win_abs0 = lo;
@@ -674,18 +703,24 @@ static int cont_feed(z_streamp strm, const uint8_t *in, size_t n, int mode)
 {
     struct internal_state *s = strm->state;
     if (!engine_get()) { strm->msg = g_engine_err; return Z_MEM_ERROR; }
-    const uint64_t cap = zgpu_deflate_cont_bound(s->win.len + n) + 64;
+    /* (the bound of the bytes at hand, and of the block that is filling: up to ZGPU_CONT_CARRY_TOKENS tokens whose bytes may have left the window -- the
+     * engine's own staging allows four bytes for each) */
+    const uint64_t cap = zgpu_deflate_cont_bound(s->win.len + n) + 4u * ZGPU_CONT_CARRY_TOKENS + 64;
     if (!buf_reserve(&s->out, cap)) return Z_MEM_ERROR;
     zgpu_deflate_params p = {s->level, 0, s->wrap == 2 ? ZGPU_F_CRC32 : 0u, ZGPU_LZ_AUTO, s->strategy, 0};
     zgpu_deflate_result r;
     s->cs.abs0 = s->win_abs0;
     zgpu_engine *e = engine_checkout();
     zgpu_deflate_set_tuning(e, s->tuned, s->tune[0], s->tune[1], s->tune[2], s->tune[3]);
+    zgpu_deflate_cont_set_stale(e, s->prev0, s->before_pos == s->win_abs0 ? s->before_byte : -1);
     const int rc = zgpu_deflate_cont_host(e, s->win.p, s->win.len, in, n, s->checked - s->win_abs0, &p, mode, &s->cs, s->carry, s->carry + ZGPU_CONT_CARRY_TOKENS, s->excl, s->nexcl, s->out.p + s->out.len, cap, &r);
+    const int last_match = zgpu_deflate_cont_last_match(e); /* (a level 4-9 flush feed: what deflate_slow left in prev_length) */
+    zgpu_deflate_cont_set_stale(e, 0, -1);
     zgpu_deflate_set_tuning(e, 0, 0, 0, 0, 0);
     engine_checkin(e);
     if (rc != ZGPU_OK) { strm->msg = (char *)zgpu_engine_error(e); return rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : Z_STREAM_ERROR; }
     s->out.len += r.out_bytes;
+    if (last_match >= 0) s->prev0 = last_match;
     const uint64_t new_fed = s->fed + n, nck = new_fed - s->checked;
     if (nck) { s->adler = adler_join(s->adler, r.adler32, nck); if (s->wrap == 2) s->crc = crc_join(s->crc, r.crc32, nck); }
     s->checked = new_fed; s->tail_adler = 1; s->tail_crc = 0;
