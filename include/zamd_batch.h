@@ -45,6 +45,15 @@ int zamd_uncompress_sizes_batch(uLongf *destLen, const Bytef *const *source, con
 int zamd_uncompress_batch_packed(Bytef *dest, uLongf *destCap, uLong *destOffsets, const Bytef *const *source, const uLong *sourceLen, size_t n,
                                  int windowBits, int *status);
 
+/* The integrity test: are these streams intact?  No destination (gzip -t over many streams, a scrubber, a pack-file fsck).  windowBits as above.
+ * status[k] = what zamd_uncompress_batch gives item k with enough room: Z_OK, or Z_DATA_ERROR (damaged, truncated, in need of a dictionary, a wrong
+ * Adler-32, CRC-32 or ISIZE -- the trailers ARE checked here).  destLen (optional, may be NULL): destLen[k] = the decoded size, 0 for a failed item.
+ * Every item is decoded in full on the device, inside the workgroup's local memory, and its check values are taken there
+ * (zgpu_inflate_batch_verify_host): no room for any decoded byte is allocated anywhere.  Items of 512 MiB of input or more go one by one through
+ * inflate(), their output discarded.  The return value is the first failing item's code; Z_STREAM_ERROR for bad arguments touches nothing; n == 0
+ * is Z_OK and creates no engine. */
+int zamd_uncompress_verify_batch(uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status);
+
 /* crc32() / adler32() of many buffers, all items in one engine call (zgpu_checksum_batch_host).  crc[k] / adler[k] hold the running value on
  * entry, as the first argument of crc32() / adler32() (0 / 1 for a fresh one), and crc32(crc[k], buf[k], len[k]) / adler32(...) on return: the
  * items' own checksums come from the device, the running values are folded in on the host with crc32_combine / adler32_combine.  Items of any

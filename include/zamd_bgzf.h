@@ -30,6 +30,11 @@ int zamd_bgzf_compress(Bytef *dest, uLongf *destLen, const Bytef *source, uLong 
 /* the whole file; CRC-32 and ISIZE of every block are checked.  *destLen too small: Z_BUF_ERROR with *destLen = the size needed. */
 int zamd_bgzf_uncompress(Bytef *dest, uLongf *destLen, const Bytef *source, uLong sourceLen);
 
+/* bgzip -t: the whole file tested, nothing delivered -- every block decoded in the device's local memory, its CRC-32 and ISIZE compared there
+ * (zgpu_bgzf_verify_host); no room for the decoded bytes is allocated.  *decodedLen (optional): the decoded size, when the file is good.  Return codes
+ * are zamd_bgzf_uncompress's for the same file, without Z_BUF_ERROR; an empty file is Z_OK and creates no engine. */
+int zamd_bgzf_test(const Bytef *source, uLong sourceLen, uLongf *decodedLen);
+
 /* The block index, from the headers alone, on the host (no GPU needed): blocks[k] = where block k begins in the file and in the decoded data,
  * k = 0..n-1, and blocks[n] = (sourceLen, the decoded size).  cap: entries `blocks` has room for; when n + 1 > cap the call returns Z_BUF_ERROR with
  * *n set and nothing written (blocks may be NULL then).  *has_eof (optional): the file ends with the 28-byte end block.  Z_DATA_ERROR when the

@@ -392,6 +392,24 @@ int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_b
                                    uint32_t checks, uint32_t align, void *out, uint64_t out_cap, uint64_t *out_offsets, zgpu_inflate_item *items,
                                    uint64_t *total, uint64_t *nfailed);
 
+/* ---- batch integrity test: are these streams intact?  No destination ----
+ * Every item is decoded in full -- the same wrapper rules, the same deflate decoder, every match copied -- inside a 32 KiB ring in the workgroup's
+ * LDS, and where the decoder would flush a half of the ring to memory the bytes go into the item's running Adler-32 / CRC-32 instead.  The trailer is
+ * then compared as zgpu_inflate_batch_* compares it.  No decoded byte is written to device memory or read from it: the call needs the input, 144 bytes
+ * of scratch per item and nothing else, whatever the items decode to (gzip -t, unzip -t, bgzip -t, a scrubber, a pack-file fsck).
+ * Record k equals, field for field, the record zgpu_inflate_batch_* gives the same item with the same `checks` and an output range of exactly the
+ * right size: code (ZGPU_OK, ZGPU_DATA_ERROR or 2 for FDICT; ZGPU_BUF_ERROR cannot occur), msg ("incorrect data check", "incorrect length check", a
+ * trailer that does not fit as "segment ends inside a block", every decoder message), out_bytes, in_used, adler32 and crc32 (the check the wrapper
+ * needs is always computed, AUTO: both; the others as `checks` asks; one that is not computed reads 1 / 0).  A failed item has out_bytes = in_used = 0.
+ * What it does not promise: speed over a decode -- it does all the decoder's work but the stores; its claim is memory.  Arguments, limits (< 512 MiB
+ * compressed, < 4 GiB decoded per item, no preset dictionary, a multi-member gzip item is its first member), ZGPU_STREAM_ERROR for offsets that run
+ * backwards or leave the buffer, *nfailed and n == 0 are zgpu_inflate_batch_sizes_*'s.  One read-back, at the end; the device entry blocks until the
+ * records are in d_items. */
+int zgpu_inflate_batch_verify_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                                     uint32_t checks, zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream);
+int zgpu_inflate_batch_verify_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,
+                                   uint32_t checks, zgpu_inflate_item *items, uint64_t *nfailed);
+
 /* ---- BGZF decode (the encode side and the format: zgpu_bgzf_deflate_* above) ---- */
 /* The block index of a BGZF file in device memory, found on the device from the headers alone (zlib_amd/csrc/zgpu_bgzf.hip): d_in_offsets[0..n] =
  * where every block begins, entry n = in_bytes; d_out_offsets[0..n] = the exclusive sum of the blocks' ISIZE (entry n = *out_bytes).  Both arrays
@@ -415,6 +433,11 @@ int zgpu_bgzf_index_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, 
 int zgpu_bgzf_inflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, void *d_out, uint64_t out_cap, zgpu_inflate_item *d_items,
                              zgpu_inflate_result *res, void *hip_stream);
 int zgpu_bgzf_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, void *out, uint64_t out_cap, zgpu_inflate_item *items, zgpu_inflate_result *res);
+/* Test a whole BGZF file (bgzip -t): the index above, then every block as one item of zgpu_inflate_batch_verify_*.  There is no `out` and so no
+ * ZGPU_BUF_ERROR; everything else -- the return code, res->out_bytes (the sum of ISIZE), first_bad_chunk / error_code / error_msg, the verdict on a
+ * file whose blocks do not chain, the optional per-block records -- is what zgpu_bgzf_inflate_* says of the same file. */
+int zgpu_bgzf_verify_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, zgpu_inflate_item *d_items, zgpu_inflate_result *res, void *hip_stream);
+int zgpu_bgzf_verify_host(zgpu_engine *e, const void *in, uint64_t in_bytes, zgpu_inflate_item *items, zgpu_inflate_result *res);
 
 /* ---- multi-member gzip (RFC 1952 2.2: `cat a.gz b.gz`, logs appended to one .gz, .warc.gz), all members in one batch (zlib_amd/csrc/zgpu_gzip.hip) ----
  * out receives the members' decoded bytes, concatenated in file order.  Member k reads in[in_offsets[k] .. in_offsets[k+1]) and writes

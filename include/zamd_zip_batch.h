@@ -35,6 +35,8 @@ int zamd_zip_add_batch(zamd_zip *z, size_t n, const char *const *name, const voi
  * one.  u == NULL, or n > 0 with a null out, cap or result: ZAMD_ZIP_PARAMERROR, nothing touched.  n == 0: ZAMD_ZIP_OK. */
 int zamd_unzip_read_batch(zamd_unzip *u, const int *index, size_t n, void *const *out, const unsigned long *cap, long *result);
 
+/* unzip -t for n members at once, nothing delivered: zamd_zip_test.h */
+
 #ifdef __cplusplus
 }
 #endif

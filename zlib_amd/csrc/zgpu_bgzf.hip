@@ -197,11 +197,17 @@ __global__ void __launch_bounds__(1024) bgzf_order_kernel(const uint8_t *__restr
 
 // after the batch decode: a block that would decode to more than its ISIZE (the batch's "room too small") has a wrong ISIZE, and a block's deflate
 // data must end where its trailer begins.  first[0] = the first block that failed (start value: ~0)
-__global__ void __launch_bounds__(256) bgzf_verdict_kernel(zgpu_inflate_item *items, const uint64_t *__restrict__ in_off, uint64_t n, unsigned long long *first)
+// states (the integrity test, which knows no room): a block whose deflate data decoded, to more than the ISIZE the index read (out_off), gets the
+// record the decode gives it -- there the trailer is never looked at
+__global__ void __launch_bounds__(256) bgzf_verdict_kernel(zgpu_inflate_item *items, const uint64_t *__restrict__ in_off, uint64_t n, unsigned long long *first,
+                                                           const BatchItemState *__restrict__ states, const uint64_t *__restrict__ out_off)
 {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     zgpu_inflate_item it = items[k];
+    if (states && states[k].code == ZGPU_OK && states[k].out_bytes > out_off[k + 1] - out_off[k]) {
+        it = zgpu_inflate_item{}; it.code = ZGPU_DATA_ERROR; it.msg = kMsgLengthCheck; it.adler32 = 1; items[k] = it;
+    } else
     if (it.code == ZGPU_BUF_ERROR) { it.code = ZGPU_DATA_ERROR; it.msg = kMsgLengthCheck; it.out_bytes = 0; items[k] = it; }
     else if (it.code == ZGPU_OK && it.in_used != in_off[k + 1] - in_off[k]) { it.code = ZGPU_DATA_ERROR; it.msg = kMsgTrailing; it.out_bytes = 0; it.in_used = 0; items[k] = it; }
     if (it.code != ZGPU_OK) atomicMin(first, (unsigned long long)k);
@@ -263,8 +269,9 @@ static void bad_chain(zgpu_inflate_result *res)
 
 // index, then every block as one gzip item of the batch decoder.  d_out == nullptr: into e->stage_out, grown to what the index says.
 // d_items: optional (device); *items_out: where the records are.  A block that failed: ZGPU_DATA_ERROR, every other block's bytes are in place.
+// verify: the blocks go through the integrity test instead -- no destination at all, d_out and out_cap are not looked at
 static int bgzf_inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint8_t *d_out, uint64_t out_cap, zgpu_inflate_item *d_items, zgpu_inflate_result *res,
-                            uint64_t *nblocks_out, zgpu_inflate_item **items_out, hipStream_t st)
+                            uint64_t *nblocks_out, zgpu_inflate_item **items_out, hipStream_t st, bool verify = false)
 {
     uint64_t n = 0, total = 0;
     uint32_t eof = 0;
@@ -273,17 +280,20 @@ static int bgzf_inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_byt
     if (rc == ZGPU_DATA_ERROR) bad_chain(res);
     if (rc) return rc;
     res->out_bytes = total;
-    if (total > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    if (!verify && total > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
     if (n == 0) return ZGPU_OK;
-    if (!d_out) { if ((rc = ensure_stage(e, 0, total + 64))) return rc; d_out = e->stage_out; }
+    if (!verify && !d_out) { if ((rc = ensure_stage(e, 0, total + 64))) return rc; d_out = e->stage_out; }
     if (!d_items) { if ((rc = e->bz_items.reserve(e, n))) return rc; d_items = e->bz_items; }
     uint64_t nfailed = 0;
-    if ((rc = inflate_batch_run(e, d_in, in_bytes, e->bz_in_off, n, ZGPU_WRAP_GZIP, 0, d_out, total, e->bz_out_off, d_items, &nfailed, st))) return rc;
+    const BatchItemState *states = nullptr;
+    if (verify) rc = inflate_batch_verify_run(e, d_in, in_bytes, e->bz_in_off, n, ZGPU_WRAP_GZIP, 0, d_items, &nfailed, &states, st);
+    else rc = inflate_batch_run(e, d_in, in_bytes, e->bz_in_off, n, ZGPU_WRAP_GZIP, 0, d_out, total, e->bz_out_off, d_items, &nfailed, st);
+    if (rc) return rc;
     *nblocks_out = n; *items_out = d_items;
     unsigned long long *first = reinterpret_cast<unsigned long long *>(e->bz_res.p); // (the index's record has been read)
     unsigned long long h_first = ~0ull;
     ZGPU_HIP_CHECK(hipMemsetAsync(first, 0xff, 8, st));
-    hipLaunchKernelGGL(bgzf_verdict_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_items, e->bz_in_off.p, n, first);
+    hipLaunchKernelGGL(bgzf_verdict_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_items, e->bz_in_off.p, n, first, states, e->bz_out_off.p);
     ZGPU_HIP_CHECK(hipGetLastError());
     ZGPU_HIP_CHECK(hipMemcpyAsync(&h_first, first, 8, hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
@@ -361,6 +371,38 @@ int zgpu_bgzf_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, vo
     if ((rc == ZGPU_OK || rc == ZGPU_DATA_ERROR) && n) { // (n: the decode ran)
         if (res->out_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost, st));
         if (items) ZGPU_HIP_CHECK(hipMemcpyAsync(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost, st));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return rc;
+}
+
+int zgpu_bgzf_verify_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, zgpu_inflate_item *d_items, zgpu_inflate_result *res, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (!res || (!d_in && in_bytes)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
+    inflate_result_init(res);
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    uint64_t n = 0;
+    zgpu_inflate_item *where = nullptr;
+    return bgzf_inflate_run(e, static_cast<const uint8_t *>(d_in), in_bytes, nullptr, 0, d_items, res, &n, &where, st, true);
+}
+
+int zgpu_bgzf_verify_host(zgpu_engine *e, const void *in, uint64_t in_bytes, zgpu_inflate_item *items, zgpu_inflate_result *res)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (!res || (!in && in_bytes)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
+    inflate_result_init(res);
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    int rc = ensure_stage(e, in_bytes + 64, 0);
+    if (rc) return rc;
+    if (in_bytes) ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in, in, in_bytes, hipMemcpyHostToDevice, st));
+    uint64_t n = 0;
+    zgpu_inflate_item *d_items = nullptr;
+    rc = bgzf_inflate_run(e, e->stage_in, in_bytes, nullptr, 0, nullptr, res, &n, &d_items, st, true);
+    if ((rc == ZGPU_OK || rc == ZGPU_DATA_ERROR) && n && items) { // (n: the test ran)
+        ZGPU_HIP_CHECK(hipMemcpyAsync(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost, st));
         ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     }
     return rc;

@@ -331,12 +331,110 @@ __host__ __device__ inline uint32_t crc_xpow8n(uint64_t n) // x^(8n) mod P: the 
 // CRC of X||Y from the finished CRCs of X and Y and |Y| (what crc32_combine computes with its 32x32 bit matrices)
 __host__ __device__ inline uint32_t crc_join(uint32_t cx, uint32_t cy, uint32_t op_leny) { return crc_mulmod(op_leny, cx) ^ cy; }
 // Adler of X||Y from Adler(X) = (ax, bx), Adler(Y) = (ay, by), |Y| = ny:  a = ax + ay - 1,  b = bx + by + ny (ax - 1)
-__device__ inline void adler_join(uint32_t &ax, uint32_t &bx, uint32_t ay, uint32_t by, uint64_t ny)
+__host__ __device__ inline void adler_join(uint32_t &ax, uint32_t &bx, uint32_t ay, uint32_t by, uint64_t ny)
 {
     uint64_t rem = ny % kAdlerBase;
     uint64_t a = ((uint64_t)ax + ay + kAdlerBase - 1) % kAdlerBase;
     uint64_t b = ((uint64_t)bx + by + rem * ((ax + kAdlerBase - 1) % kAdlerBase)) % kAdlerBase;
     ax = (uint32_t)a; bx = (uint32_t)b;
+}
+
+// ---- the fold of the verifying decoder (inflate_kernel_t<..., VERIFY>, zgpu_inflate.hip): the check values of a stream taken piece by piece, a piece
+// being what the decoder would flush -- at most kFoldMax bytes that start at a 16-byte boundary.  A piece is folded by 64 lanes: Adler-32 from the lanes'
+// sums over 16-byte vectors dealt round robin, CRC-32 from 64 end-aligned slices joined across the lanes; both are then joined onto the running values.
+// Everything here is host-callable, and tests/tools/fold_model.cpp folds byte strings through these same functions on the CPU.
+constexpr uint32_t kFoldMax = 16384, kFoldLanes = 64;
+// The CRC lookup: slicing by four over NIBBLES, eight tables of 16 words.  tab[2k][v] is the CRC register after the byte v (a low nibble) and k more
+// zero bytes, tab[2k + 1][v] the same for the byte v << 4; the register is linear in the byte, so byte b's entry is the XOR of its two nibbles'.
+constexpr uint32_t kCrcNibWords = 128;
+__host__ __device__ inline uint32_t crc_nib_entry(uint32_t e) // word e of the eight tables
+{
+    const uint32_t t = e >> 4, v = e & 15u, steps = 8 * ((t >> 1) + 1);
+    uint32_t r = (t & 1u) ? v << 4 : v;
+    for (uint32_t k = 0; k < steps; k++) r = (r & 1u) ? (r >> 1) ^ kCrcPoly : r >> 1;
+    return r;
+}
+__host__ __device__ inline uint32_t crc_nib_byte(const uint32_t *tab, uint32_t crc, uint32_t b)
+{
+    const uint32_t x = (crc ^ b) & 255u;
+    return tab[x & 15u] ^ tab[16 + (x >> 4)] ^ (crc >> 8);
+}
+// the finished CRC-32 of p[0, n) (0 for n == 0): bytes up to a word boundary, words four bytes a step (eight lookups that do not wait for each other), the
+// bytes behind.  Bounded by n
+__host__ __device__ inline uint32_t crc_nib_span(const uint32_t *tab, const uint8_t *p, uint32_t n)
+{
+    uint32_t crc = 0xffffffffu;
+    while (n && (reinterpret_cast<uintptr_t>(p) & 3)) { crc = crc_nib_byte(tab, crc, *p++); n--; }
+    for (; n >= 4; n -= 4, p += 4) {
+        uint32_t w;
+        __builtin_memcpy(&w, __builtin_assume_aligned(p, 4), 4);
+        const uint32_t x = crc ^ w;
+        crc = tab[96 + (x & 15u)] ^ tab[112 + ((x >> 4) & 15u)] ^ tab[64 + ((x >> 8) & 15u)] ^ tab[80 + ((x >> 12) & 15u)] ^
+              tab[32 + ((x >> 16) & 15u)] ^ tab[48 + ((x >> 20) & 15u)] ^ tab[(x >> 24) & 15u] ^ tab[16 + (x >> 28)];
+    }
+    for (; n; n--) crc = crc_nib_byte(tab, crc, *p++);
+    return crc ^ 0xffffffffu;
+}
+// x^(8 * 2^k) mod P, k = 0 .. 14: the operator "append 2^k bytes" for every power of two up to a piece (a compile-time table: a full piece needs no
+// multiplication for its operators, a ragged one one per set bit of its length)
+struct CrcPow2 { uint32_t v[15]; };
+constexpr uint32_t crc_mulmod_c(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (uint32_t m = 0x80000000u; m; m >>= 1) { if (a & m) p ^= b; b = (b & 1u) ? (b >> 1) ^ kCrcPoly : b >> 1; }
+    return p;
+}
+constexpr CrcPow2 make_crc_pow2()
+{
+    CrcPow2 t{};
+    uint32_t sq = 0x00800000u; // x^8
+    for (int k = 0; k < 15; k++) { t.v[k] = sq; sq = crc_mulmod_c(sq, sq); }
+    return t;
+}
+__host__ __device__ inline uint32_t crc_pow2(uint32_t k) { constexpr CrcPow2 t = make_crc_pow2(); return t.v[k]; }
+__host__ __device__ inline uint32_t fold_xpow8n(uint32_t n) // x^(8n) mod P for n <= kFoldMax
+{
+    uint32_t r = 0x80000000u;
+    for (int k = 0; k < 15; k++) if ((n >> k) & 1u) r = r == 0x80000000u ? crc_pow2(k) : crc_mulmod(crc_pow2(k), r);
+    return r;
+}
+// The slices of a piece of n bytes: lane t has [lo, hi), all of L bytes but the first that is not empty; L is the power of two at or above n / 64, so that
+// every operator of the join across the lanes is an entry of crc_pow2 (lg = log2 L).  Lanes in front of the piece's first byte have nothing: their CRC is 0
+__host__ __device__ inline void fold_slice(uint32_t n, uint32_t t, uint32_t &lg, uint32_t &lo, uint32_t &hi)
+{
+    lg = 0;
+    while ((kFoldLanes << lg) < n) lg++; // at most 8 steps
+    const int32_t h = (int32_t)n - (int32_t)((kFoldLanes - 1 - t) << lg), l = h - (int32_t)(1u << lg);
+    hi = h > 0 ? (uint32_t)h : 0u; lo = l > 0 ? (uint32_t)l : 0u;
+}
+// one step of the join across the lanes: lanes whose number is a multiple of 2s take the lane s to their right behind them (that one covers s slices)
+__host__ __device__ inline uint32_t fold_crc_step(uint32_t mine, uint32_t right, uint32_t lane, uint32_t s, uint32_t lg, uint32_t step)
+{
+    return (lane & (2 * s - 1)) == 0 ? crc_join(mine, right, crc_pow2(lg + step)) : mine;
+}
+// lane t's share of the Adler sums of a piece p[0, n), p 16-byte aligned: byte i counts (n - i) times in s2.  Vectors t, t + 64, ..., then the bytes
+// behind the last whole vector.  64-bit sums: a piece of 0xFF bytes brings s2 to 255 * 16384 * 16385 / 2 = 3.4e10
+__host__ __device__ inline void fold_adler_lane(const uint8_t *p, uint32_t n, uint32_t t, uint64_t &s1, uint64_t &s2)
+{
+    s1 = 0; s2 = 0;
+    const uint32_t nvec = n >> 4;
+    for (uint32_t j = t; j < nvec; j += kFoldLanes) {
+        uint32_t w[4];
+        __builtin_memcpy(w, __builtin_assume_aligned(p + (j << 4), 16), 16);
+        uint32_t t1 = 0, t2 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+#pragma unroll
+            for (int m = 0; m < 4; m++) { const uint32_t b = (w[k] >> (8 * m)) & 255u; t1 += b; t2 += b * (uint32_t)(k * 4 + m); }
+        }
+        s1 += t1; s2 += (uint64_t)(n - (j << 4)) * t1 - t2; // (n - 16 j >= 16 > any weight in t2)
+    }
+    for (uint32_t i = (nvec << 4) + t; i < n; i += kFoldLanes) { const uint32_t b = p[i]; s1 += b; s2 += (uint64_t)(n - i) * b; }
+}
+// the running Adler-32 (a, b) behind a piece of n bytes whose lanes' sums add up to s1, s2
+__host__ __device__ inline void fold_adler_join(uint32_t &a, uint32_t &b, uint64_t s1, uint64_t s2, uint32_t n)
+{
+    adler_join(a, b, (uint32_t)((1 + s1) % kAdlerBase), (uint32_t)((n + s2) % kAdlerBase), n);
 }
 
 #define ZGPU_HIP_CHECK(expr)                                                                     \

@@ -212,8 +212,10 @@ struct InfLaunch {
     uint64_t last_chunk = ~0ull; uint32_t chunk_size = kWholeStream; ChunkMeta *meta = nullptr;
     const uint8_t *dict = nullptr; uint32_t dict_len = 0; uint32_t stream_mode = 1;
 };
-enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces }; // kInfPieces: always the 32 KiB ring of 16-bit symbols; kInfSizes: no ring at all
-constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes or kInfPieces launch: the kind fixes the ring, the launcher does not look at the value
+// kInfPieces: always the 32 KiB ring of 16-bit symbols; kInfSizes: no ring at all; kInfVerify: the 32 KiB ring and no destination -- `out` is not
+// used, `out_cap` carries the checks to compute (bit 0 Adler-32, bit 1 CRC-32) and `meta` takes one record per item: out_bytes, adler_a, adler_b, crc
+enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify };
+constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes, kInfPieces or kInfVerify launch: the kind fixes the ring, the launcher does not look at the value
 int inflate_ring_kb(); // ZGPU_INF_RING_KB, read at EVERY call (the tests run the same streams through all three): 8, 16, anything else 32; not set: the build's default
 void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const SpecArgs &sp, hipStream_t st);
 int output_checksums(zgpu_engine *e, const uint8_t *d_out, uint64_t nbytes, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st);
@@ -228,6 +230,8 @@ int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
                              const BatchItemState **states, hipStream_t st);
 int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, uint64_t *nfailed,
                             hipStream_t st);
+int inflate_batch_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, zgpu_inflate_item *d_items,
+                             uint64_t *nfailed, const BatchItemState **states, hipStream_t st);
 int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint32_t align,
                              uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *total, uint64_t *nfailed, hipStream_t st,
                              bool stage_out = false);

@@ -51,6 +51,28 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_inf_time(unsig
 #define INF_N(x) do { } while (0)
 #endif
 
+// VERIFY's fold of one piece (see inflate_kernel_t): p[0, n), n <= kFoldMax, into the running Adler-32 halves and CRC-32.  The writer wave, all 64 lanes;
+// one copy of the code for the kernel's three flushes.  Every loop is bounded by n / 64 or is one of six steps across the lanes.
+struct FoldRun { uint32_t a, b, crc; }; // (by value both ways: the running values stay in registers)
+__device__ __noinline__ FoldRun verify_fold(const uint8_t *p, uint32_t n, const uint32_t *crc_nib, uint32_t lane, uint32_t do_adler, uint32_t do_crc, FoldRun run)
+{
+    if (do_adler) {
+        uint64_t s1, s2;
+        fold_adler_lane(p, n, lane, s1, s2);
+        for (int sh = 32; sh > 0; sh >>= 1) { s1 += __shfl_xor(s1, sh); s2 += __shfl_xor(s2, sh); }
+        fold_adler_join(run.a, run.b, s1, s2, n);
+    }
+    if (do_crc) {
+        uint32_t lg, slo, shi;
+        fold_slice(n, lane, lg, slo, shi);
+        uint32_t crc = crc_nib_span(crc_nib, p + slo, shi - slo);
+#pragma unroll 1
+        for (uint32_t st = 0; st < 6; st++) crc = fold_crc_step(crc, (uint32_t)__shfl_down((int)crc, 1u << st), lane, 1u << st, lg, st);
+        run.crc = crc_join(run.crc, (uint32_t)__builtin_amdgcn_readfirstlane((int)crc), fold_xpow8n(n));
+    }
+    return run;
+}
+
 // One workgroup of two waves per segment.  Wave 0 (the reader) owns the bit stream: block headers, code tables and the
 // token decode; it never needs to know how many bytes came out so far.  Wave 1 (the writer) owns the output: the 32 KiB
 // ring in LDS, match copies, flushes to the destination, and the limits that depend on the output position (distance too
@@ -82,15 +104,28 @@ __device__ inline void block_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0
 // CRC-32 and compares no ISIZE, so its verdict is the decoder's verdict minus the trailer checks.
 // Termination: SIZES adds no loop.  The block loop and the token loop are the reader's, and every iteration of either consumes input bits or ends with
 // an error (or with `stop`, which the counting sets together with its error); the counting itself is straight-line code.
-template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false>
+// VERIFY (zgpu_inflate_batch_verify_*, BATCH only, the 32 KiB ring): the integrity test.  The reader is the decoder's, and so is everything the writer does
+// inside the ring -- literals, match copies, stored blocks half by half; every match finds its source there.  What it does not have is a destination: where
+// the decoder would flush ring bytes [flushed, upto) to memory (half a ring, or the tail at the end, never wrapping) the writer wave folds them into the
+// running Adler-32 and CRC-32 it keeps in registers (zgpu_common.h, "the fold"), whichever of the two `out_cap` asks for (bit 0 Adler-32, bit 1 CRC-32:
+// there is no capacity to pass).  No byte of output goes to global memory or comes from it, `out` and the output half of the segment table are never
+// touched, and the only limit on the output position is the 4 GiB of an item.  status[] is the BATCH decoder's for a range of exactly the item's size;
+// meta[c] (one record per ITEM here) takes the two check values.
+// The CRC lookup: eight 16-word nibble tables in LDS behind the decoder's own layout (512 bytes, built by the writer wave before its first token), so
+// the workgroup stays within the 40448 bytes that let four share a CU.  A lookup's 64 lanes go to one table, 16 consecutive words: no two entries share
+// a bank.  The alternatives -- a table in lane registers read by cross-lane shuffles, a 1 KiB byte table (three workgroups a CU), the 4 KiB
+// slicing-by-4 table of zgpu_checksum.hip (three as well) -- have not been measured against it.
+// Termination: VERIFY adds the fold's loops, each bounded by the bytes of one flush (16 KiB), and a table build of two words per lane.
+template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false, bool VERIFY = false>
 __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES : (!SPEC && RING <= 8192) ? 5 : 4) inflate_kernel_t(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ offsets,
                                                         uint64_t chunk0, uint32_t nchunks, uint64_t last_chunk, uint32_t chunk_size_arg,
                                                         uint8_t *__restrict__ out, uint64_t out_cap, InfStatus *status, ChunkMeta *meta,
                                                         const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t stream_mode, SpecArgs sp)
 {
     typedef typename std::conditional<SPEC, uint16_t, uint8_t>::type ring_t;
-    typedef typename std::conditional<SIZES, InflateLdsSizes, InflateLdsT<ring_t, RING>>::type Lds;
+    typedef typename std::conditional<SIZES, InflateLdsSizes, typename std::conditional<VERIFY, InflateLdsVerify, InflateLdsT<ring_t, RING>>::type>::type Lds;
     static_assert(!SIZES || (BATCH && !SPEC), "the sizing pass serves batch items");
+    static_assert(!VERIFY || (BATCH && !SPEC && !SIZES && RING == 32768), "the integrity test serves batch items, every match from the ring");
     constexpr uint32_t kOutRing = RING, kOutHalf = RING / 2; // (this kernel's ring, not the file's default)
     constexpr bool FAR = RING < 32768;
     static_assert(!(SPEC && FAR) && RING >= 4096 && (RING & (RING - 1)) == 0, "ring size");
@@ -423,8 +458,13 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     for (uint32_t i = lane; i < reach; i += 64) L.out[(kOutRing - reach + i) & (kOutRing - 1)] = dict[i];
     uint32_t flushed = 0; // bytes already copied from the LDS ring to the destination (a multiple of kOutHalf until the end)
     bool nofit = false;   // direct placement: the destination ended before the chunk did
-    uint8_t *dst = BATCH ? out + offsets[4 * gc + 2] : compact ? out + (uint64_t)c * kChunkMax : whole ? out : out + gc * (uint64_t)chunk_size;
-    const uint64_t dst_room = BATCH ? offsets[4 * gc + 3] - offsets[4 * gc + 2] : SPEC ? ~0ull : compact ? kChunkMax : whole ? out_cap : (out_cap > gc * (uint64_t)chunk_size ? out_cap - gc * (uint64_t)chunk_size : 0);
+    FoldRun run{1, 0, 0}; // VERIFY: Adler-32 (halves) and CRC-32 of output bytes [0, flushed)
+    const uint32_t do_adler = VERIFY ? (uint32_t)out_cap & 1u : 0u, do_crc = VERIFY ? (uint32_t)out_cap & 2u : 0u;
+    if constexpr (VERIFY) {
+        if (do_crc) for (uint32_t i = lane; i < kCrcNibWords; i += 64) L.crc_nib[i] = crc_nib_entry(i);
+    }
+    uint8_t *dst = VERIFY ? nullptr : BATCH ? out + offsets[4 * gc + 2] : compact ? out + (uint64_t)c * kChunkMax : whole ? out : out + gc * (uint64_t)chunk_size;
+    const uint64_t dst_room = VERIFY ? ~0ull : BATCH ? offsets[4 * gc + 3] - offsets[4 * gc + 2] : SPEC ? ~0ull : compact ? kChunkMax : whole ? out_cap : (out_cap > gc * (uint64_t)chunk_size ? out_cap - gc * (uint64_t)chunk_size : 0);
     // copy a match of `len` bytes at distance `dist` to output position `at`; a distance shorter than the length repeats its
     // pattern (byte-sequential semantics of inffast.c:246-259).  The ring holds the last 32 KiB: a read at the full distance
     // 32768 hits the slot its own lane is about to write.
@@ -454,6 +494,11 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
         INF_T(11);
         wave_sync();
         uint32_t nbytes = upto - flushed;
+        if constexpr (VERIFY) { // the fold: ring bytes [flushed, upto) into the running check values (flushed is a multiple of kOutHalf: 16-byte aligned)
+            run = verify_fold(reinterpret_cast<const uint8_t *>(L.out) + (flushed & (kOutRing - 1)), nbytes, L.crc_nib, lane, do_adler, do_crc, run);
+            flushed = upto;
+            return;
+        }
         if (SPEC) { // the next page of the pool (flushed is a multiple of kOutHalf: the page's index within the segment)
             uint32_t page = 0;
             if (lane == 0) page = atomicAdd(sp.page_count, 1u);
@@ -641,7 +686,8 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
         t_acc[6] = n_mat;
         for (int i_ = 0; i_ < 16; i_++) if (t_acc[i_]) atomicAdd(&inf_time[i_], t_acc[i_]);
 #endif
-        if (meta) { meta[c].out_bytes = err ? 0 : o; meta[c].ntok = 0; meta[c].adler_a = 1; meta[c].adler_b = 0; meta[c].in_bytes = 0; meta[c].data_type = 2; }
+        if constexpr (VERIFY) { meta[c].out_bytes = err ? 0 : o; meta[c].adler_a = run.a; meta[c].adler_b = run.b; meta[c].crc = run.crc; }
+        else if (meta) { meta[c].out_bytes = err ? 0 : o; meta[c].ntok = 0; meta[c].adler_a = 1; meta[c].adler_b = 0; meta[c].in_bytes = 0; meta[c].data_type = 2; }
     }
     } // !SIZES
 }
@@ -711,6 +757,7 @@ void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const 
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 16384>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds16);
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 8192>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds8);
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsSpec));
+        hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 32768, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsVerify));
         opt_in = true;
     }
     // (one pointer type for all instantiations: __launch_bounds__ is no part of the type, so the 64-thread sizing kernel goes through it on purpose; `threads` counts)
@@ -720,6 +767,7 @@ void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const 
     };
     if (kind == kInfPieces) go(inflate_kernel_t<true>, 128, sizeof(InflateLdsSpec));
     else if (kind == kInfSizes) go(inflate_kernel_t<false, ZGPU_INF_RING, true, true>, 64, sizeof(InflateLdsSizes));
+    else if (kind == kInfVerify) go(inflate_kernel_t<false, 32768, true, false, true>, 128, sizeof(InflateLdsVerify));
     else if (kind == kInfBatch) {
         if (ring_kb == 8) go(inflate_kernel_t<false, 8192, true>, 128, kLds8);
         else if (ring_kb == 16) go(inflate_kernel_t<false, 16384, true>, 128, kLds16);

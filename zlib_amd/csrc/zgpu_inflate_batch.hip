@@ -1,7 +1,8 @@
 // zgpu_inflate_batch.hip -- batch of independent streams (zgpu_inflate_batch_*): item k = in[in_off[k], in_off[k+1]) -> out[out_off[k], out_off[k+1]), every
 // item a stream of its own with its own verdict.  The header kernel reads each item's wrapper (qcsrc/inflate.c:589-760), the decoder (zgpu_inflate.hip) runs
 // in BATCH mode (one workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and
-// the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.
+// the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.  The sizing pass and the integrity test (further down) run
+// the same header kernel and the decoder in its SIZES / VERIFY mode: neither has a destination, the second still has its trailers compared.
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
 #include "../../include/zamd_gpu.h"
@@ -125,23 +126,28 @@ __global__ void __launch_bounds__(256) batch_piece_fill_kernel(const BatchItemSt
 
 // The scratch of a batch call, one allocation (the engine's inf_status).  The sizing pass has the prefix; the decode adds the pieces of the output its
 // checks read.  A packed call runs one behind the other over the same items: the decode takes the scratch over, its prefix lies where the sizing pass's lay.
+// The integrity test has the prefix and, right behind it, one checksum record per item (no piece table: its pieces never leave the workgroup).
 struct BatchScratch {
     uint64_t *seg; BatchItemState *items; InfStatus *status;
     unsigned long long *cnt; // 256 bytes: [0] pieces (a packed call: the layout's total), [1] failed items, [2] bad offsets
-    uint64_t *tab; uint32_t *map; ChunkMeta *meta; // decode only: the piece boundaries, the piece list, the pieces' checksums
+    uint64_t *tab; uint32_t *map; ChunkMeta *meta; // decode only: the piece boundaries, the piece list, the pieces' checksums (verify: meta alone, the items' checksums)
 };
-static int batch_scratch(zgpu_engine *e, uint64_t n, bool decode, uint64_t max_pieces, BatchScratch *s) // decode false: the sizing pass, the prefix alone
+enum BatchScratchKind { kScratchSizes, kScratchDecode, kScratchVerify };
+static int batch_scratch(zgpu_engine *e, uint64_t n, BatchScratchKind kind, uint64_t max_pieces, BatchScratch *s)
 {
     Carve at;
+    const bool decode = kind == kScratchDecode;
     const size_t o_seg = at(n * 32), o_items = at(n * sizeof(BatchItemState)), o_status = at(n * sizeof(InfStatus)), o_cnt = at(256);
     size_t o_tab = 0, o_map = 0, o_meta = 0;
     if (decode) { o_tab = at((max_pieces + n + 1) * 8); o_map = at(max_pieces * 4); o_meta = at(max_pieces * sizeof(ChunkMeta)); }
+    if (kind == kScratchVerify) o_meta = at(n * sizeof(ChunkMeta));
     if (e->inf_status.reserve(e, at.off)) return ZGPU_MEM_ERROR;
     uint8_t *scr = e->inf_status;
     *s = BatchScratch{};
     s->seg = reinterpret_cast<uint64_t *>(scr + o_seg); s->items = reinterpret_cast<BatchItemState *>(scr + o_items);
     s->status = reinterpret_cast<InfStatus *>(scr + o_status); s->cnt = reinterpret_cast<unsigned long long *>(scr + o_cnt);
-    if (decode) { s->tab = reinterpret_cast<uint64_t *>(scr + o_tab); s->map = reinterpret_cast<uint32_t *>(scr + o_map); s->meta = reinterpret_cast<ChunkMeta *>(scr + o_meta); }
+    if (decode) { s->tab = reinterpret_cast<uint64_t *>(scr + o_tab); s->map = reinterpret_cast<uint32_t *>(scr + o_map); }
+    if (kind != kScratchSizes) s->meta = reinterpret_cast<ChunkMeta *>(scr + o_meta);
     return ZGPU_OK;
 }
 
@@ -171,7 +177,7 @@ int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
     const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
     BatchScratch s;
-    if (int rc = batch_scratch(e, n, true, (out_cap >> 16) + n, &s)) return rc;
+    if (int rc = batch_scratch(e, n, kScratchDecode, (out_cap >> 16) + n, &s)) return rc;
     ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
     const uint32_t ngrid = (uint32_t)((n + 255) / 256);
     hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_lo, d_in_hi, n, (uint32_t)wrap, out_cap, d_out_lo, d_out_hi, s.seg, s.items,
@@ -276,7 +282,7 @@ static int inflate_batch_sizes_launch(zgpu_engine *e, const uint8_t *d_in, uint6
                                       unsigned long long **cnt_out, hipStream_t st)
 {
     BatchScratch s;
-    if (int rc = batch_scratch(e, n, false, 0, &s)) return rc;
+    if (int rc = batch_scratch(e, n, kScratchSizes, 0, &s)) return rc;
     ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
     const uint32_t ngrid = (uint32_t)((n + 255) / 256);
     // (there is no destination: the header kernel is given the input tables a second time in its place, so that its range check passes what the first passes)
@@ -317,6 +323,66 @@ int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_byt
     collect_spans(e);
     if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
     if (nfailed) *nfailed = h[1];
+    return ZGPU_OK;
+}
+
+// ---- integrity test (zgpu_inflate_batch_verify_*) ----
+// the verifying decoder's verdict behind the header's, as batch_merge_kernel puts the decoder's there.  The item's check values arrive whole (meta[k]):
+// for the finish kernel the item is ONE piece of all its bytes -- joining that onto the start values (1, 0 and 0) gives it back as it is -- or none
+__global__ void __launch_bounds__(256) batch_verify_merge_kernel(const InfStatus *__restrict__ status, uint64_t n, uint32_t any_check, BatchItemState *items)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    BatchItemState s = items[k];
+    if (s.code == ZGPU_OK) {
+        const InfStatus t = status[k];
+        s.code = t.code; s.msg = t.code == ZGPU_DATA_ERROR ? t.msg : 0u; s.out_bytes = t.out_bytes; s.used = t.used & 0x7fffffffu;
+    }
+    s.npieces = (s.code == ZGPU_OK && any_check && s.out_bytes) ? 1u : 0u;
+    items[k].code = s.code; items[k].msg = s.msg; items[k].out_bytes = s.out_bytes; items[k].used = s.used; items[k].npieces = s.npieces; items[k].piece0 = k;
+}
+
+// header kernel, the verifying decoder in rounds of 65,536 items, the finish kernel of the batch decoder (the trailer is compared by the very code that
+// compares it there), one read-back.  No destination, no piece table, no checksum kernels.  *states: as inflate_batch_run_ranges
+int inflate_batch_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, zgpu_inflate_item *d_items,
+                             uint64_t *nfailed, const BatchItemState **states, hipStream_t st)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (states) *states = nullptr;
+    if (checks & ~3u) return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_sizes_args(e, d_in, in_bytes, d_in_off, n, wrap, d_items)) return rc;
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    // the check each item's wrapper needs is always computed (AUTO: both), the others when asked for
+    const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
+    const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    BatchScratch s;
+    if (int rc = batch_scratch(e, n, kScratchVerify, 0, &s)) return rc;
+    ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
+    const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    // (no destination: the input tables stand in for it, as in the sizing pass)
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, d_in_off + 1, n, (uint32_t)wrap, in_bytes, d_in_off, d_in_off + 1, s.seg, s.items,
+                       reinterpret_cast<uint32_t *>(s.cnt + 2));
+    hipEvent_t ev{};
+    prof_span_begin(e, st, &ev);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        InfLaunch a{d_in, in_bytes, s.seg, c0, nb, nullptr, (uint64_t)(do_adler | (do_crc << 1)), s.status + c0};
+        a.meta = s.meta + c0;
+        launch_inflate_decode(kInfVerify, kInfNoRing, a, SpecArgs{}, st);
+    }
+    prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+    hipLaunchKernelGGL(batch_verify_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
+    launch_batch_finish(s.items, n, s.meta, d_in, do_adler, do_crc, d_items, s.cnt + 1, st);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    collect_spans(e);
+    if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
+    if (nfailed) *nfailed = h[1];
+    if (states) *states = s.items;
     return ZGPU_OK;
 }
 
@@ -459,6 +525,30 @@ int zgpu_inflate_batch_sizes_host(zgpu_engine *e, const void *in, uint64_t in_by
     zgpu_inflate_item *d_items;
     if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, 0, &d_in_off, &d_out_off, &d_items)) return rc;
     if (int rc = inflate_batch_sizes_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, d_items, nfailed, e->stream)) return rc;
+    ZGPU_HIP_CHECK(hipMemcpy(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost));
+    return ZGPU_OK;
+}
+
+int zgpu_inflate_batch_verify_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks,
+                                     zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_batch_verify_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, checks, d_items, nfailed, nullptr, st);
+}
+
+int zgpu_inflate_batch_verify_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap, uint32_t checks,
+                                   zgpu_inflate_item *items, uint64_t *nfailed)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (nfailed) *nfailed = 0;
+    if (checks & ~3u) return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_sizes_args(e, in, in_bytes, in_offsets, n, wrap, items)) return rc;
+    if (n == 0) return ZGPU_OK;
+    uint64_t *d_in_off, *d_out_off;
+    zgpu_inflate_item *d_items;
+    if (int rc = batch_stage_input(e, in, in_bytes, in_offsets, n, 0, &d_in_off, &d_out_off, &d_items)) return rc;
+    if (int rc = inflate_batch_verify_run(e, e->stage_in, in_bytes, d_in_off, n, wrap, checks, d_items, nfailed, nullptr, e->stream)) return rc;
     ZGPU_HIP_CHECK(hipMemcpy(items, d_items, n * sizeof(zgpu_inflate_item), hipMemcpyDeviceToHost));
     return ZGPU_OK;
 }

@@ -55,12 +55,17 @@ struct InflateLdsSizes {
     uint32_t build_rc, build_n;
     uint32_t end_final, pad1;
 };
+// The integrity test (inflate_kernel_t<..., VERIFY>): the decoder's layout with the 32 KiB ring, unchanged, and behind it the writer wave's CRC lookup
+struct InflateLdsVerify : InflateLdsT<uint8_t, 32768> {
+    uint32_t crc_nib[kCrcNibWords]; // eight nibble tables of 16 words (crc_nib_entry, zgpu_common.h)
+};
 using InflateLdsSpec = InflateLdsT<uint16_t>;
 constexpr uint32_t kScanBytes = 4096; // the block finder reads the input through LDS in pieces of this size (+ the 16 bytes a bit offset at the end reaches into)
 constexpr uint32_t kFindList = 1024; // candidates listed between two rounds of the second sieve (a group of 2048 offsets yields 683 at most: one in three)
 using InflateLdsFind = InflateLdsT<uint8_t, kScanBytes + 64 + kFindList * 2>;
 static_assert(sizeof(InflateLdsFind) <= 14336, "eleven finder waves per CU");
 static_assert(sizeof(InflateLds) <= 40448, "four segments per CU");
+static_assert(sizeof(InflateLdsVerify) <= 40448 && 4 * sizeof(InflateLdsVerify) <= 160 * 1024, "the integrity test: four workgroups per CU, as the decoder it is");
 static_assert(10 * sizeof(InflateLdsT<uint8_t, 8192>) <= 160 * 1024, "ten segments per CU with the 8 KiB ring (five waves per SIMD: 96 registers)");
 static_assert(sizeof(InflateLdsSpec) <= 81920, "two workgroups per CU");
 static_assert(24 * sizeof(InflateLdsSizes) <= 160 * 1024, "the sizing pass: twenty-four one-wave workgroups per CU (six waves per SIMD)");

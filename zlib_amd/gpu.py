@@ -117,6 +117,10 @@ def load_library():
     L.zgpu_inflate_batch_sizes_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, vp, C.POINTER(u64)]
     L.zgpu_inflate_batch_packed_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, u32, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
     L.zgpu_inflate_batch_packed_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, u32, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.zgpu_inflate_batch_verify_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, C.POINTER(u64), vp]
+    L.zgpu_inflate_batch_verify_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, C.POINTER(u64)]
+    L.zgpu_bgzf_verify_device.argtypes = [vp, vp, u64, vp, C.POINTER(InflateResult), vp]
+    L.zgpu_bgzf_verify_host.argtypes = [vp, vp, u64, vp, C.POINTER(InflateResult)]
     L.zgpu_bgzf_bound.argtypes = [u64, u32]
     L.zgpu_bgzf_bound.restype = u64
     L.zgpu_bgzf_deflate_device.argtypes = [vp, vp, u64, C.c_int, C.c_int, u32, vp, u64, vp, C.POINTER(DeflateResult), vp]
@@ -428,6 +432,26 @@ class Engine:
             self._check(rc)
         return rc, total.value, failed.value
 
+    # ---- batch integrity test ----
+    def inflate_batch_verify_host(self, streams, wrap="zlib", checks=0):
+        """The integrity test (zgpu_inflate_batch_verify_host): every item decoded in full and its trailer compared, nothing decoded into memory.
+        Returns one (code, msg, out_bytes, in_used, adler32, crc32) per item: what inflate_batch_host says of it given room of exactly its size."""
+        n = len(streams)
+        blob, ioffs = self._pack_streams(streams)
+        items = (InflateItem * max(n, 1))()
+        failed = C.c_uint64(0)
+        self._check(self.L.zgpu_inflate_batch_verify_host(self.h, blob.ctypes.data, int(ioffs[-1]), ioffs.ctypes.data, n, _WRAPS[wrap], checks, items, C.byref(failed)))
+        self.last_failed = failed.value
+        return [(items[k].code, self.L.zgpu_inflate_message(items[k].msg).decode(), items[k].out_bytes, items[k].in_used, items[k].adler32, items[k].crc32) for k in range(n)]
+
+    def inflate_batch_verify_device(self, d_in, in_bytes, d_in_offsets, n, d_items, wrap="zlib", checks=0, stream=None):
+        """Device pointers as ints, as inflate_batch_sizes_device takes them.  Blocks until the records are written; returns the number of items that failed."""
+        failed = C.c_uint64(0)
+        self._check(self.L.zgpu_inflate_batch_verify_device(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks, d_items,
+                                                            C.byref(failed), stream))
+        self.last_failed = failed.value
+        return failed.value
+
     # ---- BGZF (blocked gzip) ----
     def bgzf_deflate_host(self, data, level=6, block_size=0, strategy=0, want_offsets=False):
         """data -> a BGZF file (zgpu_bgzf_deflate_host); with want_offsets also where every block begins, where the end block begins, the length."""
@@ -463,6 +487,28 @@ class Engine:
         if rc not in (0, -3, -5):
             self._check(rc)
         return rc, out[: res.out_bytes].tobytes() if rc in (0, -3) else b"", items
+
+    def bgzf_verify_host(self, data):
+        """Test a BGZF file without decoding it into memory (zgpu_bgzf_verify_host) -> (rc, items): rc 0 or -3, items as bgzf_inflate_host gives them;
+        self.last_inflate has out_bytes and the first failing block."""
+        import numpy as np
+        arr = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+        n = int(arr.size) - 1
+        items = (InflateItem * max(n // 28, 1))()
+        res = InflateResult()
+        rc = self.L.zgpu_bgzf_verify_host(self.h, arr.ctypes.data, n, items, C.byref(res))
+        self.last_inflate = res
+        if rc not in (0, -3):
+            self._check(rc)
+        return rc, items
+
+    def bgzf_verify_device(self, d_in, in_bytes, d_items=None, stream=None):
+        """Returns (rc, InflateResult)."""
+        res = InflateResult()
+        rc = self.L.zgpu_bgzf_verify_device(self.h, d_in, in_bytes, d_items, C.byref(res), stream)
+        if rc not in (0, -3):
+            self._check(rc)
+        return rc, res
 
     def bgzf_index_device(self, d_in, in_bytes, d_in_offsets, d_out_offsets, cap_blocks, stream=None):
         """Device pointers as ints; the tables hold cap_blocks + 1 uint64 each.  Returns (rc, nblocks, out_bytes, ends_with_eof_block)."""

@@ -248,14 +248,16 @@ static int packed_in_make(struct packed_in *p, const Bytef *const *source, const
     return ZGPU_OK;
 }
 
-/* sizes of all items: the engine's sizing pass for those it takes, size_one for the others.  size[k] = 0 where status[k] is not Z_OK */
-static void sizes_all(struct packed_in *p, int rc, uLongf *size, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status)
+/* sizes of all items: the engine's sizing pass for those it takes, size_one for the others.  size[k] = 0 where status[k] is not Z_OK.
+ * verify: the integrity test in the sizing pass's place -- the trailers are checked too (size_one checks them as it is); size may be NULL then */
+static void sizes_all(struct packed_in *p, int rc, uLongf *size, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status, int verify)
 {
     if (p->nb && rc == ZGPU_OK) {
         zgpu_engine *e = zamd_batch_engine_lock();
         if (!e) rc = ZGPU_ERRNO;
         else {
-            rc = zgpu_inflate_batch_sizes_host(e, p->in, p->in_total, p->ioff, p->nb, window_wrap(windowBits), p->items, NULL);
+            if (verify) rc = zgpu_inflate_batch_verify_host(e, p->in, p->in_total, p->ioff, p->nb, window_wrap(windowBits), 0, p->items, NULL);
+            else rc = zgpu_inflate_batch_sizes_host(e, p->in, p->in_total, p->ioff, p->nb, window_wrap(windowBits), p->items, NULL);
             zamd_batch_engine_unlock();
         }
     }
@@ -263,12 +265,13 @@ static void sizes_all(struct packed_in *p, int rc, uLongf *size, const Bytef *co
         const size_t k = p->idx[i];
         if (rc != ZGPU_OK) status[k] = rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : engine_code(rc);
         else status[k] = p->items[i].code == ZGPU_OK ? Z_OK : Z_DATA_ERROR;
-        size[k] = status[k] == Z_OK ? (uLongf)p->items[i].out_bytes : 0;
+        if (size) size[k] = status[k] == Z_OK ? (uLongf)p->items[i].out_bytes : 0;
     }
     for (size_t k = 0; k < n; k++)
         if (sourceLen[k] >= BATCH_IN_MAX) {
-            size[k] = 0;
-            status[k] = size_one(&size[k], source[k], sourceLen[k], windowBits);
+            uLongf got = 0;
+            status[k] = size_one(&got, source[k], sourceLen[k], windowBits);
+            if (size) size[k] = got;
         }
 }
 
@@ -281,7 +284,21 @@ EXPORT int zamd_uncompress_sizes_batch(uLongf *destLen, const Bytef *const *sour
     if (n == 0) return Z_OK;
     struct packed_in p;
     const int rc = packed_in_make(&p, source, sourceLen, n);
-    sizes_all(&p, rc, destLen, source, sourceLen, n, windowBits, status);
+    sizes_all(&p, rc, destLen, source, sourceLen, n, windowBits, status, 0);
+    packed_in_free(&p);
+    return first_failure(status, n);
+}
+
+EXPORT int zamd_uncompress_verify_batch(uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status)
+{
+    if (n && (!source || !sourceLen || !status)) return Z_STREAM_ERROR;
+    if (window_wrap(windowBits) < 0) return Z_STREAM_ERROR;
+    for (size_t k = 0; k < n; k++)
+        if (!source[k] && sourceLen[k]) return Z_STREAM_ERROR;
+    if (n == 0) return Z_OK;
+    struct packed_in p;
+    const int rc = packed_in_make(&p, source, sourceLen, n);
+    sizes_all(&p, rc, destLen, source, sourceLen, n, windowBits, status, 1);
     packed_in_free(&p);
     return first_failure(status, n);
 }
@@ -331,7 +348,7 @@ EXPORT int zamd_uncompress_batch_packed(Bytef *dest, uLongf *destCap, uLong *des
         free(size); free(ooff); packed_in_free(&p);
         return Z_MEM_ERROR;
     }
-    sizes_all(&p, rc, size, source, sourceLen, n, windowBits, status);
+    sizes_all(&p, rc, size, source, sourceLen, n, windowBits, status, 0);
     uint64_t total = 0;
     for (size_t k = 0; k < n; k++) { destOffsets[k] = (uLong)total; total += size[k]; }
     destOffsets[n] = (uLong)total;

@@ -53,6 +53,20 @@ EXPORT int zamd_bgzf_uncompress(Bytef *dest, uLongf *destLen, const Bytef *sourc
     return z_code(rc);
 }
 
+EXPORT int zamd_bgzf_test(const Bytef *source, uLong sourceLen, uLongf *decodedLen)
+{
+    if (!source && sourceLen) return Z_STREAM_ERROR;
+    if (sourceLen == 0) { if (decodedLen) *decodedLen = 0; return Z_OK; } /* (a file of no blocks: nothing to ask an engine) */
+    zgpu_engine *e = zamd_engine_checkout();
+    if (!e) return Z_MEM_ERROR;
+    zgpu_inflate_result res;
+    memset(&res, 0, sizeof res);
+    const int rc = zgpu_bgzf_verify_host(e, source, sourceLen, NULL, &res);
+    zamd_engine_checkin(e);
+    if (rc == ZGPU_OK && decodedLen) *decodedLen = (uLongf)res.out_bytes;
+    return z_code(rc);
+}
+
 /* the block at `pos`: its length and ISIZE; 0 when there is no valid block (the rules of bgzf_candidate in zgpu_bgzf.hip) */
 static uint64_t block_at(const unsigned char *s, uint64_t n, uint64_t pos, uint32_t *isize)
 {

@@ -5,6 +5,7 @@
  * header check :983-1050. */
 #include "../../include/zamd_zip.h"
 #include "../../include/zamd_zip_batch.h"
+#include "../../include/zamd_zip_test.h"
 #include "../../include/zamd_zlib.h"
 #include "zamd_host.h"
 #include <stdint.h>
@@ -427,6 +428,104 @@ EXPORT int zamd_unzip_read_batch(zamd_unzip *u, const int *index, size_t n, void
     }
     for (size_t k = 0; k < n; k++)
         if (kind[k] == ONE) result[k] = zamd_unzip_read(u, index ? index[k] : (int)k, out[k], cap[k]);
+    free(kind); free(at); free(body);
+    for (size_t k = 0; k < n; k++)
+        if (result[k] < 0) return (int)result[k];
+    return ZAMD_ZIP_OK;
+}
+
+EXPORT int zamd_unzip_test_batch(zamd_unzip *u, const int *index, size_t n, long *result)
+{
+    enum { ONE = 0, STORED = 1, DEFLATED = 2, DONE = 3 }; /* how item k is served */
+    if (!u || (n && !result)) return ZAMD_ZIP_PARAMERROR;
+    if (n == 0) return ZAMD_ZIP_OK;
+    uint8_t *kind = (uint8_t *)calloc(n, 1);
+    size_t *at = (size_t *)malloc(n * sizeof *at); /* at[k]: item k's place in its engine call */
+    long *body = (long *)malloc(n * sizeof *body); /* body[k]: where the member's data starts in the file */
+    if (!kind || !at || !body) { free(kind); free(at); free(body); return ZAMD_ZIP_INTERNALERROR; }
+    /* pass 1: every item's checks (the room is the directory's size: never too small); what the two engine calls will hold */
+    uint64_t nd = 0, d_in = 0, ns = 0, s_in = 0;
+    for (size_t k = 0; k < n; k++) {
+        const int i = index ? index[k] : (int)k;
+        if (i < 0 || i >= u->n) { result[k] = ZAMD_ZIP_PARAMERROR; kind[k] = DONE; continue; }
+        const zamd_zip_entry *t = &u->ent[i];
+        const int rc = member_seek(u, t, t->uncompressed_size);
+        if (rc != ZAMD_ZIP_OK) { result[k] = rc; kind[k] = DONE; continue; }
+        if (t->method == 0 && t->compressed_size != t->uncompressed_size) { result[k] = ZAMD_ZIP_BADZIPFILE; kind[k] = DONE; continue; }
+        if (t->method != 0 && t->compressed_size >= BATCH_IN_MAX) continue; /* ONE */
+        if ((body[k] = ftell(u->fp)) < 0) { result[k] = ZAMD_ZIP_ERRNO; kind[k] = DONE; continue; }
+        if (t->method == 0) { kind[k] = STORED; at[k] = (size_t)ns++; s_in += t->uncompressed_size; }
+        else { kind[k] = DEFLATED; at[k] = (size_t)nd++; d_in += 18 + (uint64_t)t->compressed_size; }
+    }
+    /* stored members: their bytes straight from the file into the call's buffer, their CRC-32s in one call */
+    if (ns) {
+        uint8_t *in = (uint8_t *)malloc(s_in + 1);
+        uint64_t *off = (uint64_t *)malloc((ns + 1) * sizeof *off);
+        zgpu_check_item *items = (zgpu_check_item *)malloc(ns * sizeof *items);
+        int ok = in && off && items;
+        if (ok) {
+            uint64_t pos = 0;
+            for (size_t k = 0; k < n; k++)
+                if (kind[k] == STORED) {
+                    const unsigned long sz = u->ent[index ? index[k] : (int)k].uncompressed_size;
+                    off[at[k]] = pos;
+                    if (fseek(u->fp, body[k], SEEK_SET) || fread(in + pos, 1, sz, u->fp) != sz) { result[k] = ZAMD_ZIP_ERRNO; kind[k] = DONE; memset(in + pos, 0, sz); }
+                    pos += sz;
+                }
+            off[ns] = pos;
+            zgpu_engine *e = zamd_batch_engine_lock();
+            ok = e != NULL;
+            if (e) { ok = zgpu_checksum_batch_host(e, in, s_in, off, ns, ZGPU_CHECK_CRC32, items) == ZGPU_OK; zamd_batch_engine_unlock(); }
+        }
+        for (size_t k = 0; k < n; k++)
+            if (kind[k] == STORED) {
+                const zamd_zip_entry *t = &u->ent[index ? index[k] : (int)k];
+                result[k] = !ok ? ZAMD_ZIP_INTERNALERROR : items[at[k]].crc32 == (uint32_t)t->crc32 ? (long)t->uncompressed_size : ZAMD_ZIP_CRCERROR;
+            }
+        free(in); free(off); free(items);
+    }
+    /* deflated members: each framed as zamd_unzip_read frames it -- gzip header, the raw data, the directory's CRC-32 and size -- one integrity test */
+    if (nd) {
+        uint8_t *in = (uint8_t *)malloc(d_in + 1);
+        uint64_t *ioff = (uint64_t *)malloc((nd + 1) * sizeof *ioff);
+        zgpu_inflate_item *items = (zgpu_inflate_item *)malloc(nd * sizeof *items);
+        int ok = in && ioff && items;
+        if (ok) {
+            static const uint8_t gh[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3};
+            uint64_t pi = 0;
+            for (size_t k = 0; k < n; k++)
+                if (kind[k] == DEFLATED) {
+                    const zamd_zip_entry *t = &u->ent[index ? index[k] : (int)k];
+                    ioff[at[k]] = pi;
+                    memcpy(in + pi, gh, 10);
+                    if (fseek(u->fp, body[k], SEEK_SET) || fread(in + pi + 10, 1, t->compressed_size, u->fp) != t->compressed_size) {
+                        result[k] = ZAMD_ZIP_ERRNO; kind[k] = DONE; memset(in + pi + 10, 0, t->compressed_size); /* (its item decodes to an error nobody reads) */
+                    }
+                    put32(in + pi + 10 + t->compressed_size, t->crc32); put32(in + pi + 14 + t->compressed_size, t->uncompressed_size);
+                    pi += 18 + (uint64_t)t->compressed_size;
+                }
+            ioff[nd] = pi;
+            zgpu_engine *e = zamd_batch_engine_lock();
+            ok = e != NULL;
+            if (e) { ok = zgpu_inflate_batch_verify_host(e, in, d_in, ioff, nd, ZGPU_WRAP_GZIP, 0, items, NULL) == ZGPU_OK; zamd_batch_engine_unlock(); }
+        }
+        for (size_t k = 0; k < n; k++)
+            if (kind[k] == DEFLATED) {
+                const zamd_zip_entry *t = &u->ent[index ? index[k] : (int)k];
+                if (!ok) result[k] = ZAMD_ZIP_INTERNALERROR;
+                else if (items[at[k]].code == ZGPU_OK) result[k] = (long)t->uncompressed_size; /* (CRC-32 and size have been checked on the device) */
+                else kind[k] = ONE; /* refused: the code is zamd_unzip_read's own */
+            }
+        free(in); free(ioff); free(items);
+    }
+    for (size_t k = 0; k < n; k++)
+        if (kind[k] == ONE) {
+            const int i = index ? index[k] : (int)k;
+            const unsigned long sz = u->ent[i].uncompressed_size;
+            void *room = malloc(sz + 1);
+            result[k] = room ? zamd_unzip_read(u, i, room, sz) : ZAMD_ZIP_INTERNALERROR;
+            free(room);
+        }
     free(kind); free(at); free(body);
     for (size_t k = 0; k < n; k++)
         if (result[k] < 0) return (int)result[k];
