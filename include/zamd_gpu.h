@@ -161,7 +161,7 @@ int zgpu_deflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, con
 int zgpu_deflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const zgpu_deflate_params *p, void *out,
                       uint64_t out_cap, uint64_t *chunk_offsets, zgpu_deflate_result *res);
 
-/* ---- ONE continuous stream, feed by feed (zlib_amd/csrc/zgpu_cont.hip): what deflate() of the zlib API is built on ----
+/* ---- ONE continuous stream, feed by feed (zlib_amd/csrc/zgpu_cont.hip the kernels, zgpu_deflate_cont.hip the host side): what deflate() of the zlib API is built on ----
  * The stream's state between feeds lives with the CALLER (zgpu_cont_state + the tokens of the block that is still filling); the engine keeps nothing.
  * All positions are positions in the stream (a preset dictionary's bytes count: the first one is position 0).
  *   hist, in   buf = hist followed by in (two host buffers, so that a caller's large input need not be copied behind the little history the stream keeps):

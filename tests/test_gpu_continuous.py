@@ -66,7 +66,7 @@ def test_golden_streams_of_both_corpora_through_the_z_stream_api():
 
 def test_fast_levels_round_zero_in_phases(eng, monkeypatch):
     """Levels 1-3: only every K-th tile of a batch starts from a guess, the K - 1 behind it are parsed phase by phase from the tile in front's results
-    (zgpu_engine.hip lz_tiles_fast; K = tiles / 256 by default, 1 for inputs this small).  Runs of 1, 3, 4 and 7 tiles over 3 MiB of both corpora and over data
+    (zgpu_deflate_cont.hip lz_tiles_fast, zgpu_deflate_plan.h plan_fast_phases; K = tiles / 256 by default, 1 for inputs this small).  Runs of 1, 3, 4 and 7 tiles over 3 MiB of both corpora and over data
     whose parse never forgets where it started (a period, zeros): the restatement's bytes whatever K is."""
     from zlib_amd import gpu
     F = gpu.F_FINAL | gpu.F_CONTINUOUS

@@ -31,7 +31,7 @@ def gold(golden):
 
 
 def impls(cfg):
-    """Every implementation that serves the configuration (zgpu_engine.hip: LZ_PARALLEL the default strategy only; Z_RLE is a chain budget of
+    """Every implementation that serves the configuration (zgpu_deflate_plan.h plan_deflate: LZ_PARALLEL the default strategy only; Z_RLE is a chain budget of
     the all-position search, so neither the walkers nor the level 1-3 kernels on sorted buckets take it)."""
     from zlib_amd import gpu
     k = P.CONFIGS[cfg]

@@ -110,7 +110,7 @@ struct ChunkGeom {
     uint32_t block_tokens;   // lit_bufsize - 1: a block is cut after this many tokens (kBlockTokens by default)
     uint32_t slot_stride;    // bytes between the chunks' output slots (kSlotStride by default)
     const uint32_t *nostore_bits; // nullptr: ChunkMeta::nostore has a bit per block; else kGeoNostoreWords words per chunk (a chunk may have 517 blocks)
-    // A launch over a LIST of the batch's chunks (levels 1-3: the chunks the lane-per-chunk loop handed on, zgpu_engine.hip): workgroup c works on
+    // A launch over a LIST of the batch's chunks (levels 1-3: the chunks the lane-per-chunk loop handed on, zgpu_deflate.hip lz_batch): workgroup c works on
     // chunk chunk_map[c] of the batch -- the input, tokens and meta of that chunk; its scratch (sorted buckets) is slot c.  nullptr: chunk c.
     const uint32_t *chunk_map;
     // Continuous stream (round 4, zgpu_cont.hip): tile_stride != 0 makes "chunk" c of the launch the TILE chunk0 + c -- the 64 KiB of the buffer that start at

@@ -133,8 +133,27 @@ hipEvent_t engine_copy_event(zgpu_engine *e, size_t i);
 // stage timing of the other files' launches with the engine's event pool
 void prof_span_begin(zgpu_engine *e, hipStream_t st, hipEvent_t *a);
 void prof_span_end(zgpu_engine *e, hipStream_t st, int stage, hipEvent_t a);
+struct StageTimer { // a stage's launches in one scope
+    zgpu_engine *e; hipStream_t st; int stage; hipEvent_t a{};
+    StageTimer(zgpu_engine *e_, hipStream_t st_, int stage_) : e(e_), st(st_), stage(stage_) { prof_span_begin(e, st, &a); }
+    ~StageTimer() { prof_span_end(e, st, stage, a); }
+};
+uint32_t env_u32(const char *name, uint32_t dflt); // an environment knob: its value when it is a number above 0, else dflt
 // Adler-32 (mask bit 0) and CRC-32 (bit 1) of d_bytes[0, nbytes) from 64 KiB pieces, at most batch_cap of them a launch, their records in `meta`
 int checksum_pass(zgpu_engine *e, const uint8_t *d_bytes, uint64_t nbytes, uint32_t mask, uint32_t batch_cap, DevBuf<ChunkMeta> &meta, hipStream_t st, uint32_t *adler, uint32_t *crc);
+
+// ---- zgpu_deflate.hip ----
+// the chunked compressor's workspace for `batch` chunks a launch (serial: the lane-per-chunk loop's tables, else the sorted buckets; geo: a non-default
+// geometry's wider group) and the offsets of a call of nchunks_total chunks; the tiles of the continuous stream and the checksum entry points use it too
+int ensure_deflate_ws(zgpu_engine *e, uint32_t batch, bool serial, uint64_t nchunks_total, bool geo = false);
+LevelCfg level_cfg_for(const zgpu_engine *e, int level, int strategy); // the level's parameters, or zgpu_deflate_set_tuning's
+FrameHead frame_head(int level, int strategy, bool wrap, bool gz, bool bgzf = false);
+int write_trailer(zgpu_engine *e, bool gz, uint32_t adler, uint32_t crc, uint64_t in_bytes, uint8_t *d_out, uint64_t *out_total, hipStream_t st);
+struct PlanEngine; // zgpu_deflate_plan.h
+PlanEngine plan_engine(const zgpu_engine *e, const LevelCfg *cfg);
+
+// ---- zgpu_deflate_cont.hip ----
+int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const zgpu_deflate_params *p, uint8_t *d_out, uint64_t out_cap, zgpu_deflate_result *res, hipStream_t st);
 
 // ---- zgpu_lz_serial.hip ----
 void launch_lz_serial(const ChunkGeom &g, LevelCfg cfg, uint4 *tables, uint32_t *tokens, ChunkMeta *meta, hipStream_t st, uint32_t *nostore_bits, bool hand_on, uint32_t tag);

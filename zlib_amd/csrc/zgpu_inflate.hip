@@ -1,4 +1,4 @@
-// zgpu_inflate.hip -- decode path: the decoder kernel, one workgroup per segment, its one launcher and the chunk path (inflate_run).  The batch of
+// zgpu_inflate.hip -- decode path: the decoder kernel, one workgroup per segment, its one launcher, the chunk path (inflate_run) and its C entry points.  The batch of
 // independent streams is zgpu_inflate_batch.hip, a stream that was not produced in chunks zgpu_inflate_stream.hip; what the kernels share, zgpu_inflate_dev.h.
 //
 // Restates (file:line under /root/reference):
@@ -892,3 +892,61 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
 } // namespace zgpu
 
 extern "C" __attribute__((visibility("default"))) const char *zgpu_inflate_message(uint32_t index) { return index < zgpu::kMsgCount ? zgpu::kInfMessages[index] : ""; }
+
+// ---- the C entry points of the chunked decoder (include/zamd_gpu.h): all they call is inflate_run ----
+using namespace zgpu;
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int zgpu_inflate_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_chunk_offsets, uint64_t nchunks,
+                        uint32_t chunk_size, void *d_out, uint64_t out_cap, zgpu_inflate_result *res, void *hip_stream)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    return inflate_run(e, static_cast<const uint8_t *>(d_in), in_bytes, d_chunk_offsets, nchunks, chunk_size, static_cast<uint8_t *>(d_out), out_cap, res, st);
+}
+
+int zgpu_inflate_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *chunk_offsets, uint64_t nchunks, uint32_t chunk_size,
+                      void *out, uint64_t out_cap, zgpu_inflate_result *res)
+{
+    if (!e || !res || !in || !out || !chunk_offsets || nchunks == 0) return fail(e, ZGPU_STREAM_ERROR, "null argument");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    const uint64_t need_out = nchunks * (uint64_t)(chunk_size ? chunk_size : kChunkMax);
+    int rc = ensure_stage(e, in_bytes + 64, need_out);
+    if (rc) return rc;
+    if ((rc = e->offsets.reserve(e, nchunks + 1))) return rc;
+    ZGPU_HIP_CHECK(hipMemcpyAsync(e->stage_in, in, in_bytes, hipMemcpyHostToDevice, e->stream));
+    ZGPU_HIP_CHECK(hipMemcpyAsync(e->offsets, chunk_offsets, (nchunks + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    // direct placement with room for every chunk: the output goes to the caller's buffer batch by batch, under the decoding of the next batch
+    // (the device buffer has room for nchunks whole chunks; the caller's buffer has out_cap bytes, and no copy into it goes beyond them)
+    const bool stream_out = chunk_size != 0 && chunk_size <= kChunkMax;
+    rc = inflate_run(e, e->stage_in, in_bytes, e->offsets, nchunks, chunk_size, e->stage_out, need_out, res, e->stream, 0, nullptr, false,
+                     stream_out ? static_cast<uint8_t *>(out) : nullptr, out_cap);
+    if (rc) return rc;
+    if (res->out_bytes > out_cap) return fail(e, ZGPU_BUF_ERROR, "output capacity too small");
+    if (!stream_out) ZGPU_HIP_CHECK(hipMemcpyAsync(out, e->stage_out, res->out_bytes, hipMemcpyDeviceToHost, e->stream));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream));
+    return ZGPU_OK;
+}
+
+int zgpu_inflate_set_dictionary(zgpu_engine *e, const void *dict, uint32_t len)
+{
+    if (!e || (!dict && len)) return fail(e, ZGPU_STREAM_ERROR, "null argument");
+    ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    if (len > kWSize) { dict = static_cast<const uint8_t *>(dict) + (len - kWSize); len = kWSize; } // the window keeps the tail (inflate.c:1222-1226)
+    if (len) { const int rc = e->inf_dict.reserve(e, kWSize); if (rc) return rc; }
+    if (len) { ZGPU_HIP_CHECK(hipMemcpyAsync(e->inf_dict, dict, len, hipMemcpyHostToDevice, e->stream)); ZGPU_HIP_CHECK(hipStreamSynchronize(e->stream)); }
+    e->inf_dict_len = len;
+    return ZGPU_OK;
+}
+
+int zgpu_inflate_set_checks(zgpu_engine *e, uint32_t mask)
+{
+    if (!e || mask > 3u) return fail(e, ZGPU_STREAM_ERROR, "checks: a mask of ZGPU_CHECK_ADLER32 | ZGPU_CHECK_CRC32");
+    e->inf_checks = mask;
+    return ZGPU_OK;
+}
+
+#pragma GCC visibility pop
+} // extern "C"

@@ -82,7 +82,7 @@ struct __attribute__((packed, aligned(1))) FwU64 { uint64_t v; };
 #define ZGPU_FW_STG64 0 // 1 (built at the end of round 4, scripts/build_variant.sh stg64 -DZGPU_FW_STG64=1): the staged entries of the form without the ring at 64 bytes a lane, slots swizzled -- 12 304 bytes a
                         // workgroup, TWELVE to a CU (LDS is handed out in pieces of 1 280 bytes): 4 GiB level 1 in 22 phases 673 -> 564 ms, parity tests of levels 1-3 pass; not the default before the whole suite has run on it
 #endif
-constexpr uint32_t kFwOffFlagsNR = 0, kFwOffStgNR = (kFwFlagWords * 4 + 15) & ~15u, kFwLdsNR = kFwOffStgNR + (ZGPU_FW_STG64 ? 64 * 64 : 63 * kFwStgStride + 64); // (13 312 bytes, without the last lane's padding.  ELEVEN workgroups run on a CU, not the twelve that 160 KiB / 13 KiB promise: a launch of 3 003 tiles takes two waves of workgroups' time, one of 2 752 one -- zgpu_engine.hip lz_tiles_fast)
+constexpr uint32_t kFwOffFlagsNR = 0, kFwOffStgNR = (kFwFlagWords * 4 + 15) & ~15u, kFwLdsNR = kFwOffStgNR + (ZGPU_FW_STG64 ? 64 * 64 : 63 * kFwStgStride + 64); // (13 312 bytes, without the last lane's padding.  ELEVEN workgroups run on a CU, not the twelve that 160 KiB / 13 KiB promise: a launch of 3 003 tiles takes two waves of workgroups' time, one of 2 752 one -- zgpu_deflate_plan.h plan_fast_phases)
 __device__ inline uint64_t fw_g64(const uint8_t *src, uint32_t pos, uint64_t safe_end)
 {
     if ((uint64_t)pos + 8 <= safe_end) return reinterpret_cast<const FwU64 *>(src + pos)->v;
@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(64) fastwin_kernel(ChunkGeom g, uint32_t max_i
 // 32512 positions later the parse and the chains have almost always fallen into step with the stream's); from round 1 on a tile whose predecessor's
 // results have changed is parsed again from where the predecessor's parse ended, with the predecessor's "inserted" bits as its history; a round in which
 // no tile's results (exit, bits) change has reached the one consistent assignment, which is the reference's parse (the recursion tile i = F(tile i - 1)
-// has exactly one solution).  The engine runs rounds until no tile is active (zgpu_engine.hip, deflate_cont).
+// has exactly one solution).  The engine runs rounds until no tile is active (zgpu_deflate_cont.hip, lz_tiles_fast).
 //   ins (per tile, two buffers): one bit per local position 32512 .. 65535: "in the chains", valid below the tile's exit -- read by the tile behind it,
 //   for which these are its local positions 0 .. 33023.
 // Block cuts, the window's slides and the stored-block veto are the stream's business (cont_table_kernel), not the tile's.
@@ -897,7 +897,7 @@ __global__ void __launch_bounds__(256) fast_hist_kernel(const uint32_t *before, 
     }
     out[w] = v;
 }
-// behind a launch over a list of tiles that all make their new results current (the phases of round 0, zgpu_engine.hip lz_tiles_fast)
+// behind a launch over a list of tiles that all make their new results current (the phases of round 0, zgpu_deflate_cont.hip fast_round0_phases)
 __global__ void __launch_bounds__(256) fast_flip_list_kernel(uint8_t *cur, uint16_t *exit_cur, const uint16_t *exit_new, const uint32_t *list, uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;

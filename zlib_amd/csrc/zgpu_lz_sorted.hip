@@ -1545,7 +1545,7 @@ bool launch_lz_sorted(const ChunkGeom &g, LevelCfg cfg, void *workspace, uint32_
 
 // A batch of tiles of a continuous stream (zgpu_cont.hip): sort, walkers + exit functions, the chain of entries, the tiles' tokens.
 
-// the sort alone (levels 1-3 go on with fastwin_tile_kernel's rounds, zgpu_engine.hip): where S and ir of the batch's tiles are
+// the sort alone (levels 1-3 go on with fastwin_tile_kernel's rounds, zgpu_deflate_cont.hip lz_tiles_fast): where S and ir of the batch's tiles are
 void launch_sort_tiles(const ChunkGeom &g, void *workspace, ChunkMeta *meta, hipStream_t st, zgpu_engine *prof, int exact_sort, const uint16_t **S_out, const uint32_t **ir_out)
 {
     const SortedWs ws(workspace, g.nchunks);
