@@ -410,6 +410,51 @@ int zgpu_inflate_batch_verify_device(zgpu_engine *e, const void *d_in, uint64_t 
 int zgpu_inflate_batch_verify_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,
                                    uint32_t checks, zgpu_inflate_item *items, uint64_t *nfailed);
 
+/* ---- stream-ordered batch inflate: the four jobs above, enqueued ----
+ * For a caller whose data lives on the GPU.  A call puts hipMemsetAsync and kernel launches on hip_stream (null: the engine's stream) as ONE chain and
+ * returns; it does not synchronize, allocate, copy to or from host memory, record an event, use a second stream or time anything, and it uses no device
+ * memory of the engine's: its scratch is d_ws, device memory of the caller's, 256-byte aligned, of at least
+ * zgpu_inflate_batch_workspace_bytes(job, n) bytes (a function of n alone -- never of out_cap or of what the items decode to; it needs no engine and no
+ * GPU).  The engine supplies the device and the error text, nothing else: two calls with different workspaces may be in flight on different streams of
+ * one engine, a call can wait in a stream behind the copy that brings its input, and it can be captured into a graph (not the first call of a
+ * process: that one loads the code).  d_in, the offset tables, d_out, d_items, d_summary and d_ws are read and written in stream order: they must be
+ * valid when the work runs, and stay untouched by other streams until it is done; the results are there when the stream has reached that point.
+ * Arguments the host can judge -- a null pointer that is needed, wrap, checks or align out of range, n >= 2^32, ws_bytes too small, d_ws not 256-byte
+ * aligned -- return ZGPU_STREAM_ERROR at once with nothing enqueued.  n == 0 enqueues at most the summary's memset.
+ * d_items[k] is, field for field, the record the blocking entry point of the same job gives item k with the same arguments.  What differs: offsets that
+ * run backwards or leave their buffer do not fail the call (the host never sees them).  Such an item reads and writes nothing and gets
+ * code = ZGPU_STREAM_ERROR, msg = 0, out_bytes = in_used = 0, adler32 = 1, crc32 = 0; it counts in nfailed and in nbad_offsets, and every other item is
+ * served as if it were not there.
+ * d_summary (optional, device memory): nfailed = items whose code is not ZGPU_OK; nbad_offsets; packed only: total = d_out_offsets[n], and
+ * overflow = 1 when total > out_cap -- then, as ZGPU_BUF_ERROR of the blocking call, d_out_offsets and total are written, d_items holds the sizing
+ * records and no decoded byte is written (the decode stage's items are emptied on the device; there is no second sizing pass).
+ * The decode and the packed decode run the decoder in a mode of its own: every item through the ring of its workgroup (the ring the blocking decode
+ * picks), its Adler-32 / CRC-32 folded out of the ring in the flush that stores the bytes, so no pass reads the output again and no count has to
+ * reach the host.  Rates (profiles/r08_batch_enqueue_table.txt, level 6, device-resident): 200 batches of 64 items of 4 KiB, 151 us a batch against
+ * 207 us through 200 blocking calls; one large batch takes what the blocking call takes (enqueue / blocking 0.95 to 1.01 over both shapes and rings). */
+#define ZGPU_BATCH_JOB_DECODE 0
+#define ZGPU_BATCH_JOB_SIZES 1
+#define ZGPU_BATCH_JOB_VERIFY 2
+#define ZGPU_BATCH_JOB_PACKED 3
+typedef struct {
+    uint64_t nfailed, nbad_offsets, total;
+    uint32_t overflow, reserved;
+} zgpu_inflate_batch_summary;
+uint64_t zgpu_inflate_batch_workspace_bytes(int job, uint64_t n); /* 0: no such job, or n >= 2^32 */
+int zgpu_inflate_batch_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                               uint32_t checks, void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_inflate_item *d_items,
+                               zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, void *hip_stream);
+int zgpu_inflate_batch_sizes_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                                     zgpu_inflate_item *d_items, zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes,
+                                     void *hip_stream);
+int zgpu_inflate_batch_verify_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                                      uint32_t checks, zgpu_inflate_item *d_items, zgpu_inflate_batch_summary *d_summary, void *d_ws,
+                                      uint64_t ws_bytes, void *hip_stream);
+int zgpu_inflate_batch_packed_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
+                                      uint32_t checks, uint32_t align, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                      zgpu_inflate_item *d_items, zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes,
+                                      void *hip_stream);
+
 /* ---- BGZF decode (the encode side and the format: zgpu_bgzf_deflate_* above) ---- */
 /* The block index of a BGZF file in device memory, found on the device from the headers alone (zlib_amd/csrc/zgpu_bgzf.hip): d_in_offsets[0..n] =
  * where every block begins, entry n = in_bytes; d_out_offsets[0..n] = the exclusive sum of the blocks' ISIZE (entry n = *out_bytes).  Both arrays

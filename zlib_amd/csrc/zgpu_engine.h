@@ -230,10 +230,13 @@ struct InfLaunch {
     uint8_t *out; uint64_t out_cap; InfStatus *status;
     uint64_t last_chunk = ~0ull; uint32_t chunk_size = kWholeStream; ChunkMeta *meta = nullptr;
     const uint8_t *dict = nullptr; uint32_t dict_len = 0; uint32_t stream_mode = 1;
+    uint32_t checks = 0; // kInfBatchFold only: the checks to fold (bit 0 Adler-32, bit 1 CRC-32)
 };
 // kInfPieces: always the 32 KiB ring of 16-bit symbols; kInfSizes: no ring at all; kInfVerify: the 32 KiB ring and no destination -- `out` is not
-// used, `out_cap` carries the checks to compute (bit 0 Adler-32, bit 1 CRC-32) and `meta` takes one record per item: out_bytes, adler_a, adler_b, crc
-enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify };
+// used, `out_cap` carries the checks to compute (bit 0 Adler-32, bit 1 CRC-32) and `meta` takes one record per item: out_bytes, adler_a, adler_b, crc;
+// kInfBatchFold: kInfBatch that also folds what it stores (ring_kb counts, as for kInfBatch) -- `out` and `out_cap` are the destination's, `checks`
+// says what to fold, `meta` takes one record per item as for kInfVerify
+enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify, kInfBatchFold };
 constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes, kInfPieces or kInfVerify launch: the kind fixes the ring, the launcher does not look at the value
 int inflate_ring_kb(); // ZGPU_INF_RING_KB, read at EVERY call (the tests run the same streams through all three): 8, 16, anything else 32; not set: the build's default
 void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const SpecArgs &sp, hipStream_t st);

@@ -116,16 +116,28 @@ __device__ inline void block_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0
 // a bank.  The alternatives -- a table in lane registers read by cross-lane shuffles, a 1 KiB byte table (three workgroups a CU), the 4 KiB
 // slicing-by-4 table of zgpu_checksum.hip (three as well) -- have not been measured against it.
 // Termination: VERIFY adds the fold's loops, each bounded by the bytes of one flush (16 KiB), and a table build of two words per lane.
-template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false, bool VERIFY = false>
+// FOLD (zgpu_inflate_batch_*_enqueue, BATCH only, the rings BATCH has): the fused decode.  BATCH as it stands -- the same destination, the same dst_room / nofit
+// rules, the same status[] -- whose writer wave, in flush_to, first folds ring bytes [flushed, upto) into the running check values as VERIFY does and then
+// stores them as BATCH does.  The bytes are folded out of LDS in the flush that carries them to memory, so the output is never read again: no piece table, no
+// second pass, and no count the host would have to fetch to size one.  Which checks: `fold_checks` (bit 0 Adler-32, bit 1 CRC-32), an argument of its
+// own, since `out_cap` is the destination's here.  meta[c] takes what VERIFY writes.  An item that does not fit its range (nofit) goes on folding the
+// bytes that are not stored: its status is ZGPU_BUF_ERROR and nobody reads its check values.  With the 32 KiB ring every match finds its source in LDS
+// and the destination is write-only; with a small ring the far matches read the destination back as in BATCH, behind the wait that follows the flush's
+// stores (the fold stands in front of the stores and reads LDS only, so it changes nothing about what is in memory when).  The CRC lookup lies behind the
+// layout (InflateLdsFoldT): 512 bytes that leave the workgroups per CU of every ring as they are -- four, six, ten.
+// Termination: FOLD adds to BATCH exactly what VERIFY adds -- the fold's loops, each bounded by the bytes of one flush (half a ring, 16 KiB at most), and the table build --
+// and the flush's store loops stay BATCH's, bounded by the same bytes.
+template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false, bool VERIFY = false, bool FOLD = false>
 __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES : (!SPEC && RING <= 8192) ? 5 : 4) inflate_kernel_t(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ offsets,
                                                         uint64_t chunk0, uint32_t nchunks, uint64_t last_chunk, uint32_t chunk_size_arg,
                                                         uint8_t *__restrict__ out, uint64_t out_cap, InfStatus *status, ChunkMeta *meta,
-                                                        const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t stream_mode, SpecArgs sp)
+                                                        const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t stream_mode, SpecArgs sp, uint32_t fold_checks)
 {
     typedef typename std::conditional<SPEC, uint16_t, uint8_t>::type ring_t;
-    typedef typename std::conditional<SIZES, InflateLdsSizes, typename std::conditional<VERIFY, InflateLdsVerify, InflateLdsT<ring_t, RING>>::type>::type Lds;
+    typedef typename std::conditional<SIZES, InflateLdsSizes, typename std::conditional<VERIFY, InflateLdsVerify, typename std::conditional<FOLD, InflateLdsFoldT<RING>, InflateLdsT<ring_t, RING>>::type>::type>::type Lds;
     static_assert(!SIZES || (BATCH && !SPEC), "the sizing pass serves batch items");
-    static_assert(!VERIFY || (BATCH && !SPEC && !SIZES && RING == 32768), "the integrity test serves batch items, every match from the ring");
+    static_assert(!VERIFY || (BATCH && !SPEC && !SIZES && !FOLD && RING == 32768), "the integrity test serves batch items, every match from the ring");
+    static_assert(!FOLD || (BATCH && !SPEC && !SIZES && !VERIFY), "the fused decode serves batch items");
     constexpr uint32_t kOutRing = RING, kOutHalf = RING / 2; // (this kernel's ring, not the file's default)
     constexpr bool FAR = RING < 32768;
     static_assert(!(SPEC && FAR) && RING >= 4096 && (RING & (RING - 1)) == 0, "ring size");
@@ -458,9 +470,9 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     for (uint32_t i = lane; i < reach; i += 64) L.out[(kOutRing - reach + i) & (kOutRing - 1)] = dict[i];
     uint32_t flushed = 0; // bytes already copied from the LDS ring to the destination (a multiple of kOutHalf until the end)
     bool nofit = false;   // direct placement: the destination ended before the chunk did
-    FoldRun run{1, 0, 0}; // VERIFY: Adler-32 (halves) and CRC-32 of output bytes [0, flushed)
-    const uint32_t do_adler = VERIFY ? (uint32_t)out_cap & 1u : 0u, do_crc = VERIFY ? (uint32_t)out_cap & 2u : 0u;
-    if constexpr (VERIFY) {
+    FoldRun run{1, 0, 0}; // VERIFY, FOLD: Adler-32 (halves) and CRC-32 of output bytes [0, flushed)
+    const uint32_t want = VERIFY ? (uint32_t)out_cap : FOLD ? fold_checks : 0u, do_adler = want & 1u, do_crc = want & 2u;
+    if constexpr (VERIFY || FOLD) {
         if (do_crc) for (uint32_t i = lane; i < kCrcNibWords; i += 64) L.crc_nib[i] = crc_nib_entry(i);
     }
     uint8_t *dst = VERIFY ? nullptr : BATCH ? out + offsets[4 * gc + 2] : compact ? out + (uint64_t)c * kChunkMax : whole ? out : out + gc * (uint64_t)chunk_size;
@@ -513,6 +525,8 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
             flushed = upto;
             return;
         }
+        if constexpr (FOLD) // the fold in front of the store, out of the ring (flushed is a multiple of kOutHalf: 16-byte aligned; nbytes <= kOutHalf = kFoldMax)
+            run = verify_fold(reinterpret_cast<const uint8_t *>(L.out) + (flushed & (kOutRing - 1)), nbytes, L.crc_nib, lane, do_adler, do_crc, run);
         if ((uint64_t)flushed + nbytes > dst_room) { nofit = true; nbytes = dst_room > flushed ? (uint32_t)(dst_room - flushed) : 0; }
         const uint8_t *src_r = reinterpret_cast<const uint8_t *>(L.out) + (flushed & (kOutRing - 1)); // (the byte ring; SPEC has returned above)
         uint8_t *d = dst + flushed;
@@ -686,7 +700,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
         t_acc[6] = n_mat;
         for (int i_ = 0; i_ < 16; i_++) if (t_acc[i_]) atomicAdd(&inf_time[i_], t_acc[i_]);
 #endif
-        if constexpr (VERIFY) { meta[c].out_bytes = err ? 0 : o; meta[c].adler_a = run.a; meta[c].adler_b = run.b; meta[c].crc = run.crc; }
+        if constexpr (VERIFY || FOLD) { meta[c].out_bytes = err ? 0 : o; meta[c].adler_a = run.a; meta[c].adler_b = run.b; meta[c].crc = run.crc; }
         else if (meta) { meta[c].out_bytes = err ? 0 : o; meta[c].ntok = 0; meta[c].adler_a = 1; meta[c].adler_b = 0; meta[c].in_bytes = 0; meta[c].data_type = 2; }
     }
     } // !SIZES
@@ -758,16 +772,24 @@ void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const 
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 8192>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds8);
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsSpec));
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 32768, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsVerify));
+        hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 32768, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFoldT<32768>));
+        hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 16384, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFoldT<16384>));
+        hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 8192, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFoldT<8192>));
         opt_in = true;
     }
     // (one pointer type for all instantiations: __launch_bounds__ is no part of the type, so the 64-thread sizing kernel goes through it on purpose; `threads` counts)
     auto go = [&](decltype(&inflate_kernel_t<false>) kern, uint32_t threads, size_t lds) {
         hipLaunchKernelGGL(kern, dim3(a.nchunks), dim3(threads), lds, st, a.in, a.in_bytes, a.offsets, a.chunk0, a.nchunks, a.last_chunk, a.chunk_size, a.out, a.out_cap,
-                           a.status, a.meta, a.dict, a.dict_len, a.stream_mode, sp);
+                           a.status, a.meta, a.dict, a.dict_len, a.stream_mode, sp, a.checks);
     };
     if (kind == kInfPieces) go(inflate_kernel_t<true>, 128, sizeof(InflateLdsSpec));
     else if (kind == kInfSizes) go(inflate_kernel_t<false, ZGPU_INF_RING, true, true>, 64, sizeof(InflateLdsSizes));
     else if (kind == kInfVerify) go(inflate_kernel_t<false, 32768, true, false, true>, 128, sizeof(InflateLdsVerify));
+    else if (kind == kInfBatchFold) {
+        if (ring_kb == 8) go(inflate_kernel_t<false, 8192, true, false, false, true>, 128, sizeof(InflateLdsFoldT<8192>));
+        else if (ring_kb == 16) go(inflate_kernel_t<false, 16384, true, false, false, true>, 128, sizeof(InflateLdsFoldT<16384>));
+        else go(inflate_kernel_t<false, 32768, true, false, false, true>, 128, sizeof(InflateLdsFoldT<32768>));
+    }
     else if (kind == kInfBatch) {
         if (ring_kb == 8) go(inflate_kernel_t<false, 8192, true>, 128, kLds8);
         else if (ring_kb == 16) go(inflate_kernel_t<false, 16384, true>, 128, kLds16);

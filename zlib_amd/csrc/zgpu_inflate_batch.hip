@@ -3,8 +3,11 @@
 // in BATCH mode (one workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and
 // the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.  The sizing pass and the integrity test (further down) run
 // the same header kernel and the decoder in its SIZES / VERIFY mode: neither has a destination, the second still has its trailers compared.
+// The stream-ordered calls (zgpu_inflate_batch_*_enqueue, at the end) put the same chains on the caller's stream with the caller's workspace in place of
+// the engine's scratch and read nothing back; their decode runs the decoder in its FOLD mode, which checks the bytes while it stores them.
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
+#include "zgpu_inflate_batch_plan.h"
 #include "../../include/zamd_gpu.h"
 #include <cstring>
 #include <vector>
@@ -426,6 +429,125 @@ int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     if (nfailed) *nfailed = h[0];
     return ZGPU_OK;
 }
+
+// ---- stream-ordered calls (zgpu_inflate_batch_*_enqueue) ----
+// A call is hipMemsetAsync and kernel launches on one stream, in one chain, and returns: no synchronize, no allocation, no copy to or from the host, no
+// event, no second stream, no profiling span, and no device memory of the engine's -- the scratch is the caller's workspace, laid out by
+// zgpu_inflate_batch_plan.h.  What the blocking calls learn from a read-back is decided on the device instead: offsets that run backwards or leave their
+// buffer fail their item, not the call; a packed call's total > out_cap empties the decode stage's items; the counts go to the caller's summary.
+static_assert(sizeof(BatchItemState) == kWsStateBytes && sizeof(InfStatus) == kWsStatusBytes && sizeof(ChunkMeta) == kWsMetaBytes &&
+              sizeof(zgpu_inflate_item) == kWsItemBytes && 4 * sizeof(uint64_t) == kWsSegBytes, "zgpu_inflate_batch_plan.h states the record sizes as numbers");
+static_assert(ZGPU_BATCH_JOB_DECODE == kBatchJobDecode && ZGPU_BATCH_JOB_SIZES == kBatchJobSizes && ZGPU_BATCH_JOB_VERIFY == kBatchJobVerify &&
+              ZGPU_BATCH_JOB_PACKED == kBatchJobPacked, "the jobs of the public header are the plan's");
+
+// behind the header kernel, which has made such an item empty (it reads and writes nothing): the item's own verdict, ZGPU_STREAM_ERROR with no message.
+// The merge kernels leave a verdict that is not ZGPU_OK alone and the finish kernels report it with sizes 0, adler32 = 1, crc32 = 0.
+__global__ void __launch_bounds__(256) batch_bad_offsets_kernel(uint64_t in_bytes, const uint64_t *in_lo, const uint64_t *in_hi, uint64_t n, uint64_t out_cap, const uint64_t *out_lo,
+                                                                const uint64_t *out_hi, BatchItemState *items, unsigned long long *nbad)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint64_t lo = in_lo[k], hi = in_hi[k], ol = out_lo[k], oh = out_hi[k];
+    if (lo > hi || hi > in_bytes || ol > oh || oh > out_cap) { items[k].code = ZGPU_STREAM_ERROR; items[k].msg = 0; atomicAdd(nbad, 1ull); } // (batch_header_kernel's test)
+}
+
+// a packed call whose layout does not fit the destination: the decode stage's items are made empty before the decoder sees them, so that it writes nothing
+__global__ void __launch_bounds__(256) batch_packed_gate_kernel(const unsigned long long *total, uint64_t out_cap, uint64_t n, uint64_t *seg)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n || total[0] <= out_cap) return;
+    seg[4 * k] = 0; seg[4 * k + 1] = 0; seg[4 * k + 2] = 0; seg[4 * k + 3] = 0;
+}
+
+// batch_packed_merge_kernel with the overflow decided here: a layout that did not fit leaves every sizing record as it is
+__global__ void __launch_bounds__(256) batch_packed_merge_gated_kernel(const zgpu_inflate_item *__restrict__ decoded, uint64_t n, const unsigned long long *total, uint64_t out_cap,
+                                                                       zgpu_inflate_item *items, unsigned long long *nfailed)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    if (total[0] <= out_cap && items[k].code == ZGPU_OK) items[k] = decoded[k];
+    if (items[k].code != ZGPU_OK) atomicAdd(nfailed, 1ull);
+}
+
+__global__ void batch_summary_kernel(const unsigned long long *cnt, uint32_t failed_at, uint32_t packed, uint64_t out_cap, zgpu_inflate_batch_summary *s)
+{
+    const bool over = packed && cnt[kCntTotal] > out_cap; // (the merge has counted the sizing records' failures then)
+    s->nfailed = cnt[failed_at]; s->nbad_offsets = cnt[kCntBadOffsets]; s->total = packed ? cnt[kCntTotal] : 0;
+    s->overflow = over ? 1u : 0u; s->reserved = 0;
+}
+
+struct BatchWs { BatchScratch s; uint64_t *hi; zgpu_inflate_item *items2; };
+
+// what every enqueue call checks before it enqueues anything, and the workspace carved up.  *st: the stream of the call.  n == 0 needs no workspace
+static int batch_enqueue_begin(zgpu_engine *e, int job, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, const void *d_items,
+                               void *d_ws, uint64_t ws_bytes, void *hip_stream, BatchWs *w, hipStream_t *st)
+{
+    if (!e) return ZGPU_STREAM_ERROR;
+    if (wrap < (int)kWrapRaw || wrap > (int)kWrapAuto || (checks & ~3u) || n >= kWsMaxItems || (n && (!d_in_off || !d_items)) || (n && in_bytes && !d_in))
+        return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    *st = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->stream;
+    *w = BatchWs{};
+    if (n == 0) return ZGPU_OK;
+    const BatchWsPlan p = inflate_batch_ws_plan(job, n);
+    if (!d_ws || (reinterpret_cast<uintptr_t>(d_ws) & (kWsAlign - 1)) || p.total == 0 || ws_bytes < p.total) return fail(e, ZGPU_STREAM_ERROR, "inflate batch workspace: null, not 256-byte aligned or too small");
+    uint8_t *b = static_cast<uint8_t *>(d_ws);
+    w->s.seg = reinterpret_cast<uint64_t *>(b + p.seg.off); w->s.items = reinterpret_cast<BatchItemState *>(b + p.states.off);
+    w->s.status = reinterpret_cast<InfStatus *>(b + p.status.off); w->s.cnt = reinterpret_cast<unsigned long long *>(b + p.cnt.off);
+    if (p.meta.bytes) w->s.meta = reinterpret_cast<ChunkMeta *>(b + p.meta.off);
+    if (p.hi.bytes) w->hi = reinterpret_cast<uint64_t *>(b + p.hi.off);
+    if (p.items2.bytes) w->items2 = reinterpret_cast<zgpu_inflate_item *>(b + p.items2.off);
+    int cur = -1; // (the engine supplies the device; a thread that is on it already -- a stream capture, say -- is left alone)
+    ZGPU_HIP_CHECK(hipGetDevice(&cur));
+    if (cur != e->device) ZGPU_HIP_CHECK(hipSetDevice(e->device));
+    return ZGPU_OK;
+}
+
+static uint32_t batch_grid(uint64_t n) { return (uint32_t)((n + 255) / 256); }
+
+static int batch_enqueue_summary(zgpu_engine *e, const BatchWs &w, uint64_t n, uint32_t failed_at, bool packed, uint64_t out_cap, zgpu_inflate_batch_summary *d_summary, hipStream_t st)
+{
+    if (d_summary && n) hipLaunchKernelGGL(batch_summary_kernel, dim3(1), dim3(1), 0, st, w.s.cnt, failed_at, packed ? 1u : 0u, out_cap, d_summary);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    return ZGPU_OK;
+}
+
+// header kernel, the items with bad offsets marked (mark_bad: a packed call's decode stage leaves that to its sizing stage), the gate of a packed call,
+// the fused decoder in rounds of 65,536 items, the merge of the integrity test (an item is ONE piece of all its bytes, folded already), the finish kernel
+static void enqueue_fused_decode(const BatchScratch &s, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *in_lo, const uint64_t *in_hi, uint64_t n, int wrap, uint32_t checks,
+                                 uint8_t *d_out, uint64_t out_cap, const uint64_t *out_lo, const uint64_t *out_hi, zgpu_inflate_item *d_items, unsigned long long *nfailed, bool mark_bad,
+                                 const unsigned long long *gate_total, hipStream_t st)
+{
+    const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
+    const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    const uint32_t ngrid = batch_grid(n);
+    const int ring_kb = inflate_ring_kb(); // (the ring the blocking decode would pick: the small rings serve items as they serve chunks)
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, in_lo, in_hi, n, (uint32_t)wrap, out_cap, out_lo, out_hi, s.seg, s.items,
+                       reinterpret_cast<uint32_t *>(s.cnt + kCntHeaderFlag));
+    if (mark_bad) hipLaunchKernelGGL(batch_bad_offsets_kernel, dim3(ngrid), dim3(256), 0, st, in_bytes, in_lo, in_hi, n, out_cap, out_lo, out_hi, s.items, s.cnt + kCntBadOffsets);
+    if (gate_total) hipLaunchKernelGGL(batch_packed_gate_kernel, dim3(ngrid), dim3(256), 0, st, gate_total, out_cap, n, s.seg);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        InfLaunch a{d_in, in_bytes, s.seg, c0, nb, d_out, out_cap, s.status + c0};
+        a.meta = s.meta + c0; a.checks = do_adler | (do_crc << 1);
+        launch_inflate_decode(kInfBatchFold, ring_kb, a, SpecArgs{}, st);
+    }
+    hipLaunchKernelGGL(batch_verify_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
+    launch_batch_finish(s.items, n, s.meta, d_in, do_adler, do_crc, d_items, nfailed, st);
+}
+
+// the sizing pass's chain (inflate_batch_sizes_launch) with the workspace in place of the scratch
+static void enqueue_sizes(const BatchScratch &s, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, hipStream_t st)
+{
+    const uint32_t ngrid = batch_grid(n);
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, d_in_off + 1, n, (uint32_t)wrap, in_bytes, d_in_off, d_in_off + 1, s.seg, s.items,
+                       reinterpret_cast<uint32_t *>(s.cnt + kCntHeaderFlag));
+    hipLaunchKernelGGL(batch_bad_offsets_kernel, dim3(ngrid), dim3(256), 0, st, in_bytes, d_in_off, d_in_off + 1, n, in_bytes, d_in_off, d_in_off + 1, s.items, s.cnt + kCntBadOffsets);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        launch_inflate_decode(kInfSizes, kInfNoRing, InfLaunch{d_in, in_bytes, s.seg, c0, nb, nullptr, 0, s.status + c0}, SpecArgs{}, st);
+    }
+    hipLaunchKernelGGL(batch_sizes_finish_kernel, dim3(ngrid), dim3(256), 0, st, s.items, s.status, n, d_items, s.cnt + kCntFailed);
+}
 } // namespace zgpu
 
 using namespace zgpu;
@@ -574,6 +696,89 @@ int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_b
     bool dense = align == 1; // every item succeeded and no alignment leaves gaps between them
     for (uint64_t k = 0; k < n && dense; k++) dense = items[k].code == ZGPU_OK;
     return batch_copy_back(e, dense, 0, *total, out_offsets, items, n, static_cast<uint8_t *>(out));
+}
+
+// ---- the stream-ordered entry points (include/zamd_gpu.h) ----
+uint64_t zgpu_inflate_batch_workspace_bytes(int job, uint64_t n) { return inflate_batch_ws_bytes(job, n); }
+
+int zgpu_inflate_batch_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks, void *d_out, uint64_t out_cap,
+                               const uint64_t *d_out_offsets, zgpu_inflate_item *d_items, zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, void *hip_stream)
+{
+    BatchWs w;
+    hipStream_t st;
+    if (e && n && (!d_out_offsets || (out_cap && !d_out))) return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_enqueue_begin(e, kBatchJobDecode, d_in, in_bytes, d_in_offsets, n, wrap, checks, d_items, d_ws, ws_bytes, hip_stream, &w, &st)) return rc;
+    if (d_summary) ZGPU_HIP_CHECK(hipMemsetAsync(d_summary, 0, sizeof *d_summary, st));
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipMemsetAsync(w.s.cnt, 0, kWsCntBytes, st));
+    enqueue_fused_decode(w.s, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, d_in_offsets + 1, n, wrap, checks, static_cast<uint8_t *>(d_out), out_cap, d_out_offsets,
+                         d_out_offsets + 1, d_items, w.s.cnt + kCntFailed, true, nullptr, st);
+    return batch_enqueue_summary(e, w, n, kCntFailed, false, 0, d_summary, st);
+}
+
+int zgpu_inflate_batch_sizes_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, zgpu_inflate_item *d_items,
+                                     zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, void *hip_stream)
+{
+    BatchWs w;
+    hipStream_t st;
+    if (int rc = batch_enqueue_begin(e, kBatchJobSizes, d_in, in_bytes, d_in_offsets, n, wrap, 0, d_items, d_ws, ws_bytes, hip_stream, &w, &st)) return rc;
+    if (d_summary) ZGPU_HIP_CHECK(hipMemsetAsync(d_summary, 0, sizeof *d_summary, st));
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipMemsetAsync(w.s.cnt, 0, kWsCntBytes, st));
+    enqueue_sizes(w.s, static_cast<const uint8_t *>(d_in), in_bytes, d_in_offsets, n, wrap, d_items, st);
+    return batch_enqueue_summary(e, w, n, kCntFailed, false, 0, d_summary, st);
+}
+
+// the integrity test's chain (inflate_batch_verify_run) with the workspace in place of the scratch
+int zgpu_inflate_batch_verify_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks, zgpu_inflate_item *d_items,
+                                      zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, void *hip_stream)
+{
+    BatchWs w;
+    hipStream_t st;
+    if (int rc = batch_enqueue_begin(e, kBatchJobVerify, d_in, in_bytes, d_in_offsets, n, wrap, checks, d_items, d_ws, ws_bytes, hip_stream, &w, &st)) return rc;
+    if (d_summary) ZGPU_HIP_CHECK(hipMemsetAsync(d_summary, 0, sizeof *d_summary, st));
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipMemsetAsync(w.s.cnt, 0, kWsCntBytes, st));
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    const BatchScratch &s = w.s;
+    const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
+    const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    const uint32_t ngrid = batch_grid(n);
+    hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, in, in_bytes, d_in_offsets, d_in_offsets + 1, n, (uint32_t)wrap, in_bytes, d_in_offsets, d_in_offsets + 1, s.seg,
+                       s.items, reinterpret_cast<uint32_t *>(s.cnt + kCntHeaderFlag));
+    hipLaunchKernelGGL(batch_bad_offsets_kernel, dim3(ngrid), dim3(256), 0, st, in_bytes, d_in_offsets, d_in_offsets + 1, n, in_bytes, d_in_offsets, d_in_offsets + 1, s.items,
+                       s.cnt + kCntBadOffsets);
+    for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
+        const uint32_t nb = (uint32_t)(n - c0 < 65536 ? n - c0 : 65536);
+        InfLaunch a{in, in_bytes, s.seg, c0, nb, nullptr, (uint64_t)(do_adler | (do_crc << 1)), s.status + c0};
+        a.meta = s.meta + c0;
+        launch_inflate_decode(kInfVerify, kInfNoRing, a, SpecArgs{}, st);
+    }
+    hipLaunchKernelGGL(batch_verify_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
+    launch_batch_finish(s.items, n, s.meta, in, do_adler, do_crc, d_items, s.cnt + kCntFailed, st);
+    return batch_enqueue_summary(e, w, n, kCntFailed, false, 0, d_summary, st);
+}
+
+// sizing pass, layout, fused decode into that layout, merge: one chain.  Whether the layout fits out_cap is decided where the total is, on the device
+int zgpu_inflate_batch_packed_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap, uint32_t checks, uint32_t align, void *d_out,
+                                      uint64_t out_cap, uint64_t *d_out_offsets, zgpu_inflate_item *d_items, zgpu_inflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes,
+                                      void *hip_stream)
+{
+    BatchWs w;
+    hipStream_t st;
+    if (e && (align == 0 || align > 256 || (align & (align - 1)) || (n && !d_out_offsets) || (n && out_cap && !d_out))) return fail(e, ZGPU_STREAM_ERROR, "bad inflate batch arguments");
+    if (int rc = batch_enqueue_begin(e, kBatchJobPacked, d_in, in_bytes, d_in_offsets, n, wrap, checks, d_items, d_ws, ws_bytes, hip_stream, &w, &st)) return rc;
+    if (d_summary) ZGPU_HIP_CHECK(hipMemsetAsync(d_summary, 0, sizeof *d_summary, st));
+    if (n == 0) return ZGPU_OK;
+    ZGPU_HIP_CHECK(hipMemsetAsync(w.s.cnt, 0, kWsCntBytes, st));
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    enqueue_sizes(w.s, in, in_bytes, d_in_offsets, n, wrap, d_items, st);
+    hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(1024), 0, st, d_items, n, (uint64_t)align, d_out_offsets, w.hi, w.s.cnt + kCntTotal);
+    // (the decode stage takes seg, the states and the status over; its records go to the second set until the merge)
+    enqueue_fused_decode(w.s, in, in_bytes, d_in_offsets, d_in_offsets + 1, n, wrap, checks, static_cast<uint8_t *>(d_out), out_cap, d_out_offsets, w.hi, w.items2,
+                         w.s.cnt + kCntDecodeFailed, false, w.s.cnt + kCntTotal, st);
+    hipLaunchKernelGGL(batch_packed_merge_gated_kernel, dim3(batch_grid(n)), dim3(256), 0, st, w.items2, n, w.s.cnt + kCntTotal, out_cap, d_items, w.s.cnt + kCntMerged);
+    return batch_enqueue_summary(e, w, n, kCntMerged, true, out_cap, d_summary, st);
 }
 #pragma GCC visibility pop
 }

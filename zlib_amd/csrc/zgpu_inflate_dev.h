@@ -59,6 +59,10 @@ struct InflateLdsSizes {
 struct InflateLdsVerify : InflateLdsT<uint8_t, 32768> {
     uint32_t crc_nib[kCrcNibWords]; // eight nibble tables of 16 words (crc_nib_entry, zgpu_common.h)
 };
+// The fused batch decode (inflate_kernel_t<..., FOLD>): the decoder's layout with the ring the call picks -- the rings BATCH serves -- and the CRC lookup behind it
+template <uint32_t kRing> struct InflateLdsFoldT : InflateLdsT<uint8_t, kRing> {
+    uint32_t crc_nib[kCrcNibWords];
+};
 using InflateLdsSpec = InflateLdsT<uint16_t>;
 constexpr uint32_t kScanBytes = 4096; // the block finder reads the input through LDS in pieces of this size (+ the 16 bytes a bit offset at the end reaches into)
 constexpr uint32_t kFindList = 1024; // candidates listed between two rounds of the second sieve (a group of 2048 offsets yields 683 at most: one in three)
@@ -66,6 +70,9 @@ using InflateLdsFind = InflateLdsT<uint8_t, kScanBytes + 64 + kFindList * 2>;
 static_assert(sizeof(InflateLdsFind) <= 14336, "eleven finder waves per CU");
 static_assert(sizeof(InflateLds) <= 40448, "four segments per CU");
 static_assert(sizeof(InflateLdsVerify) <= 40448 && 4 * sizeof(InflateLdsVerify) <= 160 * 1024, "the integrity test: four workgroups per CU, as the decoder it is");
+static_assert(sizeof(InflateLdsFoldT<32768>) <= 40448 && 4 * sizeof(InflateLdsFoldT<32768>) <= 160 * 1024, "the fused batch decode, 32 KiB ring: four workgroups per CU");
+static_assert(6 * sizeof(InflateLdsFoldT<16384>) <= 160 * 1024, "the fused batch decode, 16 KiB ring: six workgroups per CU, as the decoder with that ring");
+static_assert(10 * sizeof(InflateLdsFoldT<8192>) <= 160 * 1024, "the fused batch decode, 8 KiB ring: ten workgroups per CU, as the decoder with that ring (five waves per SIMD)");
 static_assert(10 * sizeof(InflateLdsT<uint8_t, 8192>) <= 160 * 1024, "ten segments per CU with the 8 KiB ring (five waves per SIMD: 96 registers)");
 static_assert(sizeof(InflateLdsSpec) <= 81920, "two workgroups per CU");
 static_assert(24 * sizeof(InflateLdsSizes) <= 160 * 1024, "the sizing pass: twenty-four one-wave workgroups per CU (six waves per SIMD)");

@@ -13,6 +13,7 @@ LZ_AUTO, LZ_SERIAL, LZ_PARALLEL, LZ_SORTED, LZ_WALK, LZ_FAST, LZ_FASTWIN = 0, 1,
 CHECK_ADLER32, CHECK_CRC32 = 1, 2  # zgpu_inflate_set_checks
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP, WRAP_AUTO = 0, 1, 2, 3  # zgpu_inflate_batch_*
 _WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP, "auto": WRAP_AUTO}
+JOB_DECODE, JOB_SIZES, JOB_VERIFY, JOB_PACKED = 0, 1, 2, 3  # zgpu_inflate_batch_workspace_bytes
 BUF_ERROR = -5  # ZGPU_BUF_ERROR: what a packed batch decode answers when its output is too small
 STAGES = ["chain", "match", "parse", "lz_serial", "huffman", "stitch", "inflate"]
 CHUNK = 65536
@@ -49,6 +50,11 @@ class InflateResult(C.Structure):
 class InflateItem(C.Structure):
     """zgpu_inflate_item: the verdict of one item of a batch inflate."""
     _fields_ = [("code", C.c_int32), ("msg", C.c_uint32), ("out_bytes", C.c_uint64), ("in_used", C.c_uint64), ("adler32", C.c_uint32), ("crc32", C.c_uint32)]
+
+
+class InflateBatchSummary(C.Structure):
+    """zgpu_inflate_batch_summary: what a stream-ordered batch inflate call (zgpu_inflate_batch_*_enqueue) leaves in device memory besides the records."""
+    _fields_ = [("nfailed", C.c_uint64), ("nbad_offsets", C.c_uint64), ("total", C.c_uint64), ("overflow", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class DeflateItem(C.Structure):
@@ -119,6 +125,12 @@ def load_library():
     L.zgpu_inflate_batch_packed_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, u32, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.zgpu_inflate_batch_verify_device.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, C.POINTER(u64), vp]
     L.zgpu_inflate_batch_verify_host.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, C.POINTER(u64)]
+    L.zgpu_inflate_batch_workspace_bytes.argtypes = [C.c_int, u64]
+    L.zgpu_inflate_batch_workspace_bytes.restype = u64
+    L.zgpu_inflate_batch_enqueue.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, u64, vp, vp, vp, vp, u64, vp]
+    L.zgpu_inflate_batch_sizes_enqueue.argtypes = [vp, vp, u64, vp, u64, C.c_int, vp, vp, vp, u64, vp]
+    L.zgpu_inflate_batch_verify_enqueue.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, vp, vp, vp, u64, vp]
+    L.zgpu_inflate_batch_packed_enqueue.argtypes = [vp, vp, u64, vp, u64, C.c_int, u32, u32, vp, u64, vp, vp, vp, vp, u64, vp]
     L.zgpu_bgzf_verify_device.argtypes = [vp, vp, u64, vp, C.POINTER(InflateResult), vp]
     L.zgpu_bgzf_verify_host.argtypes = [vp, vp, u64, vp, C.POINTER(InflateResult)]
     L.zgpu_bgzf_bound.argtypes = [u64, u32]
@@ -451,6 +463,33 @@ class Engine:
                                                             C.byref(failed), stream))
         self.last_failed = failed.value
         return failed.value
+
+    # ---- stream-ordered batch inflate ----
+    def inflate_batch_workspace_bytes(self, job, n):
+        """Bytes of caller-owned device workspace a zgpu_inflate_batch_*_enqueue call of `job` (JOB_*) needs for n items; it grows with n only."""
+        return int(self.L.zgpu_inflate_batch_workspace_bytes(job, n))
+
+    def inflate_batch_enqueue(self, d_in, in_bytes, d_in_offsets, n, d_out, out_cap, d_out_offsets, d_items, d_ws, ws_bytes, wrap="zlib", checks=0, d_summary=None, stream=None):
+        """Device pointers as ints, as inflate_batch_device takes them; d_ws: 256-byte aligned workspace, d_summary: room for an InflateBatchSummary or None.
+        Enqueues the decode on `stream` (an int; None: the engine's) and returns: nothing is read back, the results are there when the stream gets there."""
+        self._check(self.L.zgpu_inflate_batch_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks, d_out, out_cap, d_out_offsets,
+                                                      d_items, d_summary, d_ws, ws_bytes, stream))
+
+    def inflate_batch_sizes_enqueue(self, d_in, in_bytes, d_in_offsets, n, d_items, d_ws, ws_bytes, wrap="zlib", d_summary=None, stream=None):
+        """The sizing pass, enqueued (see inflate_batch_enqueue)."""
+        self._check(self.L.zgpu_inflate_batch_sizes_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, d_items, d_summary, d_ws, ws_bytes,
+                                                            stream))
+
+    def inflate_batch_verify_enqueue(self, d_in, in_bytes, d_in_offsets, n, d_items, d_ws, ws_bytes, wrap="zlib", checks=0, d_summary=None, stream=None):
+        """The integrity test, enqueued (see inflate_batch_enqueue)."""
+        self._check(self.L.zgpu_inflate_batch_verify_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks, d_items, d_summary, d_ws,
+                                                             ws_bytes, stream))
+
+    def inflate_batch_packed_enqueue(self, d_in, in_bytes, d_in_offsets, n, d_out, out_cap, d_out_offsets, d_items, d_ws, ws_bytes, wrap="zlib", checks=0, align=1, d_summary=None,
+                                     stream=None):
+        """The packed decode, enqueued: d_out_offsets receives n + 1 uint64; whether the layout fit out_cap is the summary's `overflow` (see inflate_batch_enqueue)."""
+        self._check(self.L.zgpu_inflate_batch_packed_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks, align, d_out, out_cap,
+                                                             d_out_offsets, d_items, d_summary, d_ws, ws_bytes, stream))
 
     # ---- BGZF (blocked gzip) ----
     def bgzf_deflate_host(self, data, level=6, block_size=0, strategy=0, want_offsets=False):
