@@ -33,7 +33,7 @@ enum {
     MAXBLBITS = 7, EOB = 256
 };
 
-typedef struct { uint16_t good, lazy, nice, chain; int mode; } level_cfg; /* mode 0 store 1 fast 2 slow */
+typedef struct { uint16_t good, lazy, nice; uint32_t chain; int mode; } level_cfg; /* mode 0 store 1 fast 2 slow; chain: max_chain_length is a uInt (deflateTune takes any) */
 static const level_cfg LEVELS[10] = {
     {0, 0, 0, 0, 0},       {4, 4, 8, 4, 1},        {4, 5, 16, 8, 1},      {4, 6, 32, 32, 1},
     {4, 4, 16, 16, 2},     {8, 16, 32, 32, 2},     {8, 16, 128, 128, 2},  {8, 32, 128, 256, 2},
@@ -502,14 +502,24 @@ size_t ora_deflate_chunk_d(const uint8_t *in, size_t n, size_t dict_len, int lev
     return chunk_with_row(in, n, dict_len, level, NULL, strategy, pos0_matchable, is_last, out, cap, tokens, info);
 }
 
+/* deflateTune's row.  max_chain 0 is taken as it is: longest_match's `--chain_length != 0` counts down past zero, the search is unbounded
+ * (deflate.c:1163); so is the quarter (chain >> 2) of a max_chain below 4. */
+static int tuned_row(level_cfg *row, int level, int good_length, int max_lazy, int nice_length, int max_chain)
+{
+    if (level < 1 || level > 9 || good_length < 0 || max_lazy < 0 || nice_length < 0 || max_chain < 0 ||
+        good_length > 0xffff || max_lazy > 0xffff || nice_length > 0xffff) return 0;
+    row->good = (uint16_t)good_length; row->lazy = (uint16_t)max_lazy; row->nice = (uint16_t)nice_length; row->chain = (uint32_t)max_chain;
+    row->mode = LEVELS[level].mode;
+    return 1;
+}
+
 /* ora_deflate_chunk_s behind deflateTune (deflate.c:454-470): the four parameters replace the level's row, the level keeps its compress function
  * (deflate_fast for 1-3, deflate_slow for 4-9; level 0 stores and has no use for them). */
 size_t ora_deflate_chunk_t(const uint8_t *in, size_t n, int level, int strategy, int good_length, int max_lazy, int nice_length, int max_chain,
                            int pos0_matchable, int is_last, uint8_t *out, size_t cap, ora_token *tokens, ora_chunk_info *info)
 {
-    if (level < 1 || level > 9 || good_length < 0 || max_lazy < 0 || nice_length < 0 || max_chain < 1 ||
-        good_length > 0xffff || max_lazy > 0xffff || nice_length > 0xffff || max_chain > 0xffff) return 0;
-    const level_cfg row = {(uint16_t)good_length, (uint16_t)max_lazy, (uint16_t)nice_length, (uint16_t)max_chain, LEVELS[level].mode};
+    level_cfg row;
+    if (!tuned_row(&row, level, good_length, max_lazy, nice_length, max_chain)) return 0;
     return chunk_with_row(in, n, 0, level, &row, strategy, pos0_matchable, is_last, out, cap, tokens, info);
 }
 
@@ -682,7 +692,7 @@ size_t ora_deflate_cont(const uint8_t *in, size_t n, size_t dict_len, int level,
     return ora_deflate_cont_p(in, n, dict_len, level, strategy, cuts, kinds, NULL, NULL, ncuts, out, cap);
 }
 
-static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
+static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, const level_cfg *row, int strategy, const uint32_t *cuts, const int32_t *kinds,
                        const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens);
 
 /* The same with deflateParams() (deflate.c:416-451) in front of some calls: plevel[k] / pstrategy[k] >= 0 are set before call k (k == ncuts: before the
@@ -691,16 +701,25 @@ static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, 
 size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
                           const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap)
 {
-    return cont_run(in, n, dict_len, level, strategy, cuts, kinds, plevel, pstrategy, ncuts, out, cap, NULL, NULL);
+    return cont_run(in, n, dict_len, level, NULL, strategy, cuts, kinds, plevel, pstrategy, ncuts, out, cap, NULL, NULL);
 }
 
 /* What compress2() emits (no dictionary, one Z_FINISH call), with the token stream: tokens has room for n entries, *ntokens receives their number. */
 size_t ora_deflate_cont_tokens(const uint8_t *in, size_t n, int level, int strategy, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens)
 {
-    return cont_run(in, n, 0, level, strategy, NULL, NULL, NULL, NULL, 0, out, cap, tokens, ntokens);
+    return cont_run(in, n, 0, level, NULL, strategy, NULL, NULL, NULL, NULL, 0, out, cap, tokens, ntokens);
 }
 
-static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
+/* The same behind deflateTune (called before the first byte: the row holds for the whole stream). */
+size_t ora_deflate_cont_tokens_t(const uint8_t *in, size_t n, int level, int strategy, int good_length, int max_lazy, int nice_length, int max_chain,
+                                 uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens)
+{
+    level_cfg row;
+    if (!tuned_row(&row, level, good_length, max_lazy, nice_length, max_chain)) return 0;
+    return cont_run(in, n, 0, level, &row, strategy, NULL, NULL, NULL, NULL, 0, out, cap, tokens, ntokens);
+}
+
+static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, const level_cfg *row, int strategy, const uint32_t *cuts, const int32_t *kinds,
                        const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens)
 {
     if (n >= 0xfff00000u || dict_len > n || (dict_len != 0 && (dict_len < MINM || dict_len > MAXDIST))) return 0;
@@ -708,7 +727,7 @@ static size_t cont_run(const uint8_t *in, size_t n, size_t dict_len, int level, 
     make_tables();
     enc *e = (enc *)calloc(1, sizeof(enc));
     if (!e) return 0;
-    e->in = in; e->n = (uint32_t)dict_len; e->level = level; e->strategy = strategy; e->cfg = &LEVELS[level];
+    e->in = in; e->n = (uint32_t)dict_len; e->level = level; e->strategy = strategy; e->cfg = row ? row : &LEVELS[level];
     e->bs.out = out; e->bs.cap = cap; e->data_type = 2; e->last_eob = 8; e->tok_out = tokens;
     new_block(e);
     e->start = (uint32_t)dict_len; e->block_start = e->start;

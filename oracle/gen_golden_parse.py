@@ -4,7 +4,8 @@
 Per case of oracle/parsecases.py: the input's length and SHA-256/16 (the inputs are built again from the catalogue, not stored) and, per
 configuration the case is meant for, length and SHA-256/16 of the reference's raw stream -- an independent chunk with both endings
 ([Z_FULL_FLUSH, Z_FINISH]), or, for a case placed on a tile edge, the one continuous stream ("cont": the same for the cases placed on a
-block or window edge, which go through both).  Tuned rows go through deflateTune, position-0
+block or window edge, which go through both).  Tuned rows go through deflateTune (chunks: in front of the one call; a continuous stream: right
+behind deflateInit2), position-0
 matchable chunks through a three-byte preset dictionary (refzlib.deflate_chunk_raw)."""
 import ctypes as C
 import hashlib
@@ -47,18 +48,18 @@ def rows_of(c):
     for cfg in c.cfgs:
         if c.cont:
             k = P.CONFIGS[cfg]
-            assert not (k.tune or k.p0)
-            z = R.deflate_calls(c.data, k.level, (), wbits=-15, strategy=k.strategy)
+            assert not k.p0
+            z = R.deflate_calls(c.data, k.level, (), wbits=-15, strategy=k.strategy, tune=k.tune)
             out[cfg] = [len(z), h16(z)]
         else:
             out[cfg] = [[len(z), h16(z)] for z in (ref_chunk(c.data, cfg, 0), ref_chunk(c.data, cfg, 1))]
     row = {"data": [len(c.data), h16(c.data)], "out": out}
-    if c.family == "placed" and not c.cont:  # the cases on a block or window edge as ONE continuous stream as well (the level's own row only)
+    if c.family == "placed" and not c.cont:  # the cases on a block or window edge as ONE continuous stream as well (a level's own row, or a tuned row of CONT_EDGE)
         cont = {}
         for cfg in c.cfgs:
             k = P.CONFIGS[cfg]
-            if not (k.tune or k.p0):
-                z = R.deflate_calls(c.data, k.level, (), wbits=-15, strategy=k.strategy)
+            if not (k.tune or k.p0) or cfg in P.CONT_EDGE:
+                z = R.deflate_calls(c.data, k.level, (), wbits=-15, strategy=k.strategy, tune=k.tune)
                 cont[cfg] = [len(z), h16(z)]
         if cont:
             row["cont"] = cont

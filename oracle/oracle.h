@@ -81,6 +81,9 @@ size_t ora_deflate_cont(const uint8_t *in, size_t n, size_t dict_len, int level,
 
 /* ora_deflate_cont without cuts or dictionary (compress2), with the tokens: room for n of them, *ntokens = how many. */
 size_t ora_deflate_cont_tokens(const uint8_t *in, size_t n, int level, int strategy, uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens);
+/* ... behind a deflateTune in front of the first byte (any four non-negative values; max_chain 0 and a quarter of 0 never run out). */
+size_t ora_deflate_cont_tokens_t(const uint8_t *in, size_t n, int level, int strategy, int good_length, int max_lazy, int nice_length, int max_chain,
+                                 uint8_t *out, size_t cap, ora_token *tokens, uint32_t *ntokens);
 
 size_t ora_deflate_cont_p(const uint8_t *in, size_t n, size_t dict_len, int level, int strategy, const uint32_t *cuts, const int32_t *kinds,
                           const int32_t *plevel, const int32_t *pstrategy, size_t ncuts, uint8_t *out, size_t cap);

@@ -50,6 +50,9 @@ def lib():
         L.ora_deflate_cont_p.restype = C.c_size_t
         L.ora_deflate_cont_tokens.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ora_deflate_cont_tokens.restype = C.c_size_t
+        L.ora_deflate_cont_tokens_t.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.POINTER(C.c_uint32)]
+        L.ora_deflate_cont_tokens_t.restype = C.c_size_t
         L.ora_deflate_bound.argtypes = [C.c_size_t, C.c_size_t]
         L.ora_deflate_bound.restype = C.c_size_t
         L.ora_adler32.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t]
@@ -85,7 +88,8 @@ def tree_counters() -> dict:
 
 
 def deflate_chunk(chunk: bytes, level: int, is_last: bool, pos0_matchable: bool = False, want_tokens=False, strategy: int = 0, tune=None):
-    """tune: (good_length, max_lazy, nice_length, max_chain) as deflateTune would set them in place of the level's row."""
+    """tune: (good_length, max_lazy, nice_length, max_chain) as deflateTune would set them in place of the level's row: any four values that are
+    not negative (a max_chain of 0, or a quarter of it that is 0, is a search that never runs out of budget, as in the reference)."""
     L = lib()
     cap = len(chunk) + 512
     out = C.create_string_buffer(cap)
@@ -207,14 +211,18 @@ def deflate_cont(data: bytes, level: int, calls=(), strategy: int = 0, dictionar
     return out.raw[:n]
 
 
-def deflate_cont_tokens(data: bytes, level: int, strategy: int = 0):
-    """(the continuous raw stream of compress2, its tokens as a numpy record array with the fields dist and lc)."""
+def deflate_cont_tokens(data: bytes, level: int, strategy: int = 0, tune=None):
+    """(the continuous raw stream of compress2, its tokens as a numpy record array with the fields dist and lc); tune: deflateTune's row, set in
+    front of the first byte."""
     import numpy as np
     cap = len(data) + (len(data) >> 3) + 1024
     out = C.create_string_buffer(cap)
     toks = (Token * max(len(data), 1))()
     nt = C.c_uint32(0)
-    n = lib().ora_deflate_cont_tokens(data, len(data), level, strategy, out, cap, C.cast(toks, C.c_void_p), C.byref(nt))
+    if tune:
+        n = lib().ora_deflate_cont_tokens_t(data, len(data), level, strategy, *tune, out, cap, C.cast(toks, C.c_void_p), C.byref(nt))
+    else:
+        n = lib().ora_deflate_cont_tokens(data, len(data), level, strategy, out, cap, C.cast(toks, C.c_void_p), C.byref(nt))
     if n == 0:
         raise RuntimeError("oracle deflate_cont_tokens failed")
     t = np.frombuffer(toks, dtype=np.dtype([("dist", "<u2"), ("lc", "u1"), ("pad", "u1")]), count=nt.value)

@@ -4,7 +4,7 @@ deflate_fast :1448-1546, deflate_slow :1554-1674).  TEST INFRASTRUCTURE, pure Py
 Shared by oracle/gen_golden_parse.py and the tests.  catalogue() returns Case rows:
 
   name      unique
-  family    chain | quarter | nice | clip | tie | stairs | lazy | short | reach | fast | placed
+  family    chain | quarter | nice | clip | tie | stairs | lazy | short | reach | fast | hand | placed
   data      the bytes (one chunk of at most 64 KiB; placed continuous cases are one stream of up to 96 KiB)
   cfgs      the configurations (keys of CONFIGS) the case is meant for
   claims    {cfg: [(position, token), ...]}: the token the reference must START at that position, (dist, len) or LIT
@@ -32,9 +32,24 @@ What is left out, and why:
   * nice_length of levels 8 and 9 is 258 = MAX_MATCH: there is no "nice + 1" and "nice - 1 in front of 258" is no threshold, no nice rows there;
   * the 255-step staircase of disjoint strings would span 33150 bytes, more than MAX_DIST: it is built from a run (every position of a run of
     257 equal bytes is a candidate one byte shorter than the one behind it); the 70-step one exists in both forms;
-  * deflateTune rows are chunk cases only: the continuous cases (tile edges, and the block / window edge cases a second time) use the rows of levels 1-9;
-  * a max_chain below 4 (a quarter budget of 0, which the reference treats as unbounded) has no row yet;
-  * other memLevel / windowBits change the hash: this catalogue is for the default geometry only."""
+  * the level-like deflateTune rows (T13, T100, T33) and every tuned deflate_fast row are chunk cases only (the engine serves a tuned level 1-3 stream in
+    chunks); the continuous cases (tile edges, and the block / window edge cases a second time) use the rows of levels 1-9 and the rows of CONT_EDGE;
+  * other memLevel / windowBits change the hash: this catalogue is for the default geometry only;
+  * negative arguments of deflateTune (the restatement takes unsigned values).
+
+The rows no level's row resembles (EDGE_SLOW, EDGE_FAST; edge_catalogue).  The reference takes any four integers, and the device code rests on relations
+that hold in all nine rows of the level table; each of these rows breaks one:
+  * max_chain 1..3: the quarter budget is 0, which never runs out -- with good_length bytes in hand the prize is found behind max_chain + 1, 8, 40 and
+    DEEP decoys, with one byte fewer in hand behind max_chain - 1 and not behind max_chain; max_chain 0 and 70000: the full budget never runs out either;
+  * good_length 0 and 2 (quartered with nothing in hand: found at depth 32, not at 33, of 128), 3 (quartered behind any match), 300 (never);
+  * max_lazy 0 and 2 (no search at all: repeats are literals), 3 (a search only with nothing in hand: the longer match one position on is not taken);
+  * max_lazy > nice_length (hand_case): with nice_length..max_lazy - 1 bytes in hand a candidate no longer than that is passed over and a farther, longer
+    one taken; the first one that IS longer ends the walk.  The "hole" cases have a near candidate that shares nice_length bytes or more with the probe,
+    differs in one byte and agrees again in the two bytes a search with h bytes in hand checks first;
+  * nice_length 0, 2, 3 (the first candidate that improves ends the walk) and 1000 (no walk ends on a length);
+  * deflate_fast: max_insert_length 0, 3, nice - 1, nice and 258 (inside_case: a probe whose only candidate lies inside a match of exactly m bytes), and
+    good_length 2 (every search quartered: budgets 1 and, for max_chain 3, none).
+A ladder has at most 40 decoys but for the DEEP one per unbounded search (300: deeper than any budget of these rows, cheap for a one-lane kernel)."""
 from collections import namedtuple
 
 import numpy as np
@@ -60,7 +75,30 @@ CONFIGS.update({
 })
 SLOW = ["L4", "L5", "L6", "L7", "L8", "L9", "T13", "T100", "T33"]
 FAST = ["L1", "L2", "L3"]
-CONT_CFGS = ["L%d" % k for k in range(1, 10)]  # (one continuous stream: the levels' own rows; deflateTune rows go through chunks only)
+CONT_CFGS = ["L%d" % k for k in range(1, 10)]  # (one continuous stream: the levels' own rows)
+
+# deflateTune rows NO level's row resembles (the reference takes any four integers): each breaks a relation that holds in all nine rows.
+# They have families of their own (edge_catalogue) and stay out of SLOW / FAST, whose families assume a level-like row.
+EDGE_SLOW = {
+    "Q3": (6, (4, 16, 32, 3)), "Q2": (6, (4, 16, 32, 2)), "Q1": (6, (4, 16, 32, 1)),  # max_chain < 4: the quarter budget is 0, a search that never runs out
+    "Q3-L4": (4, (4, 16, 32, 3)), "Q3-L9": (9, (4, 16, 32, 3)),                       # (both ends of the levels that run deflate_slow)
+    "U0": (6, (8, 16, 128, 0)), "U70000": (6, (8, 16, 128, 70000)),                    # the full budget never runs out either
+    "G0": (6, (0, 16, 128, 128)), "G2": (6, (2, 16, 128, 128)),                        # good_length <= 2: quartered with nothing in hand (prev_length = 2)
+    "G3": (6, (3, 16, 128, 32)), "G300": (6, (300, 16, 128, 32)),                      # quartered behind ANY match; never quartered
+    "Z0": (6, (8, 0, 128, 128)), "Z2": (6, (8, 2, 128, 128)), "Z3": (6, (8, 3, 128, 128)),  # max_lazy <= 2: no search at all; 3: only with nothing in hand
+    "LN258": (6, (8, 258, 32, 128)), "LN64": (6, (4, 64, 8, 32)),                      # max_lazy > nice_length: a search with nice_length bytes or more in hand
+    "N0": (6, (8, 4, 0, 128)), "N2": (6, (8, 4, 2, 128)), "N3": (6, (8, 4, 3, 128)),   # nice_length <= 3: the first candidate that improves ends the walk
+    "N1000": (6, (8, 4, 1000, 128)),                                                   # nice_length > MAX_MATCH: no walk ends on a length
+}
+EDGE_FAST = {
+    "I0": (1, (4, 0, 8, 4)), "I3": (1, (4, 3, 8, 4)), "I7": (1, (4, 7, 8, 4)), "I8": (1, (4, 8, 8, 4)), "I258": (1, (4, 258, 8, 4)),  # max_insert_length against nice_length
+    "I0-L3": (3, (4, 0, 32, 32)), "I31-L3": (3, (4, 31, 32, 32)), "I32-L3": (3, (4, 32, 32, 32)), "I258-L3": (3, (4, 258, 32, 32)),
+    "FG2": (1, (2, 4, 8, 4)), "FG2U": (1, (2, 4, 8, 3)),                               # good_length <= 2 on deflate_fast: every search quartered -- 1, and 0 = unbounded
+}
+CONFIGS.update({k: Config(lv, 0, t, 0) for k, (lv, t) in list(EDGE_SLOW.items()) + list(EDGE_FAST.items())})
+CONT_EDGE = ["Q3", "LN258", "G2"]  # the tuned rows that go through ONE continuous stream as well (deflate_slow only: tuned deflate_fast is served in chunks)
+DEEP = 300                         # the deep ladder of an unbounded search: deeper than any max_chain of these rows, cheap for a one-lane kernel
+INF = 1 << 32
 
 Case = namedtuple("Case", "name family data cfgs claims buckets fill pair cont")
 
@@ -72,6 +110,13 @@ def row(cfg):
 
 def is_fast(cfg):
     return CONFIGS[cfg].level <= 3
+
+
+def budget(cfg, held=2):
+    """Candidates longest_match looks at with a match of `held` bytes in hand (2: none): max_chain, a quarter of it from good_length on; a
+    budget of 0 never runs out (the count-down `--chain_length != 0` passes zero, deflate.c:1163)."""
+    good, lazy, nice, chain = row(cfg)
+    return (chain >> 2 if held >= good else chain) or INF
 
 
 def bucket(t):
@@ -237,7 +282,9 @@ def ladder(cfg, d, flavour, at=None, tag="", cont=False, pair=None):
     probe = b.put(prize)
     b.fill(9)
     assert at is None or probe == at
-    if d <= chain:
+    assert flavour == "bkt" or (nice > 3 and (is_fast(cfg) or lazy > 3))  # (a decoy's trigram neither ends the walk nor ends the lazy evaluation)
+    assert is_fast(cfg) or lazy > 2
+    if d <= budget(cfg):
         claim = [(probe, (probe - ppos, 20))]
     elif is_fast(cfg) and flavour == "tri":
         claim = [(probe, (probe - last, 3))]
@@ -253,32 +300,36 @@ def depths(chain):
     return sorted({d for d in (1, 8, 9, 31, 32, 33, 64, 65, chain - 1, chain, chain + 1) if 1 <= d <= chain + 1})
 
 
-def quarter(cfg, d, g):
+def quarter(cfg, d, g, at=None, tag="", cont=False):
     """The same ladder searched with a match of g bytes in hand (g = good_length - 1: the whole budget, g = good_length: a quarter of it)."""
     good, lazy, nice, chain = row(cfg)
     assert 3 <= g < lazy
-    budget = chain >> 2 if g >= good else chain
+    qbudget = budget(cfg, g)
     b = Build(skew=d + g)
     prize = b.word(max(20, g + 8))
     held = bytes([X0]) + prize[: g - 1]
     b.key(prize)
     b.key(bytes([X0]) + prize)
-    b.fill(LEAD)
+    b.fill(LEAD if at is None else at - (g + 2 + len(prize) + 2 + 6 * (d - 1) + 2))
     hpos = b.put(held)
     b.fill(2)
     ppos = b.put(prize)
     b.fill(2)
-    for j in range(d - 1):
+    # (decoy 31 ends in a byte that shares its low five bits with 255: the trigram across its end falls into the bucket of the held match's.  A budget
+    #  of one or two candidates with nothing in hand would never reach the held copy behind it: those rows leave it out)
+    for j in (range(d - 1) if budget(cfg) > 2 else [j for j in range(d) if j != 31][: d - 1]):
         b.put(decoy(prize, j, "tri"))
     b.fill(2)
     q = b.put(bytes([X0]) + prize)
     b.fill(9)
-    claim = [(q, LIT), (q + 1, (q + 1 - ppos, len(prize)))] if d <= budget else [(q, (q - hpos, g))]
-    side = None if d not in (budget, budget + 1) else ("quarter-%s-g%d" % (cfg, g), int(d > budget))
-    c = b.case("quarter-%s-g%d-d%d" % (cfg, g, d), "quarter", [cfg], claim, [q, q + 1], side)
+    claim = [(q, LIT), (q + 1, (q + 1 - ppos, len(prize)))] if d <= qbudget else [(q, (q - hpos, g))]
+    assert at is None or q == at
+    side = None if d not in (qbudget, qbudget + 1) else ("quarter-%s-g%d%s" % (cfg, g, tag), int(d > qbudget))
+    c = b.case("quarter-%s-g%d-d%d%s" % (cfg, g, d, tag), "placed" if tag else "quarter", [cfg], claim, [q, q + 1], side, cont)
     ch = chain_of(c.data, q + 1)
     cq = chain_of(c.data, q)  # (a decoy's last byte may share its low five bits with 255: one more candidate of that bucket, no match)
-    assert ch[d - 1] == ppos and ch[-1] == hpos + 1 and cq[-1] == hpos and len(cq) <= 3, c.name
+    assert len(cq) <= budget(cfg), c.name
+    assert ch[d - 1] == ppos and (ch[-1] == hpos + 1 or g == 3) and cq[-1] == hpos and len(cq) <= 3, c.name  # (g == 3: the held copy's second trigram ends in filler)
     return c
 
 
@@ -298,7 +349,7 @@ def nice_case(cfg, m, far=MAXM, at=None, tag="", cont=False, pair=None, name=Non
     probe = b.put(w)
     b.fill(9)
     assert at is None or probe == at
-    assert m >= lazy or is_fast(cfg)  # (no lazy step behind the nearer copy: max_lazy <= nice_length - 1 in every row used)
+    assert m >= lazy or is_fast(cfg)  # (no lazy step behind the nearer copy; a row whose max_lazy exceeds nice_length - 1 has hand_case instead)
     claim = [(probe, (probe - npos, m) if m >= nice or m >= far else (probe - fpos, far))]
     c = b.case(name or "nice-%s-m%d%s" % (cfg, m, tag), "placed" if tag else "nice", [cfg], claim, [probe], pair, cont)
     assert chain_of(c.data, probe) == [npos, fpos], c.name
@@ -415,7 +466,7 @@ def lazy_case(cfg, h, longer):
     b.fill(9)
     switch = h < lazy and qlen > h
     claim = [(p, LIT), (p + 1, (p + 1 - qpos, qlen))] if switch else [(p, (p - hpos, h))]
-    side = ("lazy-%s" % cfg, int(not switch)) if longer and h in (lazy - 1, lazy) and lazy < MAXM else None
+    side = ("lazy-%s" % cfg, int(not switch)) if longer and h in (lazy - 1, lazy) and 3 < lazy < MAXM else None
     return b.case("lazy-%s-h%d-%s" % (cfg, h, "longer" if longer else "equal"), "lazy", [cfg], claim, [p, p + 1], side)
 
 
@@ -535,6 +586,205 @@ def insert_case(cfg, extra):
     return b.case("fast-insert-%s-%d" % (cfg, m), "fast", [cfg], claim, [s1, p], ("fast-insert-%s" % cfg, extra))
 
 
+# ---- deflateTune rows no level's row resembles ----
+def hand_case(cfg, h, near, far, hole=None, at=None, tag="", cont=False, pair=None):
+    """max_lazy > nice_length: a match of h bytes in hand with nice_length <= h < max_lazy, and one position on two copies of the probe, the
+    nearer of `near` bytes, the farther of `far`.  longest_match starts with best_len = h: a candidate of nice_length..h bytes neither updates nor
+    ends the walk (deflate.c:1126-1163), the first one LONGER than h does both.  `hole`: the nearer copy differs from the probe in byte `hole`
+    alone among its first h + 2 -- nice_length bytes or more in common, and the two bytes a search with h in hand checks first (h - 1 and h) equal."""
+    good, lazy, nice, chain = row(cfg)
+    assert nice <= h < lazy and 3 <= h and near < far <= MAXM and budget(cfg, h) >= 3
+    b = Build(skew=h + near)
+    w = b.word(MAXM)
+    held = bytes([X0]) + w[: h - 1]
+    ncopy = w[:near] if hole is None else w[:hole] + bytes([X0]) + w[hole + 1: h + 2]
+    assert hole is None or (nice <= hole <= h - 2 and near == hole)
+    b.key(w)
+    b.key(w[1:])
+    b.key(bytes([X0]) + w)
+    b.fill(LEAD if at is None else at - (h + 2 + far + 2 + len(ncopy) + 2))
+    hpos = b.put(held)
+    b.fill(2)
+    fpos = b.put(w[:far])
+    b.fill(2)
+    npos = b.put(ncopy)
+    b.fill(2)
+    p = b.put(bytes([X0]) + w)
+    b.fill(9)
+    assert at is None or p == at
+    if near > h and near < lazy and far - 1 > near:  # ... and given up one position on, where the farther copy is the longer one (max_lazy is still above)
+        claim = [(p + 1, LIT), (p + 2, (p + 1 - fpos, far - 1)), (p, LIT)]
+    elif near > h:  # the first candidate that is longer than the match in hand: taken, and the walk ends (it is nice_length bytes or more)
+        claim = [(p + 1, (p + 1 - npos, near)), (p, LIT)]
+    elif far > h:   # the nearer copy is passed over, the walk goes on
+        claim = [(p + 1, (p + 1 - fpos, far)), (p, LIT)]
+    else:
+        claim = [(p, (p - hpos, h))]
+    name = "hand-%s-h%d-n%d-f%d%s%s" % (cfg, h, near, far, "-hole" if hole is not None else "", tag)
+    c = b.case(name, "placed" if tag else "hand", [cfg], claim, [p, p + 1, p + 2], pair, cont)
+    assert chain_of(c.data, p + 1) == [npos, fpos, hpos + 1], c.name
+    return c
+
+
+def repeats_case(cfgs):
+    """max_lazy <= 2: deflate_slow never searches (prev_length = 2 is not below max_lazy, deflate.c:1588) -- three copies of a word, all literals."""
+    b = Build()
+    s_ = b.word(12)
+    b.key(s_)
+    b.fill(LEAD)
+    b.put(s_)
+    b.fill(2)
+    p1 = b.put(s_)
+    b.fill(2)
+    p2 = b.put(s_)
+    b.fill(9)
+    return b.case("lazy-none-repeats", "lazy", cfgs, [(q, LIT) for p in (p1, p2) for q in range(p, p + 12)], [p1, p2])
+
+
+def first_improver_case(cfgs):
+    """A copy of 258 bytes of the probe and a nearer one of 4: with nice_length <= 4 the nearer one ends the walk; every cfg here has max_lazy 4,
+    so nothing is looked for behind it."""
+    b = Build()
+    w = b.word(MAXM)
+    b.key(w)
+    b.fill(LEAD)
+    fpos = b.put(w)
+    b.fill(2)
+    npos = b.put(w[:4])
+    b.fill(2)
+    probe = b.put(w)
+    b.fill(9)
+    assert all(row(c)[1] == 4 and not is_fast(c) for c in cfgs)
+    claims = {c: [(probe, (probe - npos, 4) if row(c)[2] <= 4 else (probe - fpos, MAXM))] for c in cfgs}
+    c = b.case("nice-first-improver", "nice", cfgs, claims, [probe])
+    assert chain_of(c.data, probe) == [npos, fpos], c.name
+    return c
+
+
+def inside_case(cfg, m):
+    """deflate_fast, max_insert_length from the other side: a match of exactly m bytes in front of five new bytes, then a probe that begins with the
+    match's last two bytes and those five -- its only candidate lies INSIDE the match (at m - 2), and so do the next position's; the third
+    position's is the first of the five bytes, which every row inserts."""
+    good, max_insert, nice, chain = row(cfg)
+    assert is_fast(cfg) and 3 <= m <= MAXM
+    b = Build(skew=m)
+    s_, e = b.word(m), b.word(5)
+    r = s_[m - 2:] + e
+    b.key(s_ + e)
+    b.key(r)
+    b.fill(LEAD)
+    s0 = b.put(s_)
+    b.fill(3)
+    s1 = b.put(s_ + e)
+    b.fill(3)
+    p = b.put(r)
+    b.fill(9)
+    if m <= max_insert:
+        claim = [(p, (p - (s1 + m - 2), 7)), (s1, (s1 - s0, m))]
+    else:
+        claim = [(p, LIT), (p + 1, LIT), (p + 2, (p - s1 - m + 2, 5)), (s1, (s1 - s0, m))]
+    side = ("fast-inside-%s" % cfg, int(m > max_insert)) if m in (max_insert, max_insert + 1) and 3 <= max_insert < MAXM else None
+    return b.case("fast-inside-%s-%d" % (cfg, m), "fast", [cfg], claim, [s1, p], side)
+
+
+def edge_catalogue():
+    out = []
+
+    def rungs(cfg, fl="bkt"):  # the two sides of the budget that holds with nothing in hand
+        bd = budget(cfg)
+        for d in (bd, bd + 1):
+            out.append(ladder(cfg, d, fl, pair=("chain-%s-%s" % (cfg, fl), int(d > bd))))
+
+    # quarter 0: with good_length bytes in hand the prize is found however deep, with one fewer the budget is max_chain
+    for cfg in ("Q3", "Q2", "Q1", "Q3-L4", "Q3-L9"):
+        good, lazy, nice, chain = row(cfg)
+        for d in sorted({chain + 1, 8, 40, DEEP}):
+            out.append(quarter(cfg, d, good))
+        for d in (chain, chain + 1):
+            out.append(quarter(cfg, d, good - 1))
+        rungs(cfg, "tri")
+    # an unbounded full budget
+    for cfg in ("U0", "U70000"):
+        good = row(cfg)[0]
+        for fl in ("tri", "bkt"):
+            out.append(ladder(cfg, DEEP, fl))
+        out.append(ladder(cfg, 40, "tri"))
+        out.append(quarter(cfg, DEEP, good))
+        out.append(quarter(cfg, DEEP, good - 1))
+    # good_length 0, 2, 3, 300
+    for cfg in ("G0", "G2"):
+        rungs(cfg, "tri")       # 32 | 33 with nothing in hand
+        rungs(cfg, "bkt")
+        for d in (32, 33):
+            out.append(quarter(cfg, d, 5))
+    rungs("G3", "tri")          # 32 | 33: the full budget
+    for d in (8, 9):
+        out.append(quarter("G3", d, 3))
+    rungs("G300", "tri")
+    for d in (32, 33):
+        out.append(quarter("G300", d, 15))
+    # max_lazy 0, 2, 3
+    out.append(repeats_case(["Z0", "Z2", "L6"]))
+    out[-1].claims["L6"][:] = []  # (level 6 is there for the contrast: its stream must differ, see the tests; no claim)
+    out.append(lazy_case("Z3", 3, True))
+    rungs("Z3", "bkt")
+    # max_lazy > nice_length
+    for cfg in ("LN258", "LN64"):
+        good, lazy, nice, chain = row(cfg)
+        for h in sorted({nice, nice + 5, min(lazy, MAXM) - 1}):
+            far = min(MAXM, h + 20)
+            if h + 1 < far:
+                out.append(hand_case(cfg, h, nice, far, pair=("hand-%s-h%d" % (cfg, h), 0)))
+                out.append(hand_case(cfg, h, h + 1, far, pair=("hand-%s-h%d" % (cfg, h), 1)))
+                if h > nice:
+                    out.append(hand_case(cfg, h, h, far))
+            if h - 2 >= nice:
+                hole = h - 2 if h + 2 < MAXM else nice  # (h = 257: the copy runs to the probe's last byte, the differing byte lies as far in front as it may)
+                out.append(hand_case(cfg, h, hole, max(far, h + 1), hole=hole))
+        rungs(cfg, "tri")
+    # nice_length 0, 2, 3, 1000
+    out.append(first_improver_case(["N0", "N2", "N3", "N1000"]))
+    out.append(nice_case("N1000", 200))
+    out.append(nice_case("N1000", MAXM - 1))
+    for cfg in ("N0", "N2", "N3", "N1000"):
+        rungs(cfg, "bkt")
+    # deflate_fast: max_insert_length on either side of nice_length
+    for cfg in EDGE_FAST:
+        if cfg.startswith("I"):
+            mi, nice = row(cfg)[1], row(cfg)[2]
+            for m in sorted({3, nice - 1, nice, nice + 1} | {x for x in (mi, mi + 1) if 3 <= x <= MAXM}):
+                out.append(inside_case(cfg, m))
+            rungs(cfg, "tri")
+    for cfg in FAST:            # (the levels' own rows through the same construction)
+        for m in (row(cfg)[1], row(cfg)[1] + 1):
+            out.append(inside_case(cfg, m))
+    # good_length <= 2 on deflate_fast: every search is quartered
+    rungs("FG2", "bkt")         # 1 | 2
+    rungs("FG2", "tri")
+    for d in (5, 40, DEEP):
+        out.append(ladder("FG2U", d, "bkt"))
+    out.append(ladder("FG2U", 40, "tri"))
+    # placement: walker block and log window edges (chunks, and a second time as one continuous stream), tile edges (one continuous stream)
+    for cfg in CONT_EDGE:
+        good, lazy, nice, chain = row(cfg)
+        spots = [(t, a, False) for t, a in placements(LEAD + 400)] + [(t, a, True) for t, a in tile_placements()]
+        for tag, at, cont in spots:
+            if cfg == "Q3":
+                for d in (chain + 1, 8):
+                    out.append(quarter(cfg, d, good, at=at, tag="-" + tag, cont=cont))
+                for d in (chain, chain + 1):
+                    out.append(quarter(cfg, d, good - 1, at=at, tag="-" + tag, cont=cont))
+            elif cfg == "G2":
+                for d in (32, 33):
+                    out.append(ladder(cfg, d, "tri", at=at, tag="-" + tag, cont=cont, pair=("chain-%s-%s" % (cfg, tag), int(d > 32))))
+            else:
+                h = nice + 5
+                out.append(hand_case(cfg, h, nice, h + 20, at=at, tag="-" + tag, cont=cont, pair=("hand-%s-%s" % (cfg, tag), 0)))
+                out.append(hand_case(cfg, h, h + 1, h + 20, at=at, tag="-" + tag, cont=cont, pair=("hand-%s-%s" % (cfg, tag), 1)))
+                out.append(hand_case(cfg, h, h - 2, h + 20, hole=h - 2, at=at, tag="-" + tag, cont=cont))
+    return out
+
+
 _catalogue = None
 
 
@@ -629,6 +879,7 @@ def build_catalogue():
             if nice < MAXM - 1:
                 for m in (nice - 1, nice):
                     out.append(nice_case(cfg, m, at=at, tag="-" + tag, cont=True, pair=("nice-%s-%s" % (cfg, tag), int(m >= nice))))
+    out += edge_catalogue()
     names = [c.name for c in out]
     assert len(set(names)) == len(names)
     return out

@@ -279,14 +279,19 @@ def inflate_zlib(data: bytes, outcap: int):
     return rc, out
 
 
-def deflate_calls(data: bytes, level: int, calls=(), wbits: int = -15, strategy: int = 0, dictionary: bytes = None, params=None) -> bytes:
+def deflate_calls(data: bytes, level: int, calls=(), wbits: int = -15, strategy: int = 0, dictionary: bytes = None, params=None, tune=None) -> bytes:
     """ONE stream of the reference driven call by call: for (upto, flush) in calls, deflate() is handed data[fed:upto] with that flush
     value (Z_NO_FLUSH slices the input, Z_SYNC_FLUSH / Z_FULL_FLUSH / Z_PARTIAL_FLUSH flush); a last call hands over the rest with
-    Z_FINISH.  calls == () is what compress2() does (qcsrc/compress.c:22-58).  Output space is never short."""
+    Z_FINISH.  calls == () is what compress2() does (qcsrc/compress.c:22-58).  Output space is never short.
+    tune: deflateTune(good_length, max_lazy, nice_length, max_chain) right behind deflateInit2."""
     L = lib()
     s = ZStream()
     rc = L.deflateInit2_(C.byref(s), level, Z_DEFLATED, wbits, 8, strategy, b"1.2.3", C.sizeof(ZStream))
     assert rc == Z_OK, rc
+    if tune:
+        L.deflateTune.argtypes = [C.POINTER(ZStream), C.c_int, C.c_int, C.c_int, C.c_int]
+        rc = L.deflateTune(C.byref(s), *tune)
+        assert rc == Z_OK, rc
     if dictionary is not None:
         rc = L.deflateSetDictionary(C.byref(s), dictionary, len(dictionary))
         assert rc == Z_OK, rc

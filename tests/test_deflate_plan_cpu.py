@@ -119,6 +119,65 @@ def test_every_refusal(model):
     model("deflate", [(inp, dict(rc=STREAM_ERROR, msg=msg)) for inp, msg in rows])
 
 
+def tune(good, lazy, nice, chain):
+    return dict(tune_good=good, tune_lazy=lazy, tune_nice=nice, tune_chain=chain)
+
+
+def test_deflateTune_rows_no_levels_row_resembles(model):
+    """Relations between the four parameters that hold in all nine rows of the level table and that an implementation rests on: where deflateTune breaks one,
+    an explicit request for that implementation is refused with a message of its own, and ZGPU_LZ_AUTO -- whatever ZGPU_LZ_DEFAULT says -- serves the row."""
+    quarter0 = "ZGPU_LZ_SORTED / ZGPU_LZ_PARALLEL do not serve a max_chain below 4 (deflateTune): its quarter budget never runs out"
+    lazy_nice = "ZGPU_LZ_SORTED / ZGPU_LZ_PARALLEL do not serve max_lazy > nice_length (deflateTune)"
+    deep = "ZGPU_LZ_SORTED does not serve a max_chain above 4096 (deflateTune)"
+    insert = "ZGPU_LZ_FAST does not serve a max_insert_length above 7 (deflateTune)"
+    good2 = "ZGPU_LZ_FAST does not serve a good_length below 3 (deflateTune): every search of deflate_fast is quartered"
+    fastwin = "ZGPU_LZ_FASTWIN serves levels 1..3 with their own parameters, not Z_HUFFMAN_ONLY / Z_RLE, no dictionary chunk"
+    refused, served = [], []
+    for impl in (SORTED, PARALLEL):
+        refused += [(dict(level=6, lz_impl=impl, **tune(4, 16, 32, c)), quarter0) for c in (1, 2, 3)]
+        refused += [(dict(level=lv, lz_impl=impl, **tune(4, 16, 32, 3)), quarter0) for lv in (4, 9)]
+        refused += [(dict(level=6, lz_impl=impl, **tune(8, 258, 32, 128)), lazy_nice), (dict(level=6, lz_impl=impl, **tune(4, 64, 8, 32)), lazy_nice),
+                    (dict(level=6, lz_impl=impl, **tune(8, 33, 32, 128)), lazy_nice), (dict(level=6, lz_impl=impl, **tune(8, 16, 3, 128)), lazy_nice)]
+        if impl == SORTED:  # (match3_kernel's keys; the link ring counts in a register)
+            refused += [(dict(level=6, lz_impl=impl, **tune(8, 16, 128, c)), deep) for c in (0, 4097, 65535, 70000)]
+        else:
+            served += [(dict(level=6, lz_impl=impl, **tune(8, 16, 128, c)), dict(rc=0, impl="PARALLEL", chain=c or 0xffffffff)) for c in (0, 4097, 65535, 70000)]
+        # on either side of each relation: served
+        served += [(dict(level=6, lz_impl=impl, **tune(4, 16, 32, 4)), dict(rc=0, chain=4)), (dict(level=6, lz_impl=impl, **tune(8, 32, 32, 128)), dict(rc=0, lazy=32, nice=32)),
+                   (dict(level=6, lz_impl=impl, **tune(8, 16, 128, 4096)), dict(rc=0, chain=4096)),
+                   (dict(level=6, lz_impl=impl, **tune(32, 1000, 258, 4096)), dict(rc=0, lazy=1000, nice=258)),  # (258 bytes in hand: nothing is longer)
+                   (dict(level=6, lz_impl=impl, **tune(32, 1000, 1000, 4096)), dict(rc=0, nice=258)),
+                   (dict(level=6, lz_impl=impl, **tune(0, 16, 128, 128)), dict(rc=0, good=0)), (dict(level=6, lz_impl=impl, **tune(300, 0, 128, 128)), dict(rc=0, good=300, lazy=0))]
+    # Z_RLE and Z_HUFFMAN_ONLY are chain budgets of their own (1 and 0, no quarter): the all-position search keeps them whatever max_chain says
+    served += [(dict(level=6, strategy=3, **tune(4, 16, 32, 3)), dict(rc=0, impl="SORTED", chain=1)), (dict(level=6, strategy=2, **tune(8, 16, 128, 0)), dict(rc=0, impl="SORTED", chain=0)),
+               (dict(level=6, strategy=3, lz_impl=SORTED, **tune(8, 258, 32, 70000)), dict(rc=0, impl="SORTED", chain=1))]
+    # the walkers and the lane-per-chunk loop play the reference's own loop: every row
+    for t in (tune(4, 16, 32, 3), tune(4, 16, 32, 1), tune(8, 258, 32, 128), tune(8, 16, 128, 0), tune(8, 16, 128, 70000), tune(0, 0, 0, 0)):
+        served += [(dict(level=6, **t), dict(rc=0, impl="WALK")), (dict(level=6, lz_impl=WALK, **t), dict(rc=0, impl="WALK")), (dict(level=6, lz_impl=SERIAL, **t), dict(rc=0, impl="SERIAL")),
+                   (dict(level=6, lz_default=3, **t), dict(rc=0, impl="WALK"))]  # ZGPU_LZ_DEFAULT=3 does not send the default path into a refusal
+    # max_chain is kept whole (the quarter of 70000 is 17500); 0, which never runs out, is the largest budget there is
+    served += [(dict(level=6, **tune(8, 16, 128, 0)), dict(rc=0, chain=0xffffffff)), (dict(level=6, **tune(8, 16, 128, 70000)), dict(rc=0, chain=70000)),
+               (dict(level=6, **tune(8, 16, 128, 65535)), dict(rc=0, chain=65535)), (dict(level=1, nchunks=100, **tune(4, 4, 8, 0)), dict(rc=0, impl="SERIAL", chain=0xffffffff)),
+               (dict(level=6, lz_default=3, **tune(8, 16, 32, 33)), dict(rc=0, impl="SORTED"))]
+    # levels 1-3.  The waves: the level's good_length, nice_length and max_chain, and max_insert_length BELOW nice_length
+    for lv, nice, chain in ((1, 8, 4), (2, 16, 8), (3, 32, 32)):
+        served += [(dict(level=lv, nchunks=100, **tune(4, mi, nice, chain)), dict(rc=0, impl="FASTWIN", lazy=mi)) for mi in (0, 3, nice - 1)]
+        served += [(dict(level=lv, nchunks=100, lz_impl=FASTWIN, **tune(4, nice - 1, nice, chain)), dict(rc=0, impl="FASTWIN"))]
+        for mi in (nice, nice + 1, 258):
+            served += [(dict(level=lv, nchunks=100, **tune(4, mi, nice, chain)), dict(rc=0, impl="SERIAL", hand_on=0, lazy=mi)),
+                       (dict(level=lv, nchunks=100000, **tune(4, mi, nice, chain)), dict(rc=0, impl="SERIAL", hand_on=0))]  # (no hand-on to the waves either)
+            refused += [(dict(level=lv, lz_impl=FASTWIN, **tune(4, mi, nice, chain)), fastwin)]
+    refused += [(dict(level=1, lz_impl=FASTWIN, **tune(2, 4, 8, 4)), fastwin), (dict(level=1, lz_impl=FASTWIN, **tune(2, 4, 8, 3)), fastwin)]
+    served += [(dict(level=1, nchunks=100, **tune(2, 4, 8, 4)), dict(rc=0, impl="SERIAL", hand_on=0)), (dict(level=1, nchunks=100, **tune(2, 4, 8, 3)), dict(rc=0, impl="SERIAL", chain=3))]
+    # deflate_fast on the sorted buckets: max_insert_length up to 7, good_length above 2
+    served += [(dict(level=1, lz_impl=FAST, **tune(4, mi, 8, 4)), dict(rc=0, impl="FAST", lazy=mi)) for mi in (0, 3, 7)]
+    served += [(dict(level=1, lz_impl=FAST, **tune(3, 4, 8, 4)), dict(rc=0, impl="FAST")), (dict(level=1, nchunks=100, lz_default=5, **tune(4, 7, 8, 4)), dict(rc=0, impl="FAST"))]
+    refused += [(dict(level=1, lz_impl=FAST, **tune(4, mi, 8, 4)), insert) for mi in (8, 258)] + [(dict(level=3, lz_impl=FAST, **tune(4, 31, 32, 32)), insert)]
+    refused += [(dict(level=1, lz_impl=FAST, **tune(g, 4, 8, 4)), good2) for g in (0, 2)]
+    served += [(dict(level=1, nchunks=100, lz_default=5, **tune(4, 8, 8, 4)), dict(rc=0, impl="SERIAL")), (dict(level=1, nchunks=100, lz_default=5, **tune(2, 4, 8, 3)), dict(rc=0, impl="SERIAL"))]
+    model("deflate", [(inp, dict(rc=STREAM_ERROR, msg=msg)) for inp, msg in refused] + served)
+
+
 def test_framing(model):
     model("deflate", [(dict(flags=FINAL), dict(rc=0, head=0, tail=0, with_crc=0, seg_wrap=0)),
                       (dict(flags=FINAL | ZLIB), dict(rc=0, head=2, tail=4, with_crc=0, seg_wrap=0)),

@@ -43,7 +43,8 @@ static PlanEngine engine_of(const Row &r)
     pe.exact_sort = r.i("exact_sort") != 0;
     pe.lz_parallel = r.i("lz_parallel", 1) != 0;
     const int level = r.i("level", 6);
-    pe.fastwin_serves = r.i("fastwin", level >= 1 && level <= 3 && !pe.tuned) != 0; // (what lz_fastwin_serves says of the levels' own parameters)
+    // (what lz_fastwin_serves says: of the level's own parameters, or of deflateTune's)
+    pe.fastwin_serves = r.i("fastwin", level >= 1 && level <= 9 && fastwin_row_serves(level_cfg_tuned(level, r.i("strategy"), pe.tuned, pe.tune))) != 0;
     pe.sorted_ws_chunk = r.u("sws", 1245184);
     pe.batch_cap = (uint32_t)r.u("batch_cap"); pe.par_cap = (uint32_t)r.u("par_cap"); pe.ct_tiles = (uint32_t)r.u("ct_tiles");
     pe.free_bytes = r.u("free");

@@ -60,11 +60,47 @@ inline LevelCfg level_cfg_tuned(int level, int strategy, bool tuned, const uint3
     LevelCfg cfg = level_cfg(level);
     cfg.strategy = (uint32_t)strategy;
     if (tuned) {
-        // (a budget of 0 never runs out in the reference: its loop counts down past zero, deflate.c:1163 -- no chain of a chunk is longer than 65535)
-        cfg.good = tune[0]; cfg.lazy = tune[1]; cfg.nice = tune[2]; cfg.chain = (tune[3] && tune[3] < 0xffffu) ? tune[3] : 0xffffu;
+        // (a budget of 0 never runs out in the reference: its loop counts down past zero, deflate.c:1163 -- here the largest budget there is, whose quarter no
+        //  chain of a chunk, 65535 candidates at the most, reaches either.  Any other max_chain is kept as it is: the quarter of 70000 is 17500.)
+        cfg.good = tune[0]; cfg.lazy = tune[1]; cfg.nice = tune[2]; cfg.chain = tune[3] ? tune[3] : 0xffffffffu;
         if (cfg.nice > kMaxMatch) cfg.nice = kMaxMatch; // (no match is longer: the same searches)
     }
     return cfg;
+}
+
+// The implementations that search every position ONCE, with nothing in hand, and leave two records per position -- the full budget's and the quarter's --
+// for the parse to pick from (ZGPU_LZ_SORTED, ZGPU_LZ_PARALLEL; ParseCtx::take) rest on relations that hold in every level's row and that deflateTune
+// can break.  nullptr: the row is served; else why not.  (cfg: the strategy's chain budget applied.)
+inline const char *records_refuse(const LevelCfg &cfg, int impl)
+{
+    const bool searches = cfg.strategy != kHuffmanOnly && cfg.strategy != kRle; // (Z_RLE: the nearest candidate only, no quarter; ParseCtx::take)
+    // a quarter budget of 0 never runs out (deflate.c:1163): with good_length bytes in hand the search goes through the whole chain, not max_chain candidates
+    if (searches && cfg.chain < 4) return "ZGPU_LZ_SORTED / ZGPU_LZ_PARALLEL do not serve a max_chain below 4 (deflateTune): its quarter budget never runs out";
+    // with nice_length bytes or more in hand a candidate of nice_length bytes is passed over and the walk goes on; the record's walk ended there
+    if (searches && cfg.lazy > cfg.nice && cfg.nice < kMaxMatch) return "ZGPU_LZ_SORTED / ZGPU_LZ_PARALLEL do not serve max_lazy > nice_length (deflateTune)";
+    // match3_kernel counts a walk's candidates in 12 bits of a key (level 9's 4096 fill them)
+    if (searches && impl == ZGPU_LZ_SORTED && cfg.chain > 4096) return "ZGPU_LZ_SORTED does not serve a max_chain above 4096 (deflateTune)";
+    return nullptr;
+}
+
+// The wave-per-chunk kernels of levels 1-3 (ZGPU_LZ_FASTWIN, zgpu_lz_fastwin.hip; lz_fastwin_serves) are instantiated for the levels' three pairs of max_chain and
+// nice_length and start every search with the full budget (prev_length = 2 < good_length = 4).  max_insert_length (cfg.lazy) is a run-time value, but it must stay
+// below nice_length: the token walk decides whether a match's strings go into the chains from the length the lanes have COMPARED, which for a match of
+// nice_length bytes or more is not its length yet ("longm", in both kernels) -- right only while every such match is longer than max_insert_length.
+// Anything else -- a deflateTune row -- goes to the lane-per-chunk loop; the same predicate guards the continuous stream and the hand-on.
+inline bool fastwin_row_serves(const LevelCfg &cfg)
+{
+    if (cfg.slow || cfg.good != 4 || cfg.lazy >= cfg.nice) return false;
+    return (cfg.chain == 4 && cfg.nice == 8) || (cfg.chain == 8 && cfg.nice == 16) || (cfg.chain == 32 && cfg.nice == 32);
+}
+
+// deflate_fast on the sorted buckets (ZGPU_LZ_FAST, fast_kernel) holds the index of the seven positions behind a token's start, which is all a level's
+// max_insert_length (4, 5, 6) asks for, and starts every search with the full budget, as prev_length = 2 < good_length = 4 has it.
+inline const char *fast_refuse(const LevelCfg &cfg)
+{
+    if (cfg.lazy > 7) return "ZGPU_LZ_FAST does not serve a max_insert_length above 7 (deflateTune)";
+    if (cfg.good <= 2) return "ZGPU_LZ_FAST does not serve a good_length below 3 (deflateTune): every search of deflate_fast is quartered";
+    return nullptr;
 }
 
 // What is refused before anything is asked of the device (a BGZF call's segment table is measured there, behind these)
@@ -166,11 +202,18 @@ inline DeflatePlan plan_deflate(const PlanCall &c, const PlanEngine &eng, const 
     const bool walk_ok = cfg.strategy != kHuffmanOnly && cfg.strategy != kRle;
     // levels 1-3 above the crossover: the lane-per-chunk loop hands the chunks that do not compress on to the wave-per-chunk kernel (lz_serial_chunk)
     bool hand_on = false;
-    if (impl == ZGPU_LZ_AUTO) impl = plan_auto_impl(c, eng, kn, cfg, walk_ok, &hand_on);
+    if (impl == ZGPU_LZ_AUTO) {
+        impl = plan_auto_impl(c, eng, kn, cfg, walk_ok, &hand_on);
+        // (ZGPU_LZ_DEFAULT=3 / =5 on a row that implementation does not serve: the default path refuses nothing)
+        if (impl == ZGPU_LZ_SORTED && walk_ok && records_refuse(cfg, impl)) impl = ZGPU_LZ_WALK;
+        if (impl == ZGPU_LZ_FAST && fast_refuse(cfg)) impl = ZGPU_LZ_SERIAL;
+    }
     if ((impl == ZGPU_LZ_PARALLEL || impl == ZGPU_LZ_SORTED || impl == ZGPU_LZ_WALK) && (!cfg.slow || !eng.lz_parallel)) return plan_refused("parallel LZ77 serves levels 4..9 only");
     if (impl == ZGPU_LZ_FAST && (cfg.slow || !walk_ok || c.skip0 || !eng.lz_parallel)) return plan_refused("ZGPU_LZ_FAST serves levels 1..3, not Z_HUFFMAN_ONLY / Z_RLE, no dictionary chunk");
     if (impl == ZGPU_LZ_FASTWIN && (cfg.slow || !walk_ok || c.skip0 || !eng.lz_parallel || !eng.fastwin_serves))
         return plan_refused("ZGPU_LZ_FASTWIN serves levels 1..3 with their own parameters, not Z_HUFFMAN_ONLY / Z_RLE, no dictionary chunk");
+    if ((impl == ZGPU_LZ_PARALLEL || impl == ZGPU_LZ_SORTED) && records_refuse(cfg, impl)) return plan_refused(records_refuse(cfg, impl));
+    if (impl == ZGPU_LZ_FAST && fast_refuse(cfg)) return plan_refused(fast_refuse(cfg));
     if (impl < ZGPU_LZ_SERIAL || impl > ZGPU_LZ_FASTWIN) return plan_refused("unknown lz_impl");
     if (impl == ZGPU_LZ_PARALLEL && c.strategy != 0) return plan_refused("ZGPU_LZ_PARALLEL serves the default strategy only");
     if (impl == ZGPU_LZ_WALK && !walk_ok) return plan_refused("ZGPU_LZ_WALK does not serve Z_HUFFMAN_ONLY / Z_RLE");

@@ -25,6 +25,7 @@
 // five windows ahead sees bits that are not there yet, 0.7-0.8 evaluations per window stay on the serial path.
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
+#include "zgpu_deflate_plan.h"
 #include <cstdlib>
 
 #ifdef ZGPU_FW_TIME // timing builds only (scripts/build_variant.sh fwtime -DZGPU_FW_TIME; scripts/fw_time.py): cycles by phase, counts
@@ -295,7 +296,7 @@ __global__ void __launch_bounds__(64) fastwin_kernel(ChunkGeom g, uint32_t max_i
             // ---- the walk over the token starts, from `start` ----
             // What the scalar loop needs of a lane comes packed: where the token behind this lane's starts (lane + length, unclamped) and the two flags.
             // Whether a match's strings stay out of the chains is a mask of its own (a measured match is NICE or longer, i.e. longer than
-            // max_insert_length at the three levels this kernel serves), and the positions inside such matches (C) are found by all lanes behind the loop.
+            // max_insert_length in every row this kernel serves: fastwin_row_serves, zgpu_deflate_plan.h), and the positions inside such matches (C) are found by all lanes behind the loop.
             const uint64_t nonlit = __builtin_amdgcn_ballot_w64(res != 1u);
             uint32_t pk = (lane + (res & kResLen)) | (res & (kResTerm | kResInc));
             const uint32_t len_e = res & kResLen;
@@ -825,12 +826,8 @@ static bool fw_use_ring(uint32_t nlaunch)
     if (v == -2) { const char *e = getenv("ZGPU_FW_RING"); v = e ? atoi(e) : -1; }
     return v < 0 ? nlaunch < 768 : v != 0;
 }
-// the levels' own parameters only (deflate.c:137-149): a tuned stream goes to the lane-per-chunk loop
-bool lz_fastwin_serves(const LevelCfg &cfg)
-{
-    if (cfg.slow || cfg.good != 4) return false;
-    return (cfg.chain == 4 && cfg.nice == 8) || (cfg.chain == 8 && cfg.nice == 16) || (cfg.chain == 32 && cfg.nice == 32);
-}
+// (the relations between the four parameters that these kernels rest on: fastwin_row_serves, zgpu_deflate_plan.h)
+bool lz_fastwin_serves(const LevelCfg &cfg) { return fastwin_row_serves(cfg); }
 
 void launch_lz_fastwin(const ChunkGeom &g, LevelCfg cfg, const uint16_t *S, const uint32_t *ir, uint32_t *tokens, ChunkMeta *meta, hipStream_t st)
 {

@@ -13,7 +13,11 @@
 //                     results: after max_chain candidates and after max_chain>>2 candidates (the budget used when
 //                     prev_length >= good_match, deflate.c:1064-1066).  A seeded call returns that result when it is
 //                     longer than the seed and "no improvement" otherwise, so these two records answer every call
-//                     the parser can make.
+//                     the parser can make -- in every row of the level table.  deflateTune can break what that rests
+//                     on: a max_chain below 4 (the quarter is 0, and a budget of 0 never runs out, deflate.c:1163 --
+//                     not max_chain candidates, which is all a record holds) and max_lazy > nice_length (a call seeded
+//                     with nice_length bytes or more passes over a candidate the unseeded walk ended at).  plan_deflate
+//                     refuses both for this implementation and for ZGPU_LZ_SORTED (records_refuse, zgpu_deflate_plan.h).
 //   K3 parse_kernel   one lane per chunk: the deflate_slow control flow over the records (no chain walking, no byte
 //                     compares), producing the token stream and the per-block "may not be stored" flags.
 //

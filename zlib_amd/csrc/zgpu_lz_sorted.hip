@@ -683,8 +683,9 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
         uint32_t k = 0;
         // the quarter budget need not be a multiple of the four candidates of a step (deflateTune: max_chain 13 or 100 give 3 and 25): the snapshot is
         // taken in front of candidate chainQ, at the top of step snapK or, for snapJ != 0, between two candidates of it.
-        // NOT settled: a quarter of 0 (max_chain 1..3).  The reference's count-down passes zero there and the search with a good match in hand is
-        // unbounded (walk_kernel: budget 0xffff); here the snapshot at k == 0 is empty and the walk ends after chainF candidates
+        // A quarter of 0 (max_chain 1..3) never comes here: the reference's count-down passes zero there and the search with a good match in hand is
+        // unbounded (walk_kernel: budget 0xffff), which a record of at most chainF candidates cannot hold -- plan_deflate (records_refuse) refuses the row,
+        // as it does max_lazy > nice_length (the record is made with nothing in hand) and, for this kernel, a max_chain above 4096 (12 bits of a key count the candidates)
         const uint32_t snapK = chainQ & ~3u, snapJ = chainQ & 3u;
         for (;; k += 4) {
             if (amask == 0) break;
@@ -983,7 +984,10 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     const uint32_t chainF = cfg.chain, chainQ = cfg.chain >> 2, dbase = lds_off(d32), nblk = TILE ? tnent + (th1 - th0 - tnent + kWBlk - 1) / kWBlk : (n + kWBlk - 1) / kWBlk;
     const uint32_t wlim = TILE ? th1 : n; // a walker that arrives here, neutral, is done with the chunk / the tile
     const bool vexact = (chainF & 7u) != 0 || (chainQ & 7u) != 0 || cfg.strategy == kRle; // a chain may end inside a group of eight with entries of its own bucket behind it (see the bodies)
-    const uint32_t lanebits = lane << 16, dummy = ring + (kRing - 1) * 4;
+    // what a parked candidate carries besides its position: the owner's lane (bits 16-21), "first of its chain" (bit 22) and, from bit 23, the length of
+    // the match the search started with in hand (at most 258) -- set when a search starts
+    uint32_t lanebits = lane << 16;
+    const uint32_t dummy = ring + (kRing - 1) * 4;
     // walker
     uint32_t st = W_NEED, x = 0, handL = kMinMatch - 1, handM = 0, handD = 0, gstart = 0;
     uint32_t irx = 0, irn = 0, irE = 0, irl = 0; // idx | rank << 16 of: x, x + 1, the position behind the match in hand, a position asked for in the last pass
@@ -1023,7 +1027,11 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             }
             uint32_t len = xa ? l + ((uint32_t)__builtin_ctz(xa) >> 3) : xb ? l + 4 + ((uint32_t)__builtin_ctz(xb) >> 3) : l + 8;
             len = len < cap ? len : cap;
-            if (len >= kMinMatch && reach) lds_max32(slot + o * 4, len >= nice ? (0x80000000u | (q << 9) | len) : ((len << 16) | q));
+            // a candidate ends the walk when it is nice AND longer than the match in hand (deflate.c:1126-1160: best_len starts at prev_length, and only a
+            // candidate that improves on it is looked at for nice_match).  With max_lazy > nice_length -- deflateTune; no level's row -- a search starts with
+            // nice_length bytes or more in hand: a candidate of nice..seed bytes is passed over like any other that does not improve (its plain key stays
+            // below the sentinel), and the walk goes on
+            if (len >= kMinMatch && reach) lds_max32(slot + o * 4, (len >= nice && len > (e >> 23)) ? (0x80000000u | (q << 9) | len) : ((len << 16) | q));
         }
         const uint32_t key = lds_ld32(slot + lane * 4);
         if (key != key_seen) {
@@ -1127,6 +1135,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             scan2 = (uint32_t)d8[x + best - 1] | ((uint32_t)d8[x + best] << 16);
             lds_st32(slot + lane * 4, sentinel);
             lds_st16(pw + lane * 2, x);
+            lanebits = (lane << 16) | (seed << 23);
             rem = avail; firstb = 1u << 22;
             gi = (int)idx - 8;
             st = W_SEARCH;
