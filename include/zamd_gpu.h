@@ -132,6 +132,7 @@ void zgpu_engine_destroy(zgpu_engine *e);
 const char *zgpu_engine_error(const zgpu_engine *e);
 const char *zgpu_version(void);
 uint64_t zgpu_debug_handed_on(const zgpu_engine *e); /* diagnostic: chunks of level 1-3 calls that went from the lane-per-chunk loop to the wave-per-chunk kernel */
+int zgpu_debug_sort_fallback(const zgpu_engine *e);  /* diagnostic: non-zero once the fast sort's self-check has failed on this engine and its calls use the ballot-ranked sort */
 
 /* deflateInit2's geometry (qcsrc/deflate.c:222-297) for the calls that follow: windowBits 9..15 (the window is 2^windowBits bytes, matches reach
  * 2^windowBits - 262 back, the window slides every 2^windowBits bytes) and memLevel 1..9 (hash of memLevel + 7 bits, a block is cut after

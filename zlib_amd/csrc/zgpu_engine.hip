@@ -145,6 +145,7 @@ void zgpu_engine_destroy(zgpu_engine *e)
 
 const char *zgpu_engine_error(const zgpu_engine *e) { return e ? e->err : "no engine"; }
 uint64_t zgpu_debug_handed_on(const zgpu_engine *e) { return e ? e->handed_on : 0; } // chunks the lane-per-chunk loop gave to the wave-per-chunk kernel so far (tests, bench)
+int zgpu_debug_sort_fallback(const zgpu_engine *e) { return e ? e->exact_sort : 0; } // non-zero: the fast sort's self-check failed once and the engine sorts with sort_kernel since (tests)
 
 int zgpu_adler32_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, uint32_t *adler_out, void *hip_stream)
 {

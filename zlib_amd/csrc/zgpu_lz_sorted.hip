@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_
 // ranks in a scratch array by position, because a lane's passes worked on different positions: 43 GB of the sort's 77 GB per
 // 4 GiB went there and back.  DESIGN.md, K1'' and K1''', has the history.)
 //   pass A   rank(p): the token round.  The chunk's Adler-32 rides along: the pass has every byte of the chunk in a register once,
-//            and the kernel is waiting for the LDS, not for the vector unit -- a kernel of its own re-read the input for 0.7 ms per 4 GiB.
+//            for a few instructions a position -- a kernel of its own re-read the input for 0.7 ms per 4 GiB.
 //   pass B   exclusive scan of the 32768 counts -> bucket starts, in place (the count of hash h is half (h & 1) of word h >> 1);
 //            32 consecutive counts, four 16-byte vectors, per lane.
 //   pass C0  idx(p) = start(hash) + rank: the position's ir word, written and kept; a bit per bucket head.
@@ -277,9 +277,43 @@ __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_
 //   pass V   the self-check, on those 16 bytes as they go out: inside a bucket the positions must ascend.
 // Continuous stream: positions in front of earlier flush points have three bytes but are in no chain -- no rank, no place in S
 // (kNone32 in the lane's register, as for the positions the chunk does not have).
+// Passes A and C0 have two forms of a turn: the general one, which asks of every position whether the chunk has it, whether four bytes can be
+// loaded at it and whether it is in the chains, and a straight one without lane masks for a turn of which all that is known beforehand
+// (whole_turn below: all but the last turn of a full chunk).  The kernel is bound by the instructions it issues, not by the token round
+// (-DZGPU_SORT_TIME, scripts/sort_time.py: the poll loop is 6 % of a wave's time), and keeps one workgroup per CU: a form with 16 bits of state
+// per position and two 512-lane workgroups per CU was measured and was slower (DESIGN.md section 4, K1'''').
 constexpr uint32_t kS4Threads = 1024, kS4Waves = kS4Threads / 64, kS4TurnSteps = 8, kS4TurnPos = 64 * kS4TurnSteps;
 struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
 __device__ inline uint32_t lds_add_rtn32_nowait(uint32_t a, uint32_t v) { uint32_t o; asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(v) : "memory"); return o; }
+
+#ifdef ZGPU_SORT_TIME // debug build only (scripts/sort_time.py): clock cycles of a wave in 0 setup, 1 pass A (without 2), 2 waiting for the token, 3 pass B, 4 pass C0,
+                      // 5 head bits out + heads_below, 6 pass C1 + V, 7 a turn's atomics from issue to result (taken out of 1); a section ends behind its barrier, so it holds
+                      // the wait for the slowest wave.  sort_time[8]: the most workgroups seen on one CU at a time.
+__device__ unsigned long long sort_time[9];
+__device__ unsigned int sort_on_cu[16 * 256];
+extern "C" __attribute__((visibility("default"))) void zgpu_debug_sort_time(unsigned long long *out, int reset)
+{
+    unsigned long long z[9] = {};
+    hipMemcpyFromSymbol(out, HIP_SYMBOL(sort_time), sizeof z);
+    if (reset) hipMemcpyToSymbol(HIP_SYMBOL(sort_time), z, sizeof z);
+}
+// (summed in registers, written once when the wave is done, as walk_kernel's clock below)
+#define S_T0() unsigned long long st_prev = __builtin_readcyclecounter(), st_tok = 0, st_atm = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; \
+    const uint32_t st_cu = ((__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u) << 8) | ((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 8) & 255u); /* XCC_ID, HW_ID: cu, sh, se */ \
+    if (threadIdx.x == 0) atomicMax(&sort_time[8], (unsigned long long)atomicAdd(&sort_on_cu[st_cu], 1u) + 1)
+#define S_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); st_acc[i] += t_ - st_prev - ((i) == 1 ? st_tok + st_atm : 0); if ((i) == 1) { st_acc[2] += st_tok; st_acc[7] += st_atm; } st_tok = st_atm = 0; st_prev = t_; } while (0)
+#define S_TOK(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); stmt; st_tok += __builtin_readcyclecounter() - f0_; } while (0)
+#define S_A0() const unsigned long long a0_ = __builtin_readcyclecounter()
+#define S_A1() st_atm += __builtin_readcyclecounter() - a0_
+#define S_TEND() do { if (lane == 0) for (int i_ = 0; i_ < 8; i_++) atomicAdd(&sort_time[i_], st_acc[i_]); if (threadIdx.x == 0) atomicSub(&sort_on_cu[st_cu], 1u); } while (0)
+#else
+#define S_A0() do { } while (0)
+#define S_A1() do { } while (0)
+#define S_T0() do { } while (0)
+#define S_T(i) do { } while (0)
+#define S_TOK(stmt) stmt
+#define S_TEND() do { } while (0)
+#endif
 
 __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t *__restrict__ S_all, uint32_t *__restrict__ heads_all, uint32_t *__restrict__ fault,
                                                            uint32_t *__restrict__ ir_all, ChunkMeta *__restrict__ meta)
@@ -291,6 +325,7 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
     __shared__ uint32_t token;
     __shared__ __attribute__((aligned(8))) uint32_t heads[kChunkMax / 32]; // bit i: S[i] is the first entry of its bucket
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    S_T0();
     uint64_t lo; uint32_t n;
     chunk_span(g, c, lo, n);
     const uint8_t *src = g.in + lo;
@@ -309,6 +344,7 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
         for (uint32_t i = tid; i < kChunkMax / 32; i += kS4Threads) heads[i] = 0;
     }
     __syncthreads();
+    S_T(0);
     auto bytes3 = [&](uint32_t p) -> uint32_t { // b0 | b1<<8 | b2<<16 of position p < npos
         if (p + 4 <= n) return reinterpret_cast<const U32u *>(src + p)->v & 0xffffffu;
         return (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16);
@@ -318,10 +354,26 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
     constexpr uint32_t kNone32 = 0xffffffffu;
     uint32_t pk[kTurnsPerWave][kS4TurnSteps]; // this lane's 64 positions: hash -> hash | rank << 16 -> index | rank << 16; kNone32: no position, or not in the chains
 
+    // A turn in the middle of the chunk -- all but the last of a full one: every position exists, has four bytes to load and is in the chains.
+    // The sort is bound by the instructions it issues (DESIGN.md 4, K1'''), and the general form of passes A and C0 spends more of them on the
+    // conditions of a position, lane masks and branches, than on its hash: such a turn takes a straight path in both.  (T: a scalar.)
+    auto whole_turn = [&](uint32_t T) { return nout == 0 && T * kS4TurnPos + kS4TurnPos + 3 <= n; };
+
     // ---- pass A: rank(p) ----
     {
         uint32_t s1 = 0, s2 = 0; // Adler: sum of this lane's bytes, and of (n - p) * byte (64 positions a lane: below 2^32)
-        auto preload = [&](uint32_t T, uint32_t (&h)[kS4TurnSteps]) {
+        auto preload = [&](uint32_t Tv, uint32_t (&h)[kS4TurnSteps]) {
+            const uint32_t T = __builtin_amdgcn_readfirstlane(Tv); // (the wave's number: the same in all lanes, and now the compiler knows)
+            if (whole_turn(T)) { // (scalar)
+                const uint8_t *q = src + T * kS4TurnPos + lane;
+#pragma unroll
+                for (uint32_t u = 0; u < kS4TurnSteps; u++) {
+                    const uint32_t v = reinterpret_cast<const U32u *>(q + 64 * u)->v & 0xffffffu, b0 = v & 255u;
+                    h[u] = hash_of(v);
+                    s1 += b0; s2 += (n - (T * kS4TurnPos + 64 * u + lane)) * b0;
+                }
+                return;
+            }
 #pragma unroll
             for (uint32_t u = 0; u < kS4TurnSteps; u++) {
                 const uint32_t p = T * kS4TurnPos + 64 * u + lane, v = p < npos ? bytes3(p) : 0u;
@@ -347,11 +399,13 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
                     aa[u] = cnt_a + (ok ? (pk[j][u] >> 1) << 2 : 0);
                     vv[u] = ok ? 1u << ((pk[j][u] & 1u) << 4) : 0; // adding 0 is harmless
                 }
-                while (lds_ld32(tok_a) != T) __builtin_amdgcn_s_sleep(1);
+                S_TOK(while (lds_ld32(tok_a) != T) __builtin_amdgcn_s_sleep(1));
+                S_A0();
 #pragma unroll
                 for (uint32_t u = 0; u < kS4TurnSteps; u++) old[u] = lds_add_rtn32_nowait(aa[u], vv[u]);
                 lds_st32(tok_a, T + 1);
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(old[0]), "+v"(old[1]), "+v"(old[2]), "+v"(old[3]), "+v"(old[4]), "+v"(old[5]), "+v"(old[6]), "+v"(old[7])::"memory");
+                S_A1();
                 static_assert(kS4TurnSteps == 8, "the wait names eight results");
 #pragma unroll
                 for (uint32_t u = 0; u < kS4TurnSteps; u++)
@@ -364,6 +418,7 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
         if (lane == 0) { ad1[wave] = s1; ad2[wave] = t2; }
     }
     __syncthreads();
+    S_T(1);
     if (tid == 0) { // A = 1 + sum b_i, B = n + sum (n - i) b_i (mod 65521); the last two bytes start no three-byte string and are added here
         uint64_t a = 1, b = n;
         for (uint32_t w = 0; w < kS4Waves; w++) { a += ad1[w]; b += ad2[w] % 65521u; }
@@ -399,14 +454,24 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
         for (uint32_t i = 0; i < nv; i++) c4[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
     }
     __syncthreads();
+    S_T(3);
 
     // ---- pass C0: idx(p) = start(hash) + rank: the position's ir word, written and kept; a bit per bucket head ----
     const uint16_t *start = reinterpret_cast<const uint16_t *>(cnt);
 #pragma unroll
     for (uint32_t j = 0; j < kTurnsPerWave; j++) {
-        const uint32_t T = wave + j * kS4Waves;
+        const uint32_t T = __builtin_amdgcn_readfirstlane(wave + j * kS4Waves);
         __builtin_amdgcn_sched_barrier(0); // one turn's eight at a time: all 64 in flight do not fit the registers
-        if (T < nturns) {
+        if (T < nturns && whole_turn(T)) { // (scalar) every position has a rank: no lane masks
+            uint32_t *irp = ir + T * kS4TurnPos + lane;
+#pragma unroll
+            for (uint32_t u = 0; u < kS4TurnSteps; u++) {
+                const uint32_t r = pk[j][u] >> 16, id = (uint32_t)start[pk[j][u] & 0x7fffu] + r;
+                pk[j][u] = id | (r << 16);
+                irp[64 * u] = pk[j][u];
+                if (r == 0) atomicOr(&heads[id >> 5], 1u << (id & 31u));
+            }
+        } else if (T < nturns) {
 #pragma unroll
             for (uint32_t u = 0; u < kS4TurnSteps; u++) {
                 const uint32_t p = T * kS4TurnPos + 64 * u + lane;
@@ -420,8 +485,10 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
         }
     }
     __syncthreads();
+    S_T(4);
     for (uint32_t i = tid; i < kChunkMax / 32; i += kS4Threads) hd[i] = heads[i];
     reinterpret_cast<uint16_t *>(hd + kHeadWords)[tid] = (uint16_t)heads_below(reinterpret_cast<const unsigned long long *>(heads)[tid], tid, wave_tot);
+    S_T(5);
 
     // ---- pass C1: the scatter through LDS, half of S at a time, and pass V, the self-check ----
     uint16_t *stage = reinterpret_cast<uint16_t *>(cnt);
@@ -459,6 +526,8 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
         if (half == 0 && nin > 32768u) { __syncthreads(); last_of_half0 = stage[32767]; } // (uniform branch)
     }
     if (bad) atomicOr(fault, 1u);
+    S_T(6);
+    S_TEND();
 }
 
 // ------------------------------------------------------------------------------------------------- K2'
