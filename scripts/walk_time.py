@@ -1,4 +1,7 @@
-"""Debug helper (GPU box): where a wave of walk_kernel spends its cycles, from a -DZGPU_WALK_TIME build (ZAMD_GPU_LIB=build/variants/wtime.so)."""
+"""Debug helper (GPU box): where a wave of walk_kernel spends its cycles, from a -DZGPU_WALK_TIME build (ZAMD_GPU_LIB=build/variants/wtime.so).
+Sections: "bodies: byte reads" is the one batch of LDS reads of a body -- the candidates' quick-check bytes and, since the scan string's two bytes ride with
+them, those as well (they were read in "folds" and in "pass: starts" before); "pass: parse" ends behind the one wait for the pass's two LDS atomics and holds
+the read of the eight scan bytes a starting search keeps in registers; "pass: starts" has no LDS wait of its own left."""
 import ctypes
 import os
 import sys

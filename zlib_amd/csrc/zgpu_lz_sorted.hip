@@ -888,7 +888,7 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_time(unsi
 #define W_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); wt_acc[i] += t_ - wt_prev - ((i) == 1 ? wt_fold + wt_lds + wt_take : 0); \
                     if ((i) == 1) { wt_acc[2] += wt_fold; wt_acc[3] += wt_lds; wt_acc[7] += wt_take; } wt_fold = wt_lds = wt_take = 0; wt_prev = t_; } while (0)
 #define W_TF(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); stmt; wt_fold += __builtin_readcyclecounter() - f0_; } while (0)
-#define W_TL(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); stmt; wt_lds += __builtin_readcyclecounter() - f0_; } while (0)   // the body's batch of byte reads
+#define W_TL(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); stmt; wt_lds += __builtin_readcyclecounter() - f0_; } while (0)   // the body's batch of byte reads (candidates' and scan string's)
 #define W_TK(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stmt; wt_take += __builtin_readcyclecounter() - f0_; } while (0) // waiting for the groups a pass asked for
 #define W_TEND() do { if (lane == 0) for (int i_ = 0; i_ < 8; i_++) atomicAdd(&walk_time[i_], wt_acc[i_]); } while (0)
 #else
@@ -1016,9 +1016,8 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     uint32_t *ctrl = lds + kM3DataLds / 4; // [0]: next block to hand out
     uint32_t *NEU = ctrl + 4;              // bit p: some walker stands, or stood, at p with nothing in hand
     uint32_t *lcnt = lds + kWOffLcnt / 4;  // FUSE: games in the log of each window of kP2Win positions
-    const uint8_t *d8 = reinterpret_cast<const uint8_t *>(d32);
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t ring = (uint32_t)__builtin_amdgcn_readfirstlane(lds_off(lds) + kM3DataLds + 16 + kWNeuBytes + wave * kM3WaveLds), slot = ring + kRing * 4, pw = slot + 64 * 4;
+    const uint32_t ring = (uint32_t)__builtin_amdgcn_readfirstlane(lds_off(lds) + kM3DataLds + 16 + kWNeuBytes + wave * kM3WaveLds), slot = ring + kRing * 4;
     uint64_t lo; uint32_t n;
     chunk_span(g, c, lo, n);
     const uint8_t *src = g.in + lo;
@@ -1062,7 +1061,8 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     uint32_t irx = 0, irn = 0, irE = 0, irl = 0; // idx | rank << 16 of: x, x + 1, the position behind the match in hand, a position asked for in the last pass
     bool haveE = false;
     // search (as in match3_kernel); keys: len >= nice: 1<<31 | q<<9 | len, else len<<16 | q -- nearest candidate first = largest q
-    uint32_t rem = 0, best = kMinMatch - 1, key_seen = 0, sentinel = 0, scan2 = 0, boff = dbase + 1;
+    uint32_t rem = 0, best = kMinMatch - 1, key_seen = 0, sentinel = 0, boff = dbase + 1;
+    uint32_t sw0 = 0, sw1 = 0; // the eight bytes at x, from the start of a search on (fold)
     // candidates arrive in groups of eight (16 bytes of S).  A lane's loads are scattered over S: nothing is shared between lanes and
     // every group comes from L2 or beyond, a latency of several bodies; streaming the groups one body ahead (as match3 does with
     // its coalesced loads) left every body waiting for memory.  So a pass fetches the first 32 candidates of the searches it
@@ -1080,19 +1080,33 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         const uint32_t cnt = tail < 64 ? tail : 64;
         W_STAT(5, 1); W_STAT(6, cnt);
         tail = (uint32_t)__builtin_amdgcn_readfirstlane(tail - cnt);
+        // The owner's position and the first eight bytes of its scan string come out of the owner's registers (x, sw0, sw1), by ds_bpermute, in one
+        // flight with the candidate's first eight bytes, whose address needs the entry alone: one wait where the owner's position, read back from LDS,
+        // and then the two strings took one each.  ds_bpermute returns nothing from a lane that is switched off, and the owners of a fold's entries
+        // are any lanes of the wave: so all 64 lanes read an entry (the lanes at and above cnt a stale one of the ring -- some lane, some position of
+        // the chunk) and permute, and only the compare and the ds_max stand under lane < cnt.  x, sw0 and sw1 are those of the search the parked
+        // candidate belongs to because a pass folds the stack empty before it moves any x.
+        const uint32_t e = lds_ld32(ring + ((tail + lane) << 2)); // (tail + lane <= 126: inside the ring)
+        const uint32_t q = e & 0xffffu, o = (e >> 16) & 63u, qa = dbase + q;
+        uint32_t po, xa, xb;
+        {
+            uint64_t va; uint32_t va2, ow0, ow1;
+            asm volatile("ds_bpermute_b32 %0, %5, %6\n\tds_bpermute_b32 %1, %5, %7\n\tds_bpermute_b32 %2, %5, %8\n\t"
+                         "ds_read2_b32 %3, %9 offset1:1\n\tds_read_b32 %4, %9 offset:8\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(po), "=&v"(ow0), "=&v"(ow1), "=&v"(va), "=&v"(va2) : "v"(o << 2), "v"(x), "v"(sw0), "v"(sw1), "v"(qa & ~3u) : "memory");
+            xa = __builtin_amdgcn_alignbyte((uint32_t)(va >> 32), (uint32_t)va, qa & 3) ^ ow0;
+            xb = __builtin_amdgcn_alignbyte(va2, (uint32_t)(va >> 32), qa & 3) ^ ow1;
+        }
         if (lane < cnt) {
-            const uint32_t e = lds_ld32(ring + ((tail + lane) << 2));
-            const uint32_t q = e & 0xffffu, o = (e >> 16) & 63u;
-            const uint32_t po = lds_ld16(pw + o * 2), look = n - po, cap = look < kMaxMatch ? look : kMaxMatch, nice = cfg.nice < look ? cfg.nice : look;
+            const uint32_t look = n - po, cap = look < kMaxMatch ? look : kMaxMatch, nice = cfg.nice < look ? cfg.nice : look;
             // the candidate must be in reach: the first one of a chain at most MAX_DIST back (deflate.c:1588), the others strictly less
             // (deflate.c:1163), none at the NIL position.  Positions descend along a chain, so refusing them here one by one is the
             // reference's "the chain ends at the first candidate out of reach".
             const bool reach = po - q <= kMaxDist - ((e >> 22) & 1u ? 0u : 1u) && q + base >= 1u;
-            uint32_t l = 0, xa, xb;
-            for (;;) { // eight bytes of both strings per round trip
-                lds_cmp8(dbase + q + l, dbase + po + l, xa, xb);
-                if ((xa | xb) != 0 || l + 8 >= cap) break;
+            uint32_t l = 0;
+            while ((xa | xb) == 0 && l + 8 < cap) { // eight more bytes of both strings per round trip
                 l += 8;
+                lds_cmp8(qa + l, dbase + po + l, xa, xb);
             }
             uint32_t len = xa ? l + ((uint32_t)__builtin_ctz(xa) >> 3) : xb ? l + 4 + ((uint32_t)__builtin_ctz(xb) >> 3) : l + 8;
             len = len < cap ? len : cap;
@@ -1106,8 +1120,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         if (key != key_seen) {
             key_seen = key;
             best = (key >> 31) ? key & 0x1ffu : key >> 16;
-            boff = dbase + best - 1;
-            scan2 = (uint32_t)d8[x + best - 1] | ((uint32_t)d8[x + best] << 16);
+            boff = dbase + best - 1; // (the scan string's bytes at the new best length are read by the next body, with its candidates')
         }
         amask &= ~mask_lt_i32((int)key, 0); // nice_match: that walk is over (deflate.c:1224)
     };
@@ -1123,8 +1136,8 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         const bool fin = st == W_SEARCH && !(((amask | jmask) >> lane) & 1ull) && !cont;
         W_STAT(2, 1); W_STAT(3, __popcll(__builtin_amdgcn_ballot_w64(fin || st == W_LIMBO || st == W_NEED)));
         if (st == W_LIMBO) { irx = irl; st = W_READY; } // what the last pass asked for has arrived
-        uint32_t y = 0, irY = 0;
-        bool toN = false, haveIr = false;
+        uint32_t y = 0, irY = 0, rec = 0;
+        bool toN = false, haveIr = false, emit = false;
         if (fin) {
             uint32_t len = kMinMatch - 1, dist = 0;
             if (key_seen != sentinel) {
@@ -1133,7 +1146,6 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
                 dist = x - (nz ? (key_seen >> 9) & 0xffffu : key_seen & 0xffffu);
             }
             if (len <= 5 && (cfg.strategy == kFiltered || (len == kMinMatch && dist > kTooFar))) len = kMinMatch - 1; // deflate.c:1601-1611
-            bool emit = false;
             if (len > handL) { // a (longer) match at x: the byte before it, if a match was in hand, becomes a literal (deflate.c:1642-1651)
                 if (handL < kMinMatch) gstart = x;
                 handL = len; handD = dist; handM = x;
@@ -1143,11 +1155,8 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             } else if (handL >= kMinMatch) emit = true;            // the match in hand stands (deflate.c:1611-1634)
             else { y = x + 1; irY = irn; toN = haveIr = true; }    // a literal
             if (emit) {
-                const uint32_t rec = ((handM - gstart) << 24) | (handL << 15) | handD;
-                if (FUSE) { // appended to the log of the game's window: slots go out in time order, so the stores in flight fill a few lines side by side
-                    const uint32_t w = gstart / kP2Win, at = w * kP2Win + atomicAdd(&lcnt[w], 1u); // (at most one game per position: the slot is below kP2Win)
-                    lrec[at] = rec; lpos[at] = (uint16_t)gstart;
-                } else {
+                rec = ((handM - gstart) << 24) | (handL << 15) | handD;
+                if (!FUSE) {
                     gm[gstart] = rec;
                     atomicOr(&gs[gstart >> 5], 1u << (gstart & 31u));
                 }
@@ -1155,16 +1164,36 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
                 handL = kMinMatch - 1;
             }
         }
+        // The pass's two LDS atomics -- the slot in the log of the game's window (FUSE) and the meeting bit at y -- depend on registers alone: both are
+        // issued from straight-line code by every lane and waited for once.  A lane that has no game to log, or no position to claim, adds 0 to (ORs 0
+        // into) its own word of the wave's ring, which the drain has left empty: harmless.  The eight bytes a search that starts in this pass keeps of
+        // its scan string (sw0, sw1) ride along: wherever the lane starts one, it is at y if the lane turns neutral here and at x otherwise (a block handed
+        // out below is not searched before the next pass).
+        const uint32_t yc = y >> kWNeuShift, ybit = 1u << (yc & 31u);
+        const bool meet = (y & ((1u << kWNeuShift) - 1u)) == 0; // (elsewhere walkers pass each other unseen: the same work twice, the same result)
+        const bool claim = toN && y < wlim && meet;
+        const uint32_t own = ring + lane * 4, lw = gstart / kP2Win;
+        const uint32_t xs = dbase + (toN ? y : x); // (y <= n: inside the chunk or its zero pad)
+        uint32_t lslot = 0, yold, tw2; uint64_t tw;
+        if (FUSE) {
+            asm volatile("ds_add_rtn_u32 %0, %4, %5\n\tds_or_rtn_b32 %1, %6, %7\n\tds_read2_b32 %2, %8 offset1:1\n\tds_read_b32 %3, %8 offset:8\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(lslot), "=&v"(yold), "=&v"(tw), "=&v"(tw2)
+                         : "v"(emit ? lds_off(lcnt) + lw * 4 : own), "v"(emit ? 1u : 0u), "v"(claim ? lds_off(NEU) + (yc >> 5) * 4 : own), "v"(claim ? ybit : 0u), "v"(xs & ~3u) : "memory");
+        } else {
+            asm volatile("ds_or_rtn_b32 %0, %3, %4\n\tds_read2_b32 %1, %5 offset1:1\n\tds_read_b32 %2, %5 offset:8\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(yold), "=&v"(tw), "=&v"(tw2) : "v"(claim ? lds_off(NEU) + (yc >> 5) * 4 : own), "v"(claim ? ybit : 0u), "v"(xs & ~3u) : "memory");
+        }
+        const uint32_t tw0 = __builtin_amdgcn_alignbyte((uint32_t)(tw >> 32), (uint32_t)tw, xs & 3), tw1 = __builtin_amdgcn_alignbyte(tw2, (uint32_t)(tw >> 32), xs & 3);
+        if (FUSE && emit) { // appended to the log of the game's window: slots go out in time order, so the stores in flight fill a few lines side by side
+            const uint32_t at = lw * kP2Win + lslot; // (at most one game per position: the slot is below kP2Win)
+            lrec[at] = rec; lpos[at] = (uint16_t)gstart;
+        }
         if (toN) { // neutral at y
             st = W_NEED;
-            if (y < wlim) {
-                const uint32_t yc = y >> kWNeuShift, bit = 1u << (yc & 31u);
-                const bool meet = (y & ((1u << kWNeuShift) - 1u)) == 0; // (elsewhere walkers pass each other unseen: the same work twice, the same result)
-                if (!meet || !(atomicOr(&NEU[yc >> 5], bit) & bit)) { // nobody has been here: go on
-                    x = y;
-                    if (haveIr) { irx = irY; st = W_READY; }
-                    else { irl = y < npos ? ir[y] : 0; st = W_LIMBO; W_STAT(7, 1); }
-                }
+            if (y < wlim && (!meet || !(yold & ybit))) { // nobody has been here: go on
+                x = y;
+                if (haveIr) { irx = irY; st = W_READY; }
+                else { irl = y < npos ? ir[y] : 0; st = W_LIMBO; W_STAT(7, 1); }
             }
         }
         W_T(5);
@@ -1201,9 +1230,8 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             }
             else if (x + base == kWSize + kMaxDist && avail != 0 && (int)x >= slide_at && (uint32_t)S[idx - 1] + base == kWSize) avail = 0;
             best = seed; sentinel = (seed << 16) | 0xffffu; key_seen = sentinel; boff = dbase + best - 1;
-            scan2 = (uint32_t)d8[x + best - 1] | ((uint32_t)d8[x + best] << 16);
             lds_st32(slot + lane * 4, sentinel);
-            lds_st16(pw + lane * 2, x);
+            sw0 = tw0; sw1 = tw1; // the eight bytes at x (read with the pass's atomics)
             lanebits = (lane << 16) | (seed << 23);
             rem = avail; firstb = 1u << 22;
             gi = (int)idx - 8;
@@ -1232,44 +1260,43 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             if (amask) {
                 W_STAT(0, 1);
                 // the quick-check bytes of all eight candidates in one round trip, read at the best length the body starts with: a fold
-                // inside the body moves best/boff/scan2 for the next body, the rest of this one goes on with what it read (walking with a
-                // stale best length is exact, see match3_kernel).  A lane examines nv = min(rem, 8) candidates; for the others of the
-                // group -- and for all eight in lanes that examine nothing -- it reads a fixed word whose two bytes differ from scan0, so
-                // that a hit is a hit of a real candidate and no step needs the walking mask (whether a candidate is in reach is
-                // checked when it is compared in full, fold()).
+                // inside the body moves best/boff for the next body, the rest of this one goes on with what it read (walking with a
+                // stale best length is exact, see match3_kernel).  The scan string's own two bytes at that length (scan0) ride in the same
+                // batch, from boff + x: they and the candidates' are read at one best length by construction, and neither a fold nor the
+                // start of a search has to fetch them and wait.  A lane that examines nothing reads the zero pad for its candidates and the
+                // 0xFF words behind it for its scan bytes, so that a hit is a hit of a real candidate and no step needs the walking mask
+                // (whether a candidate is in reach is checked when it is compared in full, fold()).
                 // Addresses straight from the halves of G0 (SDWA: no extraction).  Which of the eight are candidates at all is NOT checked here:
-                // a lane that examines nothing compares with a value no two bytes can make; a lane whose chain ends inside the group reads on into
+                // a lane that examines nothing compares two fixed words that differ; a lane whose chain ends inside the group reads on into
                 // the entries below its bucket, whose hashes -- so their first three bytes -- differ from the scan string's: the full comparison
                 // (fold) finds fewer than MIN_MATCH bytes and drops them.  Only a chain cut short by the BUDGET goes on into entries of its own
                 // bucket that must not be looked at: budgets are multiples of eight (whole groups) except at level 4, in tuned configurations and
-                // for Z_RLE -- `vexact`: those take the sentinel address for the entries past the chain's end, as every body did before.
-                const uint32_t scan0 = sel_mask(amask0, scan2, 0xffffffffu);
-                uint32_t bb[8], a[8], boff_e;
-                boff_e = boff;
+                // for Z_RLE -- `vexact`: there a lane examines nv = min(rem, 8) candidates, the hits of the entries past them are masked out, and
+                // a lane that examines nothing compares with a value no two bytes can make (ONE uniform branch behind the compares: a branch per
+                // candidate, though never taken at levels 5-9, made their bodies a fifth longer: profiles/walk_fold_summary.txt).
+                uint32_t bb[8], a[8], boff_e, as;
+                boff_e = boff; as = boff + x;
                 if (!vexact) { // the lanes that examine nothing read ONE common word (a broadcast): with whatever their registers held they were a third of the kernel's bank conflicts
                     const uint32_t boff_i = dbase + kChunkMax + 8u;
                     G0.x = sel_mask(amask0, G0.x, 0u); G0.y = sel_mask(amask0, G0.y, 0u); G0.z = sel_mask(amask0, G0.z, 0u); G0.w = sel_mask(amask0, G0.w, 0u);
-                    boff_e = sel_mask(amask0, boff, boff_i);
+                    boff_e = sel_mask(amask0, boff, boff_i); as = sel_mask(amask0, as, boff_i + 64u);
                 }
                 a[0] = add_w1(boff_e, G0.w); a[1] = add_w0(boff_e, G0.w); a[2] = add_w1(boff_e, G0.z); a[3] = add_w0(boff_e, G0.z); // nearest candidate = highest address
                 a[4] = add_w1(boff_e, G0.y); a[5] = add_w0(boff_e, G0.y); a[6] = add_w1(boff_e, G0.x); a[7] = add_w0(boff_e, G0.x);
-                if (vexact) { // (uniform)
-                    const uint32_t nv = rem < 8 ? rem : 8, sent = dbase + (scan2 ? kChunkMax + 8u : kChunkMax + 64u + 8u); // zero pad | the 0xFF words behind it: two bytes that differ from the scan string's
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; j++) a[j] = j < nv ? a[j] : sent;
-                }
-                uint32_t hi[8]; // (d16 loads would fill both halves of one register, but with SRAM ECC on they clear the other half)
+                uint32_t hi[8], s0, s1; // (d16 loads would fill both halves of one register, but with SRAM ECC on they clear the other half)
                 W_TL(
-                    asm volatile("ds_read_u8 %0, %16\n\tds_read_u8 %8, %16 offset:1\n\tds_read_u8 %1, %17\n\tds_read_u8 %9, %17 offset:1\n\t"
-                                 "ds_read_u8 %2, %18\n\tds_read_u8 %10, %18 offset:1\n\tds_read_u8 %3, %19\n\tds_read_u8 %11, %19 offset:1\n\t"
-                                 "ds_read_u8 %4, %20\n\tds_read_u8 %12, %20 offset:1\n\tds_read_u8 %5, %21\n\tds_read_u8 %13, %21 offset:1\n\t"
-                                 "ds_read_u8 %6, %22\n\tds_read_u8 %14, %22 offset:1\n\tds_read_u8 %7, %23\n\tds_read_u8 %15, %23 offset:1\n\t"
+                    asm volatile("ds_read_u8 %0, %18\n\tds_read_u8 %8, %18 offset:1\n\tds_read_u8 %1, %19\n\tds_read_u8 %9, %19 offset:1\n\t"
+                                 "ds_read_u8 %2, %20\n\tds_read_u8 %10, %20 offset:1\n\tds_read_u8 %3, %21\n\tds_read_u8 %11, %21 offset:1\n\t"
+                                 "ds_read_u8 %4, %22\n\tds_read_u8 %12, %22 offset:1\n\tds_read_u8 %5, %23\n\tds_read_u8 %13, %23 offset:1\n\t"
+                                 "ds_read_u8 %6, %24\n\tds_read_u8 %14, %24 offset:1\n\tds_read_u8 %7, %25\n\tds_read_u8 %15, %25 offset:1\n\t"
+                                 "ds_read_u8 %16, %26\n\tds_read_u8 %17, %26 offset:1\n\t"
                                  "s_waitcnt lgkmcnt(0)"
                                  : "=&v"(bb[0]), "=&v"(bb[1]), "=&v"(bb[2]), "=&v"(bb[3]), "=&v"(bb[4]), "=&v"(bb[5]), "=&v"(bb[6]), "=&v"(bb[7]),
-                                   "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]), "=&v"(hi[4]), "=&v"(hi[5]), "=&v"(hi[6]), "=&v"(hi[7])
-                                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]) : "memory"));
+                                   "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]), "=&v"(hi[4]), "=&v"(hi[5]), "=&v"(hi[6]), "=&v"(hi[7]), "=&v"(s0), "=&v"(s1)
+                                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(as) : "memory"));
 #pragma unroll
                 for (uint32_t j = 0; j < 8; j++) bb[j] |= hi[j] << 16;
+                const uint32_t scan0 = s0 | (s1 << 16);
                 W_STAT(1, __popcll(amask0) * 8);
                 // The hits of all eight comparisons are counted first (scalar), then parked in one straight run: no branch and no fold between
                 // two candidates -- a wave's critical path through a body is what bounds the kernel, not the number of its instructions.  The stack
@@ -1279,7 +1306,13 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
                 unsigned long long mm[8];
                 uint32_t total = 0;
 #pragma unroll
-                for (uint32_t j = 0; j < 8; j++) { mm[j] = mask_eq_u32(bb[j], scan0); total += (uint32_t)__popcll(mm[j]); }
+                for (uint32_t j = 0; j < 8; j++) mm[j] = mask_eq_u32(bb[j], scan0);
+                if (vexact) { // (uniform)
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; j++) mm[j] &= amask0 & mask_gt_u32(rem, j);
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++) total += (uint32_t)__popcll(mm[j]);
                 auto entry_of = [&](uint32_t j) -> uint32_t {
                     const uint32_t wd = j < 2 ? G0.w : j < 4 ? G0.z : j < 6 ? G0.y : G0.x, lb = j == 0 ? lf : lanebits;
                     return (j & 1) ? and_or(wd, 0xffffu, lb) : or_w1(lb, wd);
