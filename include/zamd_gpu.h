@@ -244,6 +244,62 @@ int zgpu_deflate_segments_items_host(zgpu_engine *e, const void *in, const uint6
  * engine with the default geometry (windowBits 15, memLevel 8; zgpu_deflate_set_geometry); the host entry sizes its own staging in any case. */
 uint64_t zgpu_deflate_segments_bound(uint64_t nseg, uint64_t in_bytes, uint32_t flags);
 
+/* ---- stream-ordered batch deflate: the segment calls above, enqueued ----
+ * For a caller whose data lives on the GPU.  Item k = d_in[d_in_offsets[k] .. d_in_offsets[k+1]), at most 65536 bytes (65280 with ZGPU_F_BGZF_WRAP), becomes
+ * the stream zgpu_deflate_segments_items_device makes of that segment with the same p: raw deflate, or with ZGPU_F_ZLIB_WRAP / ZGPU_F_GZIP_WRAP /
+ * ZGPU_F_BGZF_WRAP a zlib stream, a gzip member, a BGZF block (BSIZE filled in; the 28-byte end block is the caller's to append); ZGPU_F_CRC32 as usual.
+ * A call puts kernel launches on hip_stream (null: the engine's stream) as ONE chain and returns; it does not synchronize, allocate,
+ * copy to or from host memory, record an event, use a second stream or time anything, and it uses no device memory of the engine's: its scratch is d_ws,
+ * device memory of the caller's, 256-byte aligned, of at least zgpu_deflate_batch_workspace_bytes(n, batch_items) bytes (a function of n and of
+ * min(n, batch_items) alone -- never of the bytes, the level or the wrapper; it needs no engine and no GPU; about 1.39 MiB per item of a round, the staging
+ * buffer the round's items are gathered into included).  The engine supplies the device, the error text, zgpu_deflate_set_tuning's row and the choice of the sort, nothing else:
+ * two calls with different workspaces may be in flight on different streams of one engine, a call can wait in a stream behind the kernel that makes its
+ * input, and it can be captured into a graph (not the first call of a process: that one loads the code).  d_in, the tables, d_out, d_items, d_summary
+ * and d_ws are read and written in stream order: they must be valid when the work runs, and stay untouched by other streams until it is done.
+ * batch_items: items per round of launches, 0 = min(n, 4096).  Rounds follow one another in stream order in the same workspace; the packed entry's
+ * running total is carried from round to round on the device.
+ * Served: ZGPU_F_FINAL (required), levels 1..9 with ZGPU_LZ_AUTO -- levels 4-9 the parse-driven search (ZGPU_LZ_WALK), levels 1-3 the wave-per-chunk
+ * kernel (ZGPU_LZ_FASTWIN) -- Z_DEFAULT_STRATEGY, Z_FILTERED, Z_FIXED, the engine's zgpu_deflate_set_tuning as in the blocking call.
+ * Refused at once with ZGPU_STREAM_ERROR and nothing enqueued: what the chain cannot serve without a decision of the host's or the lane-per-chunk loop's
+ * tables -- Z_HUFFMAN_ONLY, Z_RLE, a deflateTune row the record searches or the levels 1-3 kernels refuse, a geometry other than windowBits 15 /
+ * memLevel 8, prime, ZGPU_F_POS0 / _POS0_ALL / _CONTINUOUS, any lz_impl but ZGPU_LZ_AUTO, two wrappers -- and every argument the host can judge: a null
+ * pointer that is needed, n >= 2^32, ws_bytes too small, d_ws not 256-byte aligned.  n == 0 enqueues at most the launch that clears the summary.
+ * d_items[k] (device memory, n records): code = ZGPU_OK with out_lo / out_bytes / in_bytes / data_type / adler32 / crc32 exactly as zgpu_deflate_item has
+ * them for that segment.  The host never sees the tables, so a bad entry fails its item, not the call: offsets that run backwards or leave in_bytes
+ * (counted in nbad_offsets) or lie further apart than an item may be long (ntoo_long) give code = ZGPU_STREAM_ERROR, out_bytes = in_bytes = 0,
+ * adler32 = 1, crc32 = 0, data_type = 2; such an item reads nothing, writes nothing and occupies no output, and every other item is served as if it
+ * were not there.
+ * zgpu_deflate_batch_enqueue: d_out_offsets (n + 1 entries, read) gives item k the room d_out[oo[k] .. oo[k+1]).  A stream that does not fit: ZGPU_BUF_ERROR
+ * with out_bytes = the size needed, its room untouched.  A range that runs backwards or leaves out_cap: ZGPU_STREAM_ERROR, counted in nbad_offsets.
+ * zgpu_deflate_batch_packed_enqueue: the streams lie back to back in item order, as the blocking call lays them; d_out_offsets (n + 1 entries, written)
+ * and total = d_out_offsets[n] are always written.  total > out_cap: overflow = 1, the items that lie wholly inside out_cap are written and ZGPU_OK, the
+ * others ZGPU_BUF_ERROR with their sizes.
+ * No byte outside d_out[0, out_cap), d_items, d_summary (optional) and d_ws is ever written.  nfailed = records that are not ZGPU_OK.
+ * The sort's self-check: the chain sorts with the fast position sort unless the engine is set to the exact one.  Its fault word lies in d_ws, is cleared at
+ * the head of the chain and read by the call's last launch: raised, sort_fault = 1, every record has code = ZGPU_ERRNO, nfailed = n, and the bytes in d_out
+ * are unspecified (but inside d_out).  The blocking calls redo themselves with the exact sort then; an enqueued call has returned long before, so the
+ * CALLER does it: zgpu_engine_set_exact_sort(e, 1) -- the setting the blocking fallback makes, reported by zgpu_debug_sort_fallback -- and enqueue again.
+ * Rates (profiles/r09_deflate_enqueue_table.txt, level 6, device-resident), enqueue over blocking: 0.84 for 200 batches of 64 items of 4 KiB on one stream,
+ * 1.005 for one batch of 4,096 items of 64 KiB, 1.14 for one batch of 16,384 items of 4 KiB in the default rounds of 4,096 (1.003 in one round). */
+typedef struct {
+    int32_t code;
+    uint32_t data_type;
+    uint64_t out_lo, out_bytes;
+    uint32_t in_bytes, adler32, crc32, reserved;
+} zgpu_deflate_batch_item;
+typedef struct {
+    uint64_t nfailed, nbad_offsets, ntoo_long, total;
+    uint32_t overflow, sort_fault;
+} zgpu_deflate_batch_summary;
+uint64_t zgpu_deflate_batch_workspace_bytes(uint64_t n, uint32_t batch_items); /* 0: n >= 2^32 */
+int zgpu_deflate_batch_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, const zgpu_deflate_params *p,
+                               void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_deflate_batch_item *d_items,
+                               zgpu_deflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, uint32_t batch_items, void *hip_stream);
+int zgpu_deflate_batch_packed_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, const zgpu_deflate_params *p,
+                                      void *d_out, uint64_t out_cap, uint64_t *d_out_offsets, zgpu_deflate_batch_item *d_items,
+                                      zgpu_deflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, uint32_t batch_items, void *hip_stream);
+int zgpu_engine_set_exact_sort(zgpu_engine *e, int on); /* on != 0: the engine's calls use the ballot-ranked sort, which needs no self-check; 0: the fast sort again */
+
 /* ---- BGZF: blocked gzip, the container of bgzip, BAM, tabix and .vcf.gz (RFC 1952 + SAM specification 4.1) ----
  * A file is gzip members laid end to end, each at most 64 KiB long and decoding to at most 64 KiB, each carrying its own total length in its header
  * (BSIZE in the 'B' 'C' extra subfield), closed by a fixed 28-byte empty block.

@@ -23,6 +23,7 @@
 //        fast_kernel    levels 1-3 (ZGPU_LZ_FAST): deflate_fast on the sorted buckets, one lane per chunk
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
+#include "zgpu_deflate_batch_plan.h"
 #define ZGPU_PARSE_HEADER_ONLY
 #include "zgpu_lz_parse.h"
 #include <cstdlib>
@@ -63,7 +64,7 @@ struct SortedWs {
     static constexpr size_t kSlack = 1024; // S's end is rounded up to 256 bytes; the rest is margin
     static_assert(kChunkMax * 4 + kChunkMax / 8 <= kRecBytes && kGStride <= kRecBytes, "gm + gs, and G, lie in the records' memory");
     static_assert(kChunkMax * (4 + 2) <= kRecBytes, "and so do the logs: the workspace, and with it the batch a device holds, is what it was");
-    static size_t bytes(size_t nchunks) { return kHeaderBytes + nchunks * (kSBytes + kRkBytes + kHeadBytes + kRecBytes + kIrBytes) + kSlack; }
+    static constexpr size_t bytes(size_t nchunks) { return kHeaderBytes + nchunks * (kSBytes + kRkBytes + kHeadBytes + kRecBytes + kIrBytes) + kSlack; }
 
     size_t nch;
     uint32_t *fault; uint16_t *S, *rk; uint32_t *heads; uint2 *recs; uint32_t *ir;
@@ -85,6 +86,8 @@ struct SortedWs {
     uint8_t *G() const { return reinterpret_cast<uint8_t *>(recs); }
 };
 
+static_assert(SortedWs::kHeaderBytes == kDwsSortedHeader && SortedWs::kSlack == kDwsSortedSlack && SortedWs::bytes(1) == kDwsSortedHeader + kDwsSortedChunk + kDwsSortedSlack &&
+              SortedWs::bytes(3) - SortedWs::bytes(2) == kDwsSortedChunk, "zgpu_deflate_batch_plan.h states the workspace of a chunk as numbers");
 size_t lz_sorted_workspace_bytes(uint32_t batch) { return SortedWs::bytes(batch); }
 uint32_t *lz_sorted_fault_word(void *workspace) { return SortedWs(workspace, 0).fault; }
 

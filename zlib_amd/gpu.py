@@ -62,6 +62,17 @@ class DeflateItem(C.Structure):
     _fields_ = [("out_lo", C.c_uint64), ("out_bytes", C.c_uint64), ("in_bytes", C.c_uint32), ("data_type", C.c_uint32), ("adler32", C.c_uint32), ("crc32", C.c_uint32)]
 
 
+class DeflateBatchItem(C.Structure):
+    """zgpu_deflate_batch_item: the record of one item of a stream-ordered batch deflate call (zgpu_deflate_batch_*_enqueue)."""
+    _fields_ = [("code", C.c_int32), ("data_type", C.c_uint32), ("out_lo", C.c_uint64), ("out_bytes", C.c_uint64), ("in_bytes", C.c_uint32), ("adler32", C.c_uint32),
+                ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DeflateBatchSummary(C.Structure):
+    """zgpu_deflate_batch_summary: what a stream-ordered batch deflate call leaves in device memory besides the records."""
+    _fields_ = [("nfailed", C.c_uint64), ("nbad_offsets", C.c_uint64), ("ntoo_long", C.c_uint64), ("total", C.c_uint64), ("overflow", C.c_uint32), ("sort_fault", C.c_uint32)]
+
+
 class CheckItem(C.Structure):
     """zgpu_check_item: the checksums of one item of zgpu_checksum_batch_*."""
     _fields_ = [("adler32", C.c_uint32), ("crc32", C.c_uint32)]
@@ -111,6 +122,12 @@ def load_library():
     L.zgpu_deflate_segments_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp]
     L.zgpu_deflate_segments_items_host.argtypes = [vp, vp, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp]
     L.zgpu_deflate_segments_items_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, C.POINTER(DeflateResult), vp, vp]
+    L.zgpu_deflate_batch_workspace_bytes.argtypes = [u64, u32]
+    L.zgpu_deflate_batch_workspace_bytes.restype = u64
+    L.zgpu_deflate_batch_enqueue.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, vp, vp, u64, u32, vp]
+    L.zgpu_deflate_batch_packed_enqueue.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, vp, vp, u64, u32, vp]
+    L.zgpu_engine_set_exact_sort.argtypes = [vp, C.c_int]
+    L.zgpu_debug_sort_fallback.argtypes = [vp]
     L.zgpu_checksum_batch_host.argtypes = [vp, vp, u64, vp, u64, u32, vp]
     L.zgpu_checksum_batch_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp]
     L.zgpu_inflate_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, C.POINTER(InflateResult), vp]
@@ -490,6 +507,31 @@ class Engine:
         """The packed decode, enqueued: d_out_offsets receives n + 1 uint64; whether the layout fit out_cap is the summary's `overflow` (see inflate_batch_enqueue)."""
         self._check(self.L.zgpu_inflate_batch_packed_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, _WRAPS[wrap] if isinstance(wrap, str) else wrap, checks, align, d_out, out_cap,
                                                              d_out_offsets, d_items, d_summary, d_ws, ws_bytes, stream))
+
+    # ---- stream-ordered batch deflate ----
+    def deflate_batch_workspace_bytes(self, n, batch_items=0):
+        """Bytes of caller-owned device workspace a zgpu_deflate_batch_*_enqueue call needs for n items in rounds of batch_items (0: min(n, 4096))."""
+        return int(self.L.zgpu_deflate_batch_workspace_bytes(n, batch_items))
+
+    def deflate_batch_enqueue(self, d_in, in_bytes, d_in_offsets, n, level, d_out, out_cap, d_out_offsets, d_items, d_ws, ws_bytes, flags=F_FINAL, strategy=0, batch_items=0,
+                              d_summary=None, stream=None, lz_impl=LZ_AUTO, prime=0):
+        """Device pointers as ints.  Item k = d_in[io[k], io[k+1]) becomes a stream of its own in its range d_out[oo[k], oo[k+1]) (d_out_offsets: n + 1 uint64, read);
+        d_items: room for n DeflateBatchItem, d_ws: 256-byte aligned workspace, d_summary: room for a DeflateBatchSummary or None.  Enqueues on `stream` (an int;
+        None: the engine's) and returns: nothing is read back, the results are there when the stream gets there."""
+        p = _Params(level, 0, flags, lz_impl, strategy, prime)
+        self._check(self.L.zgpu_deflate_batch_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, C.byref(p), d_out, out_cap, d_out_offsets, d_items, d_summary, d_ws, ws_bytes,
+                                                      batch_items, stream))
+
+    def deflate_batch_packed_enqueue(self, d_in, in_bytes, d_in_offsets, n, level, d_out, out_cap, d_out_offsets, d_items, d_ws, ws_bytes, flags=F_FINAL, strategy=0, batch_items=0,
+                                     d_summary=None, stream=None, lz_impl=LZ_AUTO, prime=0):
+        """The same with the streams back to back in item order: d_out_offsets receives n + 1 uint64; whether they fit out_cap is the summary's `overflow`."""
+        p = _Params(level, 0, flags, lz_impl, strategy, prime)
+        self._check(self.L.zgpu_deflate_batch_packed_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, C.byref(p), d_out, out_cap, d_out_offsets, d_items, d_summary, d_ws,
+                                                             ws_bytes, batch_items, stream))
+
+    def set_exact_sort(self, on):
+        """on: the engine's calls sort with the ballot-ranked sort (what a caller does after a batch's summary said sort_fault); off: the fast sort again."""
+        self._check(self.L.zgpu_engine_set_exact_sort(self.h, 1 if on else 0))
 
     # ---- BGZF (blocked gzip) ----
     def bgzf_deflate_host(self, data, level=6, block_size=0, strategy=0, want_offsets=False):
