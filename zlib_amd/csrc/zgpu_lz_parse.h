@@ -85,7 +85,11 @@ __device__ inline uint32_t next_bit(const uint32_t *bits, uint32_t x, uint32_t n
     return (w << 5) + (uint32_t)__builtin_ctz(v);
 }
 
-#if defined(ZGPU_P2_TIME) && !defined(ZGPU_PARSE_HEADER_ONLY) // debug build only (scripts/p2_time.py): cycles per phase, summed over workgroups (lane 0's clock)
+#ifdef ZGPU_P2_TIME // debug build only (scripts/p2_time.py): cycles per phase, summed over workgroups (lane 0's clock)
+// (an includer of the header alone -- walk_kernel with its fused tail -- keeps an array and an accessor of its own and names the array in P2_TIME_ARR
+// before it includes the body: a __device__ variable belongs to one translation unit)
+#ifndef ZGPU_PARSE_HEADER_ONLY
+#define P2_TIME_ARR p2_time
 __device__ unsigned long long p2_time[8];
 extern "C" __attribute__((visibility("default"))) void zgpu_debug_p2_time(unsigned long long *out, int reset)
 {
@@ -93,10 +97,11 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_p2_time(unsign
     hipMemcpyFromSymbol(out, HIP_SYMBOL(p2_time), sizeof z);
     if (reset) hipMemcpyToSymbol(HIP_SYMBOL(p2_time), z, sizeof z);
 }
+#endif
 // (summed in registers and written once at the end: an atomic per phase would sit in the memory counter and be waited for by the next load)
 #define P2_T(i) do { if (tid == 0) { const unsigned long long t_ = wall_clock64(); t_acc[i] += t_ - t_prev; t_prev = t_; } } while (0)
 #define P2_T0() unsigned long long t_prev = wall_clock64(), t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define P2_TEND() do { if (tid == 0) for (int i_ = 0; i_ < 8; i_++) atomicAdd(&p2_time[i_], t_acc[i_]); } while (0)
+#define P2_TEND() do { if (tid == 0) for (int i_ = 0; i_ < 7; i_++) atomicAdd(&P2_TIME_ARR[i_], t_acc[i_]); } while (0)
 #else
 #define P2_T(i) do { } while (0)
 #define P2_T0() do { } while (0)

@@ -41,19 +41,37 @@
     // (the logs' positions are read two to a dword, and nothing is done to a loaded value before every load of its batch is out: a 16-bit load is
     // widened, and so waited for, where it stands)
     const uint32_t *lpos2 = reinterpret_cast<const uint32_t *>(lpos);
+    // The logs' loads depend on nothing the tail computes -- the counts are final when the walkers are done -- so none of them stands on the tail's
+    // critical path by itself: stage 1 issues the position loads of all windows before it waits (a load, a wait and the atomics per window were
+    // eight round trips in a row), and the entries of window w + 1 (nq, nv) are asked for in window w and taken over at the top of w + 1.
+    uint32_t nq[kP2Own], nv[kP2Own]; // LOG: the log entries of the next window (positions two to a dword, records)
+    auto log_fetch = [&](uint32_t w0n, uint32_t tid) { // (w0n < n, uniform; tid: the window's, see the loop)
+        const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[w0n / kP2Win]);
+        const uint32_t *lp2 = lpos2 + w0n / 2, *lr = lrec + w0n; // (w0n / kP2Win * kP2Win == w0n)
+#pragma unroll
+        for (uint32_t i = 0; i < kP2Own; i++) {
+            nq[i] = 0; nv[i] = 0;
+            if (i * kP2Threads < cw) { const uint32_t e = i * kP2Threads + tid; nq[i] = p2_ld<FUSED>(lp2 + (e >> 1)); nv[i] = p2_ld<FUSED>(lr + e); } // (e < kP2Win: inside the log, whatever the count)
+        }
+    };
     if (LOG) { // a bit per logged game start: the logs' positions, read once and densely
         constexpr uint32_t kRounds = kP2Win / 2 / kP2Threads;
         __syncthreads();
-        for (uint32_t w = 0; w < kP2Wins; w++) {
-            const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[w]); // (uniform: the rounds are cut off by scalar branches)
-            uint32_t pv[kRounds];
+        log_fetch(0, tid); // (behind the position loads of stage 1 in the queue; taken over at the top of window 0)
+        uint32_t pv[kP2Wins][kRounds], cw[kP2Wins];
 #pragma unroll
-            for (uint32_t r = 0; r < kRounds; r++) { pv[r] = 0; if (r * kP2Threads * 2 < cw) pv[r] = p2_ld<FUSED>(lpos2 + w * (kP2Win / 2) + r * kP2Threads + tid); }
+        for (uint32_t a = 0; a < kP2Wins; a++) {
+            cw[a] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[a]); // (uniform: the rounds are cut off by scalar branches)
+#pragma unroll
+            for (uint32_t r = 0; r < kRounds; r++) { pv[a][r] = 0; if (r * kP2Threads * 2 < cw[a]) pv[a][r] = p2_ld<FUSED>(lpos2 + a * (kP2Win / 2) + r * kP2Threads + tid); }
+        }
+#pragma unroll
+        for (uint32_t a = 0; a < kP2Wins; a++) {
 #pragma unroll
             for (uint32_t r = 0; r < kRounds; r++) {
-                const uint32_t e = (r * kP2Threads + tid) * 2, p0 = pv[r] & 0xffffu, p1 = pv[r] >> 16;
-                if (e < cw) atomicOr(&HAS[p0 >> 5], 1u << (p0 & 31u));
-                if (e + 1 < cw) atomicOr(&HAS[p1 >> 5], 1u << (p1 & 31u));
+                const uint32_t e = (r * kP2Threads + tid) * 2, p0 = pv[a][r] & 0xffffu, p1 = pv[a][r] >> 16;
+                if (e < cw[a]) atomicOr(&HAS[p0 >> 5], 1u << (p0 & 31u));
+                if (e + 1 < cw[a]) atomicOr(&HAS[p1 >> 5], 1u << (p1 & 31u));
             }
         }
     }
@@ -87,39 +105,48 @@
 
     // ---- 2. window by window: path, matches, token indices, tokens ----
     const uint32_t w_first = TILE ? t_e / kP2Win * kP2Win : 0u, w_lim = TILE ? (t_h1 + kTileSlack < n ? t_h1 + kTileSlack : n) : n;
+    const uint32_t tid_all = tid;
     for (uint32_t w0 = w_first; w0 < w_lim; w0 += kP2Win) {
         const uint32_t wend = w0 + kP2Win;
+        // LOG: the lane's number is opaque inside a window.  Everything a window derives from it alone -- the offsets of its sixteen log entries and of its
+        // sixteen bytes, the shuffles' lanes -- the compiler otherwise computes once in front of the loop and keeps: forty registers that the loads in
+        // flight across the window's stages need (it spilled instead).  They are a few instructions a window to compute again.
+        uint32_t tid = tid_all;
+        if (LOG) asm volatile("" : "+v"(tid));
         const uint32_t entry = sh_entry;
         uint32_t gm[kP2Own]; // the game of this lane's has-positions: (m - p) << 24 | len << 15 | dist; 0: none
-        uint32_t gp[kP2Own]; // LOG: where the game gm[i] starts (otherwise a lane's positions follow from i)
+        uint32_t gp[kP2Own / 2]; // LOG: where the game gm[i] starts, two to a register (otherwise a lane's positions follow from i)
         uint32_t onp = 0;    // bit i: gm[i] is a game on the path (stage B)
 #pragma unroll
-        for (uint32_t i = 0; i < kP2Own; i++) { gm[i] = 0; gp[i] = 0; }
-        auto pos_of = [&](uint32_t i) { return LOG ? gp[i] : w0 + i * kP2Threads + tid; };
-        if (entry != kNone && entry < wend) { // (uniform) the path has nodes in this window
+        for (uint32_t i = 0; i < kP2Own; i++) { gm[i] = 0; gp[i >> 1] = 0; }
+        auto pos_of = [&](uint32_t i) { return LOG ? (gp[i >> 1] >> ((i & 1u) << 4)) & 0xffffu : w0 + i * kP2Threads + tid; };
+        // LOG: what this window takes from memory besides its log -- the bytes of its positions, for stage D's literals (lane = position, as D stores) --
+        // and the next window's log are asked for as soon as this window's log has left nq / nv (stage A1), in front of every barrier of the window.
+        // D then only selects and stores.
+        uint32_t litw[kP2Own];
+        auto win_fetch = [&]() {
+#pragma unroll
+            for (uint32_t i = 0; i < kP2Own; i++) { const uint32_t p = w0 + i * kP2Threads + tid; litw[i] = 0; if (p < n) litw[i] = src[p]; }
+            if (wend < n) log_fetch(wend, tid);
+        };
+        const bool has_path = entry != kNone && entry < wend; // (uniform) the path has nodes in this window
+        if (has_path) {
             // A1. successors of all has-positions of the window.  A lane's game reads the records of the positions right behind
             // its own: those are its neighbours' records (lanes = consecutive positions), fetched with lane shuffles; the first
             // kP2Over positions behind the wave's 64 are loaded by lanes 0..kP2Over-1 as well.  (A dependent global load per step of
             // the game -- some lane of the wave always needs one -- was 45% of this kernel.)
             if (LOG) {
-                // the window's log entries are shared out, entry e to lane e % kP2Threads: the loads of all of a lane's entries are in flight
-                // together (the rounds are cut off by the count, which is uniform), and nothing but the games is looked at -- J and END are
-                // written, and later read, at game starts only
+                // the window's log entries are shared out, entry e to lane e % kP2Threads (log_fetch, a window ago: nq, nv; zero from the count on),
+                // and nothing but the games is looked at -- J and END are written, and later read, at game starts only
                 const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[w0 / kP2Win]);
-                const uint32_t *lp2 = lpos2 + w0 / 2, *lr = lrec + w0; // (w0 / kP2Win * kP2Win == w0)
-                uint32_t gv[kP2Own], gq[kP2Own];
-#pragma unroll
-                for (uint32_t i = 0; i < kP2Own; i++) {
-                    gv[i] = 0; gq[i] = 0;
-                    if (i * kP2Threads < cw) { const uint32_t e = i * kP2Threads + tid; gq[i] = p2_ld<FUSED>(lp2 + (e >> 1)); gv[i] = p2_ld<FUSED>(lr + e); } // (e < kP2Win: inside the log, whatever the count)
-                }
 #pragma unroll
                 for (uint32_t i = 0; i < kP2Own; i++) {
                     const bool v = i * kP2Threads + tid < cw;
-                    const uint32_t p = (gq[i] >> ((tid & 1u) << 4)) & 0xffffu; // (kP2Threads is even: entry e's half is lane's)
-                    gm[i] = v ? gv[i] : 0u; gp[i] = v ? p : 0u;
+                    const uint32_t p = (nq[i] >> ((tid & 1u) << 4)) & 0xffffu; // (kP2Threads is even: entry e's half is lane's)
+                    const uint32_t gvi = nv[i];
+                    gm[i] = v ? gvi : 0u; gp[i >> 1] |= (v ? p : 0u) << ((i & 1u) << 4);
                     if (v) {
-                        const uint32_t end = p + (gv[i] >> 24) + ((gv[i] >> 15) & 511u), t = next_bit(HAS, end, nwords);
+                        const uint32_t end = p + (gvi >> 24) + ((gvi >> 15) & 511u), t = next_bit(HAS, end, nwords);
                         J[p - w0] = (uint16_t)(t < wend ? t - w0 : 0xffffu);
                         END[p - w0] = (uint16_t)(end - w0);
                     }
@@ -197,6 +224,10 @@
                 }
             }
             }
+        }
+        if (LOG) win_fetch(); // (ONE place for all of a window's loads, whether the path passes the window by or not: asked for in two branches, the registers
+                              // they arrive in were merged by copies behind the branches, and a copy waits for its load)
+        if (has_path) {
             __syncthreads();
             P2_T(1);
             // A2. The path through the window, without walking it end to end: parses started at different positions fall into
@@ -367,10 +398,16 @@
         }
         P2_T(4);
         // D. tokens of the window
+        // LOG: a batch's token indices first, then its stores in one run, each a 32-bit offset from `tok`, and the loaded bytes and the indices are
+        // pinned in front of the run (an empty asm that uses them: the compiler otherwise moves whatever a store alone needs under that store's
+        // condition).  A byte that is first used under a lane's own condition is waited for under that condition, and again under the next one, since
+        // the wave may have skipped the first -- s_waitcnt vmcnt(0) in front of every store, which waits for the store before it as well: sixteen
+        // literal stores a lane and window, each acknowledged before the next was issued.
+        auto tok_put = [&](uint32_t idx, uint32_t v) { *reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(tok) + (idx << 2)) = v; }; // (idx < kChunkMax)
         if (def_m != kNone) { tok[index_of(def_m)] = def_tok; def_m = kNone; }
 #pragma unroll
         for (uint32_t ib = 0; ib < kP2Own; ib += kP2Batch) {
-            uint32_t lit[kP2Batch];
+            uint32_t lit[kP2Batch], ix[kP2Batch];
             bool li[kP2Batch];
 #pragma unroll
             for (uint32_t u = 0; u < kP2Batch; u++) {
@@ -380,12 +417,19 @@
                 // (every position's byte is asked for, literal or not: eight loads in flight instead of eight waits one after the other.  Round 2 kept
                 // conditional loads in the all-position form because "the toolchain produced wrong tokens the other way": that was stage B's miscompiled
                 // `else gm[i] = 0`, see there)
-                if (p < n) lit[u] = src[p];
+                if (LOG) lit[u] = litw[ib + u];
+                else if (p < n) lit[u] = src[p];
+                ix[u] = LOG ? index_of(p) : 0u; // (p < kChunkMax: a word of the arrays, token or not)
+            }
+            if (LOG) {
+#pragma unroll
+                for (uint32_t u = 0; u < kP2Batch; u++) asm volatile("" : "+v"(lit[u]), "+v"(ix[u]));
             }
 #pragma unroll
             for (uint32_t u = 0; u < kP2Batch; u++) {
                 const uint32_t p = w0 + (ib + u) * kP2Threads + tid;
-                if (li[u]) tok[index_of(p)] = tok_lit(lit[u]);
+                if (LOG) { if (li[u]) tok_put(ix[u], tok_lit(lit[u])); }
+                else if (li[u]) tok[index_of(p)] = tok_lit(lit[u]);
                 const uint32_t gv = (!LOG && ((onp >> (ib + u)) & 1u)) ? gm[ib + u] : 0u;
                 if (gv) {
                     const uint32_t m = p + (gv >> 24), t = tok_match(gv & 32767u, ((gv >> 15) & 511u) - kMinMatch);
@@ -396,13 +440,20 @@
         if (LOG) { // the match tokens, by game.  A lane's games lie anywhere in the window, but a game on the path whose match starts at or behind wend
                    // is the path's last in this window (the next node lies behind the match): one per window, so one deferred token per lane is enough
 #pragma unroll
-            for (uint32_t i = 0; i < kP2Own; i++) {
-                const uint32_t gv = ((onp >> i) & 1u) ? gm[i] : 0u;
-                if (gv) {
-                    const uint32_t m = gp[i] + (gv >> 24), t = tok_match(gv & 32767u, ((gv >> 15) & 511u) - kMinMatch);
-                    if (m < wend) tok[index_of(m)] = t; else { def_m = m; def_tok = t; }
+                for (uint32_t ib = 0; ib < kP2Own; ib += kP2Batch) {
+                    uint32_t mx[kP2Batch], mt[kP2Batch];
+#pragma unroll
+                    for (uint32_t u = 0; u < kP2Batch; u++) {
+                        const uint32_t gv = ((onp >> (ib + u)) & 1u) ? gm[ib + u] : 0u, m = pos_of(ib + u) + (gv >> 24);
+                        mt[u] = gv ? tok_match(gv & 32767u, ((gv >> 15) & 511u) - kMinMatch) : 0u;
+                        mx[u] = kNone;
+                        if (gv) { if (m < wend) mx[u] = index_of(m); else { def_m = m; def_tok = mt[u]; } }
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < kP2Batch; u++) asm volatile("" : "+v"(mx[u]), "+v"(mt[u]));
+#pragma unroll
+                    for (uint32_t u = 0; u < kP2Batch; u++) if (mx[u] != kNone) tok_put(mx[u], mt[u]);
                 }
-            }
         }
         P2_T(5);
     }

@@ -845,6 +845,16 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
 #ifndef ZGPU_WBLK
 #define ZGPU_WBLK 64 // positions per block
 #endif
+// The end of a chunk (MODE 1): blocks go out in position order, so when the counter runs out every walker is somewhere inside one of the last blocks
+// and the lanes fall idle one by one for up to a block's time.  The last ZGPU_WTAPER32 positions of a chunk are therefore handed out in blocks of 32
+// and the last ZGPU_WTAPER16 in blocks of 16: what is in flight at the end is short, and a lane that finishes late finds a short block to take.
+// (Set both to 0 for uniform blocks.  A chunk with no more blocks than walkers keeps uniform blocks: there is nothing to balance.)
+#ifndef ZGPU_WTAPER32
+#define ZGPU_WTAPER32 16384
+#endif
+#ifndef ZGPU_WTAPER16
+#define ZGPU_WTAPER16 4096
+#endif
 #ifndef ZGPU_WNEU_SHIFT
 #define ZGPU_WNEU_SHIFT 0 // walkers meet at positions that are multiples of 1 << this (fewer bits in LDS, a little more duplicate work)
 #endif
@@ -854,19 +864,46 @@ __global__ void __launch_bounds__(kM2Threads, 8) match3_kernel(ChunkGeom g, Leve
 constexpr uint32_t kWFoldAt = ZGPU_WFOLD_AT;
 constexpr uint32_t kWThreads = 512, kWWaves = kWThreads / 64, kWBlk = ZGPU_WBLK, kWTrig = ZGPU_WTRIG, kWNeuShift = ZGPU_WNEU_SHIFT;
 constexpr uint32_t kWNeuBytes = (kChunkMax >> kWNeuShift) / 8;
+constexpr uint32_t kWTaper32 = ZGPU_WTAPER32, kWTaper16 = ZGPU_WTAPER16, kWTaperMin = kWThreads * kWBlk; // (chunks of at most kWTaperMin positions: uniform blocks)
+static_assert(kWTaper16 <= kWTaper32 && kWTaper32 <= kWTaperMin && kWTaper32 % 64 == 0 && kWTaper16 % 64 == 0, "the tapered end lies inside a chunk that has one");
+static_assert((kWTaper32 == 0 && kWTaper16 == 0) || kWBlk == 64, "blocks of 32 and 16 follow blocks of 64");
+static_assert(kWTaper32 == 0 || kWNeuShift <= (kWTaper16 ? 4 : 5), "a short block's start must be a meeting position of its own, or the walker in front passes through it and the block is never taken");
+// the block map of a chunk of n positions: blocks of kWBlk below b32, of 32 in [b32, b16), of 16 from b16 on (b32 a multiple of 64, b16 of 32)
+struct WalkTaper {
+    uint32_t b32, b16, n64, n32, nblk;
+    __host__ __device__ explicit WalkTaper(uint32_t n)
+    {
+        const bool on = n > kWTaperMin && kWTaper32 != 0;
+        b32 = on ? (n - kWTaper32) & ~63u : n;
+        b16 = on ? (n - kWTaper16) & ~31u : n;
+        n64 = on ? b32 / 64 : (n + kWBlk - 1) / kWBlk; n32 = (b16 - b32) / 32;
+        nblk = n64 + n32 + (n - b16 + 15) / 16;
+    }
+    __host__ __device__ uint32_t start(uint32_t b) const { return b < n64 ? b * kWBlk : b < n64 + n32 ? b32 + (b - n64) * 32 : b16 + (b - n64 - n32) * 16; }
+};
+extern "C" __attribute__((visibility("default"))) void zgpu_walk_block_map(uint32_t n, uint32_t *out) // (tests: where a chunk's walkers start) b32, b16, blocks
+{
+    const WalkTaper t(n);
+    out[0] = t.b32; out[1] = t.b16; out[2] = t.nblk;
+}
 constexpr uint32_t kWOffLcnt = kM3DataLds + 16 + kWNeuBytes + kWWaves * kM3WaveLds; // entries in each window's log (a chunk's walkers; they outlive them)
 constexpr uint32_t kWLds = kWOffLcnt + kP2Wins * 4;
 static_assert(2 * kWLds <= 160 * 1024, "two walker workgroups per CU");
 enum : uint32_t { W_NEED = 0, W_LIMBO = 1, W_READY = 2, W_SEARCH = 3, W_DONE = 4 };
-#ifdef ZGPU_WALK_STATS // debug build only: 0 bodies, 1 active lane-steps, 2 passes, 3 lanes served by passes, 4 searches, 5 folds, 6 parked, 7 limbo starts
-__device__ unsigned long long walk_stats[8];
+#ifdef ZGPU_WALK_STATS // debug build only: 0 bodies, 1 active lane-steps, 2 passes, 3 lanes served by passes, 4 searches, 5 folds, 6 parked, 7 limbo starts;
+                       // the end of a chunk (scripts/walk_stats.py): 8 / 9 live lanes (not W_DONE) summed over the passes before / after the wave has seen the
+                       // block counter run out, 10 / 11 the passes in each
+__device__ unsigned long long walk_stats[12];
 extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_stats(unsigned long long *out, int reset)
 {
-    unsigned long long z[8] = {};
+    unsigned long long z[12] = {};
     hipMemcpyFromSymbol(out, HIP_SYMBOL(walk_stats), sizeof z);
     if (reset) hipMemcpyToSymbol(HIP_SYMBOL(walk_stats), z, sizeof z);
 }
 #define W_STAT(i, v) do { const unsigned long long v_ = (unsigned long long)(v); if (lane == 0) atomicAdd(&walk_stats[i], v_); } while (0)
+#define W_SOUT0() bool ws_out = false
+#define W_SLIVE() do { W_STAT(ws_out ? 9 : 8, __popcll(__builtin_amdgcn_ballot_w64(st != W_DONE))); W_STAT(ws_out ? 11 : 10, 1); } while (0)
+#define W_SOUT() do { ws_out = ws_out || __builtin_amdgcn_ballot_w64(st == W_DONE) != 0; } while (0) // (W_DONE comes from an empty counter alone)
 __device__ unsigned long long walk_log_stats[2]; // walk_kernel<1> (scripts/walk_log_stats.py): 0 games logged, 1 the fullest log of a window
 extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_log_stats(unsigned long long *out, int reset)
 {
@@ -876,31 +913,51 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_log_stats
 }
 #else
 #define W_STAT(i, v) do { } while (0)
+#define W_SOUT0() do { } while (0)
+#define W_SLIVE() do { } while (0)
+#define W_SOUT() do { } while (0)
 #endif
 #ifdef ZGPU_WALK_TIME // debug build only (scripts/walk_time.py): clock cycles of a wave in 0 passes (rest), 1 bodies (without 2), 2 folds inside bodies, 3 setup, 4 drain folds, 5 parse + claims, 6 blocks
-__device__ unsigned long long walk_time[8];
+                      // and, over those (by when, not by what): 8 from the first pass that finds the block counter run out to the wave's exit from the
+                      // walker loop (the ramp-down), 9 from that exit to the release of the barrier in front of the tail
+__device__ unsigned long long walk_time[10];
 extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_time(unsigned long long *out, int reset)
 {
-    unsigned long long z[8] = {};
+    unsigned long long z[10] = {};
     hipMemcpyFromSymbol(out, HIP_SYMBOL(walk_time), sizeof z);
     if (reset) hipMemcpyToSymbol(HIP_SYMBOL(walk_time), z, sizeof z);
 }
 // (summed in registers, written once when the wave is done: an atomic per section would sit in the wave's memory counter and be waited for
 // by the next section that needs a load)
-#define W_T0() unsigned long long wt_prev = __builtin_readcyclecounter(), wt_fold = 0, wt_lds = 0, wt_take = 0, wt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define W_T0() unsigned long long wt_prev = __builtin_readcyclecounter(), wt_fold = 0, wt_lds = 0, wt_take = 0, wt_out = 0, wt_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
 #define W_T(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); wt_acc[i] += t_ - wt_prev - ((i) == 1 ? wt_fold + wt_lds + wt_take : 0); \
                     if ((i) == 1) { wt_acc[2] += wt_fold; wt_acc[3] += wt_lds; wt_acc[7] += wt_take; } wt_fold = wt_lds = wt_take = 0; wt_prev = t_; } while (0)
 #define W_TF(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); stmt; wt_fold += __builtin_readcyclecounter() - f0_; } while (0)
 #define W_TL(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); stmt; wt_lds += __builtin_readcyclecounter() - f0_; } while (0)   // the body's batch of byte reads (candidates' and scan string's)
 #define W_TK(stmt) do { const unsigned long long f0_ = __builtin_readcyclecounter(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stmt; wt_take += __builtin_readcyclecounter() - f0_; } while (0) // waiting for the groups a pass asked for
-#define W_TEND() do { if (lane == 0) for (int i_ = 0; i_ < 8; i_++) atomicAdd(&walk_time[i_], wt_acc[i_]); } while (0)
+#define W_TOUT() do { if (!wt_out && __builtin_amdgcn_ballot_w64(st == W_DONE)) wt_out = wt_prev; } while (0) // (behind W_T(6): the hand-out that came back empty)
+#define W_TEXIT() do { wt_acc[8] = wt_prev - wt_out; } while (0)                                                // (behind W_T(0); a wave leaves through an empty hand-out)
+#define W_TEND() do { wt_acc[9] = __builtin_readcyclecounter() - wt_prev; if (lane == 0) for (int i_ = 0; i_ < 10; i_++) atomicAdd(&walk_time[i_], wt_acc[i_]); } while (0)
 #else
 #define W_T0() do { } while (0)
 #define W_T(i) do { } while (0)
 #define W_TF(stmt) stmt
 #define W_TL(stmt) stmt
 #define W_TK(stmt) stmt
+#define W_TOUT() do { } while (0)
+#define W_TEXIT() do { } while (0)
 #define W_TEND() do { } while (0)
+#endif
+#ifdef ZGPU_P2_TIME // debug build only (scripts/p2_time.py fused): the clock of the parse (zgpu_lz_parse.h) for the tail behind a chunk's walkers -- 0 .. 6 its stages,
+                    // 7 the workgroup's time in front of it (staging, walkers, barrier), all lane 0's 100 MHz wall clock
+__device__ unsigned long long p2_fused_time[8];
+extern "C" __attribute__((visibility("default"))) void zgpu_debug_p2_fused_time(unsigned long long *out, int reset)
+{
+    unsigned long long z[8] = {};
+    hipMemcpyFromSymbol(out, HIP_SYMBOL(p2_fused_time), sizeof z);
+    if (reset) hipMemcpyToSymbol(HIP_SYMBOL(p2_fused_time), z, sizeof z);
+}
+#define P2_TIME_ARR p2_fused_time
 #endif
 // b + the high / low half of w, b | the high half of w: one instruction each (SDWA picks the half), b | (w & m)
 __device__ inline uint32_t add_w1(uint32_t b, uint32_t w) { uint32_t r; asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(r) : "v"(b), "v"(w)); return r; }
@@ -1039,6 +1096,9 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         if (tg.nil_pos >= wb && tg.nil_pos - wb < kChunkMax) nil_local = (uint32_t)(tg.nil_pos - wb);
     }
     const uint32_t npos = n >= 3 ? n - 2 : 0;
+#ifdef ZGPU_P2_TIME
+    const unsigned long long p2_t_in = wall_clock64();
+#endif
     stage_chunk<kWThreads>(src, n, d32, tid);
     for (uint32_t i = tid; i < kChunkMax / 32; i += kWThreads) { if (i < kWNeuBytes / 4) NEU[i] = 0; if (!FUSE) gs[i] = 0; }
     if (tid < 8) d32[(kChunkMax + 64) / 4 + tid] = 0xffffffffu; // the word the quick check reads where a zero word would look like a hit
@@ -1051,8 +1111,9 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         const int a = b0 - (int)kMinLookahead + 1, b = (int)(kWSize + kMaxDist) - (int)base;
         slide_at = a > b ? a : b;
     }
-    // blocks: TILE -- one per entry, then one per 64 positions of the rest of the range
-    const uint32_t chainF = cfg.chain, chainQ = cfg.chain >> 2, dbase = lds_off(d32), nblk = TILE ? tnent + (th1 - th0 - tnent + kWBlk - 1) / kWBlk : (n + kWBlk - 1) / kWBlk;
+    // blocks: TILE -- one per entry, then one per 64 positions of the rest of the range; a chunk -- WalkTaper
+    const WalkTaper taper(n);
+    const uint32_t chainF = cfg.chain, chainQ = cfg.chain >> 2, dbase = lds_off(d32), nblk = TILE ? tnent + (th1 - th0 - tnent + kWBlk - 1) / kWBlk : taper.nblk;
     const uint32_t wlim = TILE ? th1 : n; // a walker that arrives here, neutral, is done with the chunk / the tile
     const bool vexact = (chainF & 7u) != 0 || (chainQ & 7u) != 0 || cfg.strategy == kRle; // a chain may end inside a group of eight with entries of its own bucket behind it (see the bodies)
     // what a parked candidate carries besides its position: the owner's lane (bits 16-21), "first of its chain" (bit 22) and, from bit 23, the length of
@@ -1130,6 +1191,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     auto gload = [&](int gi) -> uint4 { gi = gi < -(int)kSPad ? -(int)kSPad : gi; return reinterpret_cast<const U128u *>(S + gi)->v; };
 
     W_T0();
+    W_SOUT0();
     W_T(3);
     for (;;) {
         // ================================================= pass: the parse for every lane whose search is over =================================================
@@ -1138,6 +1200,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         if (cont && (key_seen >> 31)) cont = false; // (the drain found a nice_match: no refill)
         const bool fin = st == W_SEARCH && !(((amask | jmask) >> lane) & 1ull) && !cont;
         W_STAT(2, 1); W_STAT(3, __popcll(__builtin_amdgcn_ballot_w64(fin || st == W_LIMBO || st == W_NEED)));
+        W_SLIVE();
         if (st == W_LIMBO) { irx = irl; st = W_READY; } // what the last pass asked for has arrived
         uint32_t y = 0, irY = 0, rec = 0;
         bool toN = false, haveIr = false, emit = false;
@@ -1211,7 +1274,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
                     const uint32_t b = b0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(nm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nm, 0));
                     if (b >= nblk) st = W_DONE;
                     else {
-                        const uint32_t y2 = TILE ? (b < tnent ? th0 + b : th0 + tnent + (b - tnent) * kWBlk) : b * kWBlk, bit = 1u << ((y2 >> kWNeuShift) & 31u);
+                        const uint32_t y2 = TILE ? (b < tnent ? th0 + b : th0 + tnent + (b - tnent) * kWBlk) : taper.start(b), bit = 1u << ((y2 >> kWNeuShift) & 31u);
                         if (!(atomicOr(&NEU[(y2 >> kWNeuShift) >> 5], bit) & bit)) { x = y2; handL = kMinMatch - 1; irl = y2 < npos ? ir[y2] : 0; st = W_LIMBO; }
                         // (else: a walker from further down passed through here; the next pass asks for another block)
                     }
@@ -1219,6 +1282,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             }
         }
         W_T(6);
+        W_TOUT(); W_SOUT();
         bool fresh = false;
         if (st == W_READY) { // start the search at x with the match in hand (length handL, 2: none) as the seed
             const uint32_t seed = handL, idx = irx & 0xffffu, rank = irx >> 16, budget = seed >= cfg.good ? (chainQ ? chainQ : 0xffffu) : chainF; // (a quarter of fewer than 4 never runs out, deflate.c:1163)
@@ -1253,7 +1317,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
             gi -= 32;
         }
         W_T(0);
-        if (__builtin_amdgcn_ballot_w64(st != W_DONE) == 0) { W_TEND(); break; }
+        if (__builtin_amdgcn_ballot_w64(st != W_DONE) == 0) { W_TEXIT(); break; }
         const unsigned long long smask = __builtin_amdgcn_ballot_w64(st == W_SEARCH);
         const uint32_t idle = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(st == W_LIMBO || st == W_NEED));
 
@@ -1375,10 +1439,15 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     }
     if (TILE) {
         __syncthreads(); // every walker of the tile is done: gm / gs are complete
+        W_TEND();
         tile_exits<kWThreads>(reinterpret_cast<uint8_t *>(lds), gm, gs, th0, th1, tnent_all, tg.exits + (size_t)c * kTileExitStride, tid);
     }
     if (FUSE) {
         __syncthreads(); // every walker of the chunk is done: the logs and their counts are complete (and written: the barrier waits for the stores)
+        W_TEND();
+#ifdef ZGPU_P2_TIME
+        if (tid == 0) atomicAdd(&p2_fused_time[7], wall_clock64() - p2_t_in);
+#endif
 #ifdef ZGPU_WALK_STATS
         if (tid < kP2Wins) { atomicAdd(&walk_log_stats[0], (unsigned long long)lcnt[tid]); atomicMax(&walk_log_stats[1], (unsigned long long)lcnt[tid]); }
 #endif
