@@ -1,7 +1,7 @@
 """The caller-owned workspace of the stream-ordered batch deflate calls (zlib_amd/csrc/zgpu_deflate_batch_plan.h) as a function of plain numbers.
 tests/tools/deflate_batch_plan_model.cpp includes the plan header and prints the layout; it is built for the host only, with the host sanitizers, makes
 no HIP call and is run as a program, never loaded into Python.  The expected sizes below are worked out from what the regions hold (zgpu_common.h,
-zgpu_lz_sorted.hip), not from a run.  Nothing is per item of the call.  Per item of a round, which is min(n, batch_items) items with batch_items == 0
+zgpu_lz_sorted.h), not from a run.  Nothing is per item of the call.  Per item of a round, which is min(n, batch_items) items with batch_items == 0
 standing for 4096: a uint64 for where its input begins, a uint64 for where it begins in the staging buffer (and one more, the round's end), a uint32 of
 state, 65536 bytes of staging buffer (256 more once), the sorted buckets' workspace -- S (65536 + 8) u16, the ranks 65536 u16, the head bits
 and heads_below (2048 + 512) u32, the records 65536 x 8 bytes, ir 65536 u32: 1,058,832 bytes, once more a header of 256 and a margin of 1024 --, 65536

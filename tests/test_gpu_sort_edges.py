@@ -1,4 +1,4 @@
-"""sort4_kernel (zgpu_lz_sorted.hip, K1c) keeps a lane's positions in registers through all its passes: turns of 512 positions handed round the
+"""sort4_kernel (zgpu_lz_sort.hip, K1c) keeps a lane's positions in registers through all its passes: turns of 512 positions handed round the
 sixteen waves, ranks and S indices of 16 bits beside a marker for "no position, or not in the chains", two 16-bit counts to an LDS word, S
 assembled in two halves.  Passes A and C0 have two forms of a turn: a straight one for a turn of which every position exists, has four bytes to
 load and is in the chains (whole_turn: no flush point in the chunk and 512 T + 515 <= n), and the general one for the rest.  These inputs sit on

@@ -1,4 +1,4 @@
-"""The end of a chunk in walk_kernel<1> (zgpu_lz_sorted.hip): the last positions of a chunk of more than 32768 are handed to the walkers in blocks
+"""The end of a chunk in walk_kernel<1> (zgpu_lz_walk.hip): the last positions of a chunk of more than 32768 are handed to the walkers in blocks
 of 32 and then of 16 positions instead of 64 (WalkTaper), and the fused tail behind the walkers reads the windows' logs.  These inputs sit where
 that geometry changes -- chunk lengths around the threshold and around the two boundaries, a partial last block, chunks of a few bytes; long
 matches laid across a boundary and across several short blocks -- and where the tail goes from one window to the next: logs that alternate between

@@ -1,4 +1,4 @@
-"""walk_kernel's fold and pass (zgpu_lz_sorted.hip): a parked candidate is compared with its owner's scan string, whose position and first eight
+"""walk_kernel's fold and pass (zgpu_lz_walk.hip): a parked candidate is compared with its owner's scan string, whose position and first eight
 bytes come out of the owner's registers; the scan string's two quick-check bytes are read with the candidates'; a pass issues its two LDS
 atomics together.  These inputs put matches on the seams of that code: lengths around the eight bytes held in registers, at every alignment of
 owner and candidate; matches cut by the end of the chunk; owners in the last lanes of a wave while a fold has one to three entries; a best

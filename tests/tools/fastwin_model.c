@@ -2,7 +2,7 @@
  * NOT part of the product; a tool to check the algorithm's exactness on the CPU and to count what it costs.
  *
  * One wave per chunk, 64 positions per window.  The chains of deflate_fast depend on the parse (positions inside a match longer than
- * max_insert_length are never inserted), so they are kept as: the positions counting-sorted by hash (S, idx, rank: what the sort of zgpu_lz_sorted.hip writes) plus
+ * max_insert_length are never inserted), so they are kept as: the positions counting-sorted by hash (S, idx, rank: what the sort of zgpu_lz_sort.hip writes) plus
  * ONE BIT per S index, "in the chains".  The predecessors of position p in its bucket are S[idx-1], S[idx-2], ...; the chain of p is those whose
  * bit is set, so the bits of the DEPTH nearest predecessors are DEPTH consecutive bits of the bitmap: one read, a few ctz.
  * Per window: all lanes evaluate longest_match at their own position under the bits as they stand -- final below the window, a guess (set)

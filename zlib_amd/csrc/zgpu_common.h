@@ -15,7 +15,7 @@ constexpr uint32_t kMinMatch = 3, kMaxMatch = 258, kMinLookahead = kMaxMatch + k
 constexpr uint32_t kMaxDist = kWSize - kMinLookahead; // 32506
 constexpr uint32_t kTooFar = 4096;
 constexpr uint32_t kChunkMax = 65536;
-// S, the chunk's positions counting-sorted by hash (written by zgpu_lz_sorted.hip's sorts, read there and by zgpu_lz_fastwin.hip): u16 entries,
+// S, the chunk's positions counting-sorted by hash (written by zgpu_lz_sort.hip's sorts, read by the searches -- zgpu_lz_match3.hip, zgpu_lz_walk.hip, zgpu_lz_fast.hip, zgpu_lz_fastwin.hip): u16 entries,
 // kSPad of them in front of every chunk's S (group loads may reach below index 0)
 constexpr uint32_t kSPad = 8, kSStride = kChunkMax + kSPad;
 constexpr uint32_t kBlockTokens = 16383;       // lit_bufsize-1: a block is cut after this many tokens

@@ -6,7 +6,7 @@
 //
 //   tile i   = the 64 KiB of input that start at 32512 * i: it parses its local positions [h0, h1) = [32512, 65024) with the 32512 bytes in front as
 //              history (MAX_DIST = 32506) and 512 bytes behind for the lazy game and the lookahead of its last positions (tests/tools/cont_tile_model.c
-//              is this decomposition on the CPU, byte-identical with the reference's loop).  sort4_kernel and walk_kernel<2> (zgpu_lz_sorted.hip) work
+//              is this decomposition on the CPU, byte-identical with the reference's loop).  sort4_kernel (zgpu_lz_sort.hip) and walk_kernel<2> (zgpu_lz_walk.hip) work
 //              on a tile as they work on a chunk; every quantity the reference keeps in window coordinates is a function of the absolute position here.
 //   chain 1  where the parse ENTERS each tile: a tile's walkers start from every possible entry (513 of them), tile_exits() turns their games into the
 //              tile's exit as a function of its entry, and the entries are the composition of those functions along the tiles: chain_*_kernel, groups of

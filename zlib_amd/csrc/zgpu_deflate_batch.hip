@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(256) dbatch_place_kernel(const uint8_t *__rest
     }
 }
 
-// ---- the call's last launch: the sort's self-check and the summary.  A raised fault word (sort4_kernel, zgpu_lz_sorted.hip: the LDS did not serve an
+// ---- the call's last launch: the sort's self-check and the summary.  A raised fault word (sort4_kernel, zgpu_lz_sort.hip: the LDS did not serve an
 // atomic's lanes in lane order) means that no stream of the call can be trusted: every record gets ZGPU_ERRNO.  The host cannot redo the call, it has
 // returned long ago; the caller sets the engine to the exact sort (zgpu_engine_set_exact_sort) and enqueues again ----
 __global__ void __launch_bounds__(256) dbatch_finish_kernel(const uint32_t *__restrict__ fault, uint64_t n, uint32_t packed, uint64_t out_cap, const unsigned long long *__restrict__ cnt,

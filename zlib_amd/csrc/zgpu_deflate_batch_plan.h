@@ -1,7 +1,7 @@
 // zgpu_deflate_batch_plan.h -- internal (not installed): the workspace of a stream-ordered batch deflate call (zgpu_deflate_batch_*_enqueue) as a function
 // of plain numbers.  The caller owns the workspace; a call carves it up as this header says and touches no device memory of the engine's.  Host only:
 // no HIP type, no include but <cstdint>, so that tests/tools/deflate_batch_plan_model.cpp prints the same layouts on a machine without a GPU.  What a
-// round's item costs is written out as numbers here; zgpu_lz_sorted.hip and zgpu_deflate_batch.hip assert that they are the structs and constants they
+// round's item costs is written out as numbers here; zgpu_lz_sorted.h and zgpu_deflate_batch.hip assert that they are the structs and constants they
 // stand for.
 #pragma once
 #include <cstdint>

@@ -125,7 +125,7 @@ inline int plan_auto_impl(const PlanCall &c, const PlanEngine &eng, const Deflat
 {
     const int auto_env = kn.lz_default; // ZGPU_LZ_DEFAULT=3: A/B runs of the all-position search
     int impl = (cfg.slow && eng.lz_parallel) ? ((walk_ok && auto_env != ZGPU_LZ_SORTED) ? ZGPU_LZ_WALK : ZGPU_LZ_SORTED) : ZGPU_LZ_SERIAL;
-    // levels 1-3: the head[]/prev[] loop.  deflate_fast on the sorted buckets (ZGPU_LZ_FAST, fast_kernel in zgpu_lz_sorted.hip) is a second
+    // levels 1-3: the head[]/prev[] loop.  deflate_fast on the sorted buckets (ZGPU_LZ_FAST, fast_kernel in zgpu_lz_fast.hip) is a second
     // implementation for the parity tests and for ZGPU_LZ_DEFAULT=5: it asks memory four times less often and is no faster
     if (!cfg.slow && eng.lz_parallel && walk_ok && !c.skip0 && auto_env == ZGPU_LZ_FAST) impl = ZGPU_LZ_FAST;
     // levels 1-3: a wave per chunk, window and chain bits in LDS (zgpu_lz_fastwin.hip) -- 5 ms a chunk whatever the size of the call, three chunks per

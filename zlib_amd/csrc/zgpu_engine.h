@@ -73,7 +73,7 @@ struct zgpu_engine {
     DevBuf<uint32_t> hand_list; // chunks the lane-per-chunk loop handed on: [0] their number, [1..] their indices in the batch
     int geo_w = 15, geo_m = 8;   // zgpu_deflate_set_geometry: deflateInit2's windowBits and memLevel
     DevBuf<uint8_t> geo_slots; DevBuf<uint4> geo_tables; DevBuf<uint32_t> geo_nostore; // the workspace of a non-default geometry (one group)
-    int exact_sort = 0;          // sticky: the fast sort's self-check failed once on this engine (zgpu_lz_sorted.hip, pass V)
+    int exact_sort = 0;          // sticky: the fast sort's self-check failed once on this engine (zgpu_lz_sort.hip, pass V)
     DevBuf<uint64_t> offsets;    // nchunks+1 segment offsets of the current call
     DevBuf<zgpu::RunState> run;  // one
     // staging for the *_host entry points (bytes)

@@ -3,7 +3,7 @@
 //
 // The chains of deflate_fast depend on the parse: the strings inside a match longer than max_insert_length never enter them
 // (deflate.c:1510-1534).  So neither head[]/prev[] filled ahead of the parse nor the static chains of levels 4-9 apply.  What IS known ahead of
-// the parse is which positions share a hash: the sort (zgpu_lz_sorted.hip) has counting-sorted the positions by hash (S; idx(p), rank(p) in `ir`), the bucket
+// the parse is which positions share a hash: the sort (zgpu_lz_sort.hip) has counting-sorted the positions by hash (S; idx(p), rank(p) in `ir`), the bucket
 // predecessors of p, nearest first, are S[idx-1], S[idx-2], ... S[idx-rank], and the chain of p is those of them that have been inserted.
 // "Inserted" is ONE BIT PER S INDEX, kept in LDS (8 KiB): the bits of p's 32 nearest predecessors are 32 consecutive bits -- one read, and
 // the first `max_chain_length` set ones are the chain.  The bytes the candidates are compared with come from a ring of the last 33 KiB of the

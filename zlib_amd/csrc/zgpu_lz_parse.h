@@ -1,4 +1,4 @@
-// zgpu_lz_parse.h -- K3, parallel form (device code; the kernel around it is in zgpu_lz_parse.hip, walk_kernel of zgpu_lz_sorted.hip
+// zgpu_lz_parse.h -- K3, parallel form (device code; the kernel around it is in zgpu_lz_parse.hip, walk_kernel of zgpu_lz_walk.hip
 // calls it as well): the deflate_slow control flow (/root/reference/qcsrc/deflate.c:1554-1674) over the
 // match records of a chunk, one 1024-lane workgroup per chunk, no serial walk over the positions.
 //
@@ -108,7 +108,7 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_p2_time(unsign
 #define P2_TEND() do { } while (0)
 #endif
 
-// LITE: the games have been played by walk_kernel (zgpu_lz_sorted.hip): gmv[r] holds the game of every position r a walker stood on
+// LITE: the games have been played by walk_kernel (zgpu_lz_walk.hip): gmv[r] holds the game of every position r a walker stood on
 // with nothing in hand and found a match at (bit r of gsv), in the format of gm[] below -- a subset of the has-positions that
 // contains the whole path, which is all that stages A2..D look at.
 template <bool FUSED> __device__ inline uint32_t p2_ld(const uint32_t *p) { return FUSED ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p; }

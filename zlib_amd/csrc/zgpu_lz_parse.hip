@@ -6,7 +6,7 @@
 
 namespace zgpu {
 
-// LITE: the games have been played by walk_kernel (zgpu_lz_sorted.hip): gmv[r] holds the game of every position r a walker stood on
+// LITE: the games have been played by walk_kernel (zgpu_lz_walk.hip): gmv[r] holds the game of every position r a walker stood on
 // with nothing in hand and found a match at (bit r of gsv), in the format of gm[] below -- a subset of the has-positions that
 // contains the whole path, which is all that stages A2..D look at.
 template <bool LITE, bool TILE>

@@ -1,6 +1,6 @@
 // zgpu_lz_parse_body.inc -- the body of the parallel parse (see zgpu_lz_parse.h for what it does), included where it runs:
 //   parse2_kernel (zgpu_lz_parse.hip)   a kernel of its own, the arrays below static __shared__
-//   walk_kernel   (zgpu_lz_sorted.hip)  behind its walkers, the arrays carved out of the LDS the chunk bytes lived in
+//   walk_kernel   (zgpu_lz_walk.hip)    behind its walkers, the arrays carved out of the LDS the chunk bytes lived in
 // The includer defines: the arrays J, HAS, MARK, COV, MAT, wbase, VIS, EXITS, wave_tot and the word sh_entry (LDS); g, c, cfg, recs,
 // gmv_all, gsv_all, tokens, meta; the compile-time constants LITE, FUSED, TILE, LOG, kP2Threads; the LDS word sh_exit and the TileGeom tg (used when TILE);
 // the chunk's logs lpos, lrec (global), their counts lcnt and the array END (LDS) -- used when LOG (zgpu_lz_parse.h), which implies LITE and not TILE.
