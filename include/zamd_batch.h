@@ -16,10 +16,14 @@ extern "C" {
 /* windowBits 15: each item becomes what compress2(item, level) gives; 31: a gzip member as deflateInit2(level, Z_DEFLATED, 31, 8,
  * Z_DEFAULT_STRATEGY) + deflate(Z_FINISH) gives it; -15: raw deflate the same way.  status[k]: Z_OK (destLen[k] = the stream's length) or
  * Z_BUF_ERROR when destLen[k] is too small (destLen[k] unchanged).  Items of at most 64 KiB at levels 1-9 are compressed together in one
- * launch of the engine (zgpu_deflate_segments_host); level 0 and larger items are served one by one through compress2() / deflateInit2(),
- * which handle any size. */
+ * launch of the engine (zgpu_deflate_segments_host).  Larger items at levels 4-9 are compressed together as well, many continuous streams whose
+ * tiles share the engine's launches (zgpu_deflate_streams_host; 256 items of 1 MiB at level 6: 54 ms against 364 ms one by one, from host buffers,
+ * profiles/r10_streams_table.txt), in calls of at most 1 GiB of input.  Level 0, larger items at levels 1-3 and
+ * items of 4 GiB or more are served one by one through compress2() / deflateInit2(), which handle any size.
+ * zamd_compress2_batch_count (diagnostic, since the library was loaded): 0 = zgpu_deflate_streams_host calls made, 1 = items served one by one. */
 int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int level,
                          int windowBits, int *status);
+unsigned long long zamd_compress2_batch_count(int which);
 
 /* windowBits 15 zlib, 31 gzip, 47 either (by the magic), -15 raw deflate.  status[k] as uncompress() (qcsrc/uncompr.c:50-56) gives it:
  * Z_OK (destLen[k] = the decoded size), Z_BUF_ERROR when destLen[k] is too small, Z_DATA_ERROR for a damaged or truncated stream and for one

@@ -300,6 +300,44 @@ int zgpu_deflate_batch_packed_enqueue(zgpu_engine *e, const void *d_in, uint64_t
                                       zgpu_deflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, uint32_t batch_items, void *hip_stream);
 int zgpu_engine_set_exact_sort(zgpu_engine *e, int on); /* on != 0: the engine's calls use the ballot-ranked sort, which needs no self-check; 0: the fast sort again */
 
+/* ---- batch deflate of items of ANY length: many continuous streams in one call (zlib_amd/csrc/zgpu_deflate_streams.hip) ----
+ * The segment and enqueue calls above stop at 65,536 bytes an item, because an item is one chunk there.  Here item k = in[in_offsets[k] .. in_offsets[k+1]), of any
+ * length from 0 to below 2^32, becomes exactly the bytes the reference's one-call stream gives for that item alone: compress2(level) with ZGPU_F_ZLIB_WRAP,
+ * deflateInit2(level, Z_DEFLATED, 31 or -15, 8, strategy) + deflate(Z_FINISH) with ZGPU_F_GZIP_WRAP or no wrapper -- what zgpu_deflate_device with
+ * ZGPU_F_CONTINUOUS gives one input.  Every stream is cut into tiles as a continuous stream is (zgpu_cont.hip), and the tiles of ALL items share the launches
+ * of the sort, the walkers, the chain of entries and the token parse, and so do the blocks of all streams of a batch in block construction: one launch each
+ * per batch of tiles, whatever the number of streams.  The scans around block construction (tokens -> blocks, bit positions, the bits into the room, the carry)
+ * are the continuous stream's own kernels, launched stream by stream of the batch, with no wait for the host in between.  Batches of tiles are
+ * sized by the device's memory or ZGPU_CONT_BATCH_TILES (read per call) over the tiles of all items laid end to end; they end wherever they end, also inside a stream.
+ *   zgpu_deflate_streams_bound   a room that always suffices for an item of item_bytes: zgpu_deflate_cont_bound plus the wrapper named in flags, rounded up to 4
+ *   zgpu_deflate_streams_layout  out_offsets[0..n] and *total (optional) from the sizes alone, rooms of zgpu_deflate_streams_bound each; host arithmetic, needs no
+ *                                engine and no GPU; ZGPU_STREAM_ERROR for a null table or one that runs backwards
+ *   zgpu_deflate_streams_device  the caller gives item k the room d_out[oo[k] .. oo[k+1]); every oo[k] is a multiple of 4 and d_out is 4-byte aligned (the
+ *                                stitch kernels work in 32-bit words and OR bits into place; the call clears what it must).  Bytes of a room behind its stream
+ *                                are unspecified; no byte outside the rooms is written.  d_in_offsets, d_out_offsets and d_items (n records, required) are device
+ *                                memory.  The call blocks until the result is known and reads its tables on the host.
+ *   zgpu_deflate_streams_host    lays the rooms out itself, packs the streams back to back on the device and copies them home once: out_offsets[0..n] as
+ *                                zgpu_deflate_segments_host writes them, items[k].out_lo = out_offsets[k].  in_offsets[0] is 0.  All streams together larger than
+ *                                out_cap: ZGPU_BUF_ERROR.
+ * Record k (zgpu_deflate_batch_item): code, out_lo, out_bytes (wrapper included), in_bytes, data_type, adler32, crc32 as the enqueue calls write them.  A stream
+ * that does not fit its room fails its item alone: code = ZGPU_BUF_ERROR, out_bytes = 0, nothing written outside its room; every other item is served as
+ * if it were not there, and the call returns ZGPU_OK.  res: out_bytes, ntokens and nchunks (= tiles) summed over the items, adler32 / crc32 / data_type of the
+ * last item, reserved = the number of records that are not ZGPU_OK.
+ * A table entry that runs backwards, leaves in_bytes / out_cap or (out_offsets) is no multiple of 4 fails the call with ZGPU_STREAM_ERROR before anything is launched.
+ * Served: ZGPU_F_FINAL (required), levels 4..9, all five strategies, at most one of ZGPU_F_ZLIB_WRAP / ZGPU_F_GZIP_WRAP, ZGPU_F_CRC32, zgpu_deflate_set_tuning as the
+ * continuous stream honours it.  Refused at once with ZGPU_STREAM_ERROR, the output untouched: levels 0..3 (the levels 1-3 tile path is a host-driven loop of
+ * rounds; those levels stay with one stream per call), a geometry other than windowBits 15 / memLevel 8, prime, ZGPU_F_POS0 / _POS0_ALL / _BGZF_WRAP /
+ * _CONTINUOUS, any lz_impl but ZGPU_LZ_AUTO, two wrappers, n >= 2^32.  The sort's self-check stays: a raised fault word makes the call redo itself with the exact sort.
+ * Rates (profiles/r10_streams_table.txt, level 6, zlib wrapper, device-resident), the one-by-one loop of continuous streams over this call: 7.1 for 256 items of
+ * 1 MiB (334 ms against 47), 11.7 for 4,096 items of 96 KiB (5.2 s against 0.45 s), 1.3 for 16 items of 64 MiB (80 ms against 60). */
+uint64_t zgpu_deflate_streams_bound(uint64_t item_bytes, uint32_t flags);
+int zgpu_deflate_streams_layout(const uint64_t *in_offsets, uint64_t n, uint32_t flags, uint64_t *out_offsets, uint64_t *total);
+int zgpu_deflate_streams_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, const zgpu_deflate_params *p,
+                                void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_deflate_batch_item *d_items, zgpu_deflate_result *res,
+                                void *hip_stream);
+int zgpu_deflate_streams_host(zgpu_engine *e, const void *in, const uint64_t *in_offsets, uint64_t n, const zgpu_deflate_params *p, void *out, uint64_t out_cap,
+                              uint64_t *out_offsets, zgpu_deflate_batch_item *items, zgpu_deflate_result *res);
+
 /* ---- BGZF: blocked gzip, the container of bgzip, BAM, tabix and .vcf.gz (RFC 1952 + SAM specification 4.1) ----
  * A file is gzip members laid end to end, each at most 64 KiB long and decoding to at most 64 KiB, each carrying its own total length in its header
  * (BSIZE in the 'B' 'C' extra subfield), closed by a fixed 28-byte empty block.

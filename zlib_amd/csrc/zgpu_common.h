@@ -94,10 +94,23 @@ struct ChunkMeta {
 
 // Where the chunks of one launch live.  Either uniform (chunk k = bytes [k*chunk_size, ...)) or an explicit
 // segment table (chunk k = bytes [seg_off[k], seg_off[k+1])), each segment at most 65536 bytes.
+// One tile of a launch whose tiles belong to MANY streams (zgpu_deflate_streams.hip; zgpu_deflate_streams_plan.h fills the rows): everything ChunkGeom's
+// and TileGeom's scalars say of a tile of the one stream.  The window is clipped at the tile's own stream's end, never at the buffer's.
+struct TileRow {
+    uint64_t lo;        // buffer offset of the tile's window
+    uint32_t n;         // bytes of the window: up to 65536, up to the stream's end
+    uint32_t h0, h1;    // the local positions the tile parses (a stream's first tile: from 0)
+    uint32_t nent;      // 1: a stream's first tile, entered at 0; else kTileEntries
+    uint32_t base;      // 0: the window starts at the stream's position 0, which is NIL; else 1
+    uint32_t nil_local; // local position whose first candidate, exactly MAX_DIST back, is NIL (cont_special_pos of the stream's end); ~0: none in this window
+};
 struct ChunkGeom {
     const uint8_t *in;
     uint64_t in_bytes;
-    const uint64_t *seg_off; // nullptr: uniform chunking
+    union {
+        const uint64_t *seg_off; // nullptr: uniform chunking
+        const TileRow *rows;     // with tile_stride != 0: the launch's tiles row by row (the kernels' ROWS instantiations); nullptr: the one stream's scalars
+    };
     uint64_t chunk0;         // global index of the first chunk of this batch
     uint64_t final_chunk;    // global index of the chunk that carries BFINAL (~0: none)
     uint32_t chunk_size;
@@ -122,8 +135,10 @@ struct ChunkGeom {
     const uint64_t *excl; uint32_t nexcl;
 };
 __device__ inline uint32_t chunk_of(const ChunkGeom &g, uint32_t c) { return g.chunk_map ? g.chunk_map[c] : c; }
-__device__ inline void chunk_span(const ChunkGeom &g, uint32_t c, uint64_t &lo, uint32_t &n)
+inline bool geom_rows(const ChunkGeom &g) { return g.tile_stride != 0 && g.rows != nullptr; }
+template <bool ROWS = false> __device__ inline void chunk_span(const ChunkGeom &g, uint32_t c, uint64_t &lo, uint32_t &n)
 {
+    if constexpr (ROWS) { lo = g.rows[c].lo; n = g.rows[c].n; return; }
     const uint64_t gc = g.chunk0 + chunk_of(g, c);
     if (g.tile_stride) { lo = g.tile_w0 + gc * g.tile_stride; const uint64_t rem = g.in_bytes - lo; n = (uint32_t)(rem < kChunkMax ? rem : kChunkMax); return; }
     if (g.seg_off) { lo = g.seg_off[gc]; n = (uint32_t)(g.seg_off[gc + 1] - lo); }
@@ -158,8 +173,10 @@ __device__ inline uint32_t excl_lower(const ChunkGeom &g, uint64_t at)
     return lo;
 }
 __device__ inline bool excl_has(const ChunkGeom &g, uint64_t at) { const uint32_t i = excl_lower(g, at); return i < g.nexcl && g.excl[i] == at; }
-__device__ inline void tile_span(const ChunkGeom &g, const TileGeom &tg, uint32_t c, uint64_t &wb, uint32_t &nloc, uint32_t &h0, uint32_t &h1, uint32_t &nent)
+template <bool ROWS = false>
+__host__ __device__ inline void tile_span(const ChunkGeom &g, const TileGeom &tg, uint32_t c, uint64_t &wb, uint32_t &nloc, uint32_t &h0, uint32_t &h1, uint32_t &nent)
 {
+    if constexpr (ROWS) { const TileRow r = g.rows[c]; wb = r.lo; nloc = r.n; h0 = r.h0; h1 = r.h1; nent = r.nent; return; }
     const uint64_t ti = g.chunk0 + c;
     wb = g.tile_w0 + ti * g.tile_stride;
     const uint64_t rem = g.in_bytes - wb, lim = tg.end > wb ? tg.end - wb : 0;

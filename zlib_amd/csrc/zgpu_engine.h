@@ -45,6 +45,7 @@ struct Carve {
 
 } // namespace zgpu
 
+namespace zgpu { struct StreamsBlkPart; }
 struct StageSpan { int stage; hipEvent_t a, b; };
 
 struct zgpu_engine {
@@ -92,6 +93,11 @@ struct zgpu_engine {
     uint32_t ct_tiles() const { return ct_tokoff.cap ? (uint32_t)(ct_tokoff.cap - 1) : 0; } // (ct_tokoff: a word per tile and one more)
     DevBuf<zgpu::ChunkMeta> ct_ckmeta;
     DevBuf<uint64_t> ct_excl;
+    // many streams in one call (zgpu_deflate_streams.hip): per call -- the tiles' rows and entries, a state and the checksums per item, the totals; per
+    // batch of tiles -- the token offsets (a word per tile and one more per stream); the host entry's tables, rooms' records and packed streams
+    DevBuf<zgpu::TileRow> ds_rows; DevBuf<uint16_t> ds_entry; DevBuf<zgpu::ContState> ds_st; DevBuf<zgpu_check_item> ds_check; DevBuf<unsigned long long> ds_totals;
+    DevBuf<uint32_t> ds_tokoff, ds_blk_item; DevBuf<zgpu::StreamsBlkPart> ds_parts; // (ds_parts: per call, the streams' parts of every batch)
+    DevBuf<uint64_t> ds_in_off, ds_oo, ds_po; DevBuf<zgpu_deflate_batch_item> ds_items; DevBuf<uint8_t> ds_packed;
     // ... levels 1-3: the rounds of fastwin_tile_kernel (the per-batch ones are one group)
     DevBuf<uint16_t> cf_exit_a, cf_exit_b; DevBuf<uint32_t> cf_ins0, cf_ins1, cf_prev, cf_prev2, cf_hist, cf_count;
     DevBuf<uint8_t> cf_cur, cf_act_a, cf_act_b, cf_changed, cf_kept; DevBuf<uint32_t> cf_list_a, cf_list_b, cf_used; DevBuf<uint16_t> cf_entry_used;
@@ -161,6 +167,8 @@ void launch_lz_serial(const ChunkGeom &g, LevelCfg cfg, uint4 *tables, uint32_t 
 // ---- zgpu_huffman.hip ----
 void launch_huffman(const ChunkGeom &g, const uint32_t *tokens, ChunkMeta *meta, uint8_t *slots, hipStream_t st, bool fixed_trees);
 void launch_huffman_cont(const ChunkGeom &g, const uint32_t *compact_tokens, uint32_t nblk, ContBlk *blk, ContState *cst, uint8_t *slots, hipStream_t st, bool fixed_trees);
+void launch_huffman_streams(const ChunkGeom &g, const uint32_t *batch_tokens, uint32_t nslots, ContBlk *blk, ContState *states, const uint32_t *blk_item, uint8_t *slots, hipStream_t st,
+                            bool fixed_trees);
 
 // ---- zgpu_stitch.hip ----
 void launch_collect_handed_on(const ChunkMeta *meta, uint32_t n, uint32_t *list, uint32_t *count, hipStream_t st);
@@ -221,6 +229,16 @@ void launch_cont_tokens(const ChunkGeom &g, const TileGeom &tg, const uint32_t *
                         ContBlk *blk, uint64_t seg_end, bool final_block, uint64_t sp, uint32_t nblk_cap, bool slow, hipStream_t s);
 void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const uint8_t *slots, uint32_t slot_stride, const uint8_t *in, uint64_t abs0, uint8_t *out, uint64_t out_cap,
                         uint32_t nblk_cap, const uint32_t *T, uint32_t *carry, uint64_t seg_end, hipStream_t s);
+
+// ---- zgpu_streams.hip ----
+void launch_streams_head(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out, uint16_t *entry0,
+                         unsigned long long *totals, hipStream_t s);
+void launch_streams_entry(const TileRow *rows, uint32_t ntiles, uint16_t *entry, hipStream_t s);
+struct StreamsBlkPart; // zgpu_deflate_streams_plan.h
+void launch_streams_blocks(const StreamsBlkPart *parts, uint32_t nparts, uint32_t nslots, const ContState *st, ContBlk *blk, uint32_t *blk_item, hipStream_t s);
+void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st, const zgpu_check_item *chk, bool want_crc,
+                           uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s);
+void launch_streams_pack(const uint8_t *rooms, const uint64_t *oo, const uint64_t *po, uint64_t n, uint64_t total, uint8_t *packed, hipStream_t s);
 
 // ---- zgpu_inflate.hip ----
 // One launch of the decoder, inflate_kernel_t: segments [chunk0, chunk0 + nchunks) of `offsets`, one workgroup each, records to status[0, nchunks).  The

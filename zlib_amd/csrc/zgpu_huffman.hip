@@ -521,10 +521,13 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_huf_time(unsig
 // CONT (continuous stream, zgpu_cont.hip): the workgroup codes ONE block -- blk[blockIdx.x], its tokens a run of the batch's compact token array -- into a
 // slot of its own from bit 0; where the block starts in the stream (a bit position that depends on every block in front of it) is the stitcher's business,
 // and so are the bytes of a stored block (copied from the input there); the block's size, type and last_eob_len go back into blk[].
-template <bool CONT>
+// MULTI (CONT only; zgpu_deflate_streams.hip): the launch covers the block slots of ALL streams of a batch -- blk_item[slot] is the stream (the index of its
+// ContState) a slot's block belongs to, ~0 for a slot that holds none; blk[slot].tok0 counts from the batch's token array.
+template <bool CONT, bool MULTI = false>
 __global__ void __launch_bounds__(kThreads, ZGPU_HUF_WAVES) huffman_kernel(ChunkGeom g, const uint32_t *__restrict__ tokens, ChunkMeta *meta, uint8_t *slots, uint32_t fixed_trees,
-                                                                            ContBlk *blk, ContState *cst)
+                                                                            ContBlk *blk, ContState *cst, const uint32_t *__restrict__ blk_item)
 {
+    static_assert(CONT || !MULTI, "many streams' blocks are continuous streams' blocks");
     __shared__ __attribute__((aligned(16))) TreeWork work0;
     __shared__ TreeWorkD work1;
     __shared__ uint32_t hist[kLCodes + kDCodes + 2];
@@ -542,7 +545,8 @@ __global__ void __launch_bounds__(kThreads, ZGPU_HUF_WAVES) huffman_kernel(Chunk
 
     const uint32_t c = blockIdx.x, tid = threadIdx.x;
     if (!CONT && c >= g.nchunks) return;
-    if (CONT && c >= cst->nblk) return; // (the launch is sized for the most blocks the batch can have)
+    if constexpr (MULTI) { const uint32_t item = blk_item[c]; if (item == 0xFFFFFFFFu) return; cst += item; } // (uniform: one slot per workgroup)
+    else if (CONT && c >= cst->nblk) return; // (the launch is sized for the most blocks the batch can have)
     uint64_t lo = 0; uint32_t nbytes = 0;
     if (!CONT) chunk_span(g, c, lo, nbytes);
     const uint8_t *src = g.in + lo;
@@ -761,12 +765,18 @@ __global__ void __launch_bounds__(kThreads, ZGPU_HUF_WAVES) huffman_kernel(Chunk
 
 void launch_huffman(const ChunkGeom &g, const uint32_t *tokens, ChunkMeta *meta, uint8_t *slots, hipStream_t st, bool fixed_trees)
 {
-    hipLaunchKernelGGL(huffman_kernel<false>, dim3(g.nchunks), dim3(kThreads), 0, st, g, tokens, meta, slots, fixed_trees ? 1u : 0u, nullptr, nullptr);
+    hipLaunchKernelGGL(huffman_kernel<false>, dim3(g.nchunks), dim3(kThreads), 0, st, g, tokens, meta, slots, fixed_trees ? 1u : 0u, nullptr, nullptr, nullptr);
 }
 // the blocks of a continuous stream's batch: g carries block_tokens and slot_stride only
 void launch_huffman_cont(const ChunkGeom &g, const uint32_t *compact_tokens, uint32_t nblk, ContBlk *blk, ContState *cst, uint8_t *slots, hipStream_t st, bool fixed_trees)
 {
-    if (nblk) hipLaunchKernelGGL(huffman_kernel<true>, dim3(nblk), dim3(kThreads), 0, st, g, compact_tokens, nullptr, slots, fixed_trees ? 1u : 0u, blk, cst);
+    if (nblk) hipLaunchKernelGGL(huffman_kernel<true>, dim3(nblk), dim3(kThreads), 0, st, g, compact_tokens, nullptr, slots, fixed_trees ? 1u : 0u, blk, cst, nullptr);
+}
+// the blocks of ALL streams of a batch of many streams' tiles in one launch: nslots block slots, states[blk_item[slot]] the stream of each
+void launch_huffman_streams(const ChunkGeom &g, const uint32_t *batch_tokens, uint32_t nslots, ContBlk *blk, ContState *states, const uint32_t *blk_item, uint8_t *slots, hipStream_t st,
+                            bool fixed_trees)
+{
+    if (nslots) hipLaunchKernelGGL((huffman_kernel<true, true>), dim3(nslots), dim3(kThreads), 0, st, g, batch_tokens, nullptr, slots, fixed_trees ? 1u : 0u, blk, states, blk_item);
 }
 
 } // namespace zgpu

@@ -9,7 +9,7 @@ namespace zgpu {
 // LITE: the games have been played by walk_kernel (zgpu_lz_walk.hip): gmv[r] holds the game of every position r a walker stood on
 // with nothing in hand and found a match at (bit r of gsv), in the format of gm[] below -- a subset of the has-positions that
 // contains the whole path, which is all that stages A2..D look at.
-template <bool LITE, bool TILE>
+template <bool LITE, bool TILE, bool ROWS>
 __global__ void __launch_bounds__(1024, 8) parse2_kernel(ChunkGeom g, LevelCfg cfg, const uint2 *__restrict__ recs, const uint32_t *__restrict__ gmv_all,
                                                          const uint32_t *__restrict__ gsv_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg)
 {
@@ -29,13 +29,14 @@ __global__ void __launch_bounds__(1024, 8) parse2_kernel(ChunkGeom g, LevelCfg c
 
 void launch_parse2(const ChunkGeom &g, LevelCfg cfg, const uint2 *recs, uint32_t *tokens, ChunkMeta *meta, hipStream_t st)
 {
-    hipLaunchKernelGGL((parse2_kernel<false, false>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, recs, nullptr, nullptr, tokens, meta, TileGeom{});
+    hipLaunchKernelGGL((parse2_kernel<false, false, false>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, recs, nullptr, nullptr, tokens, meta, TileGeom{});
 }
 
 // a tile of a continuous stream: the games walk_kernel<2> has played, the entry the chain over the tiles' exits has found (zgpu_cont.hip)
 void launch_parse_tile(const ChunkGeom &g, LevelCfg cfg, const uint32_t *gm, const uint32_t *gs, uint32_t *tokens, ChunkMeta *meta, const TileGeom &tg, hipStream_t st)
 {
-    hipLaunchKernelGGL((parse2_kernel<true, true>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, nullptr, gm, gs, tokens, meta, tg);
+    if (geom_rows(g)) hipLaunchKernelGGL((parse2_kernel<true, true, true>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, nullptr, gm, gs, tokens, meta, tg); // (many streams' tiles)
+    else hipLaunchKernelGGL((parse2_kernel<true, true, false>), dim3(g.nchunks), dim3(1024), 0, st, g, cfg, nullptr, gm, gs, tokens, meta, tg);
 }
 
 } // namespace zgpu

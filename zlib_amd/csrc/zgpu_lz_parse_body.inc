@@ -2,7 +2,7 @@
 //   parse2_kernel (zgpu_lz_parse.hip)   a kernel of its own, the arrays below static __shared__
 //   walk_kernel   (zgpu_lz_walk.hip)    behind its walkers, the arrays carved out of the LDS the chunk bytes lived in
 // The includer defines: the arrays J, HAS, MARK, COV, MAT, wbase, VIS, EXITS, wave_tot and the word sh_entry (LDS); g, c, cfg, recs,
-// gmv_all, gsv_all, tokens, meta; the compile-time constants LITE, FUSED, TILE, LOG, kP2Threads; the LDS word sh_exit and the TileGeom tg (used when TILE);
+// gmv_all, gsv_all, tokens, meta; the compile-time constants LITE, FUSED, TILE, ROWS (the tiles come row by row, TileRow), LOG, kP2Threads; the LDS word sh_exit and the TileGeom tg (used when TILE);
 // the chunk's logs lpos, lrec (global), their counts lcnt and the array END (LDS) -- used when LOG (zgpu_lz_parse.h), which implies LITE and not TILE.
 // TILE (continuous stream, zgpu_cont.hip): the chunk is a tile's 64 KiB; the path starts at the tile's entry (tg.entry, found by the chain over the tiles'
 // exit functions), the tokens are the positions from the entry to the end of the last game that starts below h1 (at most 512 behind it), and the block
@@ -12,7 +12,7 @@
     static_assert(kP2Own % kP2Batch == 0 && kP2Threads >= kP2Win / 32 && kP2Threads / 64 <= 16, "workgroup size");
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t lo; uint32_t n;
-    chunk_span(g, c, lo, n);
+    chunk_span<ROWS>(g, c, lo, n);
     ParseCtx cx;
     cx.rec = LITE ? nullptr : recs + (size_t)c * kChunkMax;
     const uint32_t *gmv = LITE ? gmv_all + (size_t)c * kChunkMax : nullptr, *gsv = LITE ? gsv_all + (size_t)c * kP2Words : nullptr;
@@ -30,7 +30,7 @@
     uint32_t t_h1 = n, t_e = 0; // TILE: the end of the tile's range, the entry (local positions)
     if (TILE) {
         uint64_t wb_; uint32_t nl_, h0_, ne_;
-        tile_span(g, tg, c, wb_, nl_, h0_, t_h1, ne_);
+        tile_span<ROWS>(g, tg, c, wb_, nl_, h0_, t_h1, ne_);
         t_e = h0_ + tg.entry[g.chunk0 + c];
     }
 

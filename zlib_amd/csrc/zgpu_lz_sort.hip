@@ -47,6 +47,7 @@ __global__ void __launch_bounds__(1024) heads_below_kernel(uint32_t *__restrict_
 #endif
 constexpr uint32_t kSortWaves = ZGPU_SORT_WAVES, kSortThreads = 64 * kSortWaves; // waves per chunk: 4 or 8 (or 16)
 
+template <bool ROWS>
 __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_t *__restrict__ S_all, uint16_t *__restrict__ rank_all, uint32_t *__restrict__ heads_all,
                                                             uint32_t *__restrict__ ir_all)
 {
@@ -57,7 +58,7 @@ __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_
     __shared__ uint32_t wave_tot[kSortWaves];
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t lo; uint32_t n;
-    chunk_span(g, c, lo, n);
+    chunk_span<ROWS>(g, c, lo, n);
     const uint8_t *src = g.in + lo;
     uint16_t *S = S_all + (size_t)c * kSStride + kSPad, *rk = rank_all + (size_t)c * kChunkMax;
     uint32_t *hd = heads_all + (size_t)c * kHeadStride, *ir = ir_all + (size_t)c * kChunkMax;
@@ -237,6 +238,7 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_sort_time(unsi
 #define S_TEND() do { } while (0)
 #endif
 
+template <bool ROWS> // (ROWS: the tiles of many streams, row by row -- TileRow)
 __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t *__restrict__ S_all, uint32_t *__restrict__ heads_all, uint32_t *__restrict__ fault,
                                                            uint32_t *__restrict__ ir_all, ChunkMeta *__restrict__ meta)
 {
@@ -249,7 +251,7 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     S_T0();
     uint64_t lo; uint32_t n;
-    chunk_span(g, c, lo, n);
+    chunk_span<ROWS>(g, c, lo, n);
     const uint8_t *src = g.in + lo;
     uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
     uint32_t *hd = heads_all + (size_t)c * kHeadStride, *ir = ir_all + (size_t)c * kChunkMax;
@@ -463,10 +465,12 @@ bool launch_sort(const ChunkGeom &g, const SortedWs &ws, ChunkMeta *meta, hipStr
     hipEvent_t ev{};
     prof_span_begin(prof, st, &ev);
     if (exact) {
-        hipLaunchKernelGGL(sort_kernel, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, ws.S, ws.rk, ws.heads, ws.ir);
+        if (geom_rows(g)) hipLaunchKernelGGL(sort_kernel<true>, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, ws.S, ws.rk, ws.heads, ws.ir);
+        else hipLaunchKernelGGL(sort_kernel<false>, dim3(g.nchunks), dim3(kSortThreads), 0, st, g, ws.S, ws.rk, ws.heads, ws.ir);
         hipLaunchKernelGGL(heads_below_kernel, dim3(g.nchunks), dim3(1024), 0, st, ws.heads);
     } else {
-        hipLaunchKernelGGL(sort4_kernel, dim3(g.nchunks), dim3(kS4Threads), 0, st, g, ws.S, ws.heads, ws.fault, ws.ir, meta);
+        if (geom_rows(g)) hipLaunchKernelGGL(sort4_kernel<true>, dim3(g.nchunks), dim3(kS4Threads), 0, st, g, ws.S, ws.heads, ws.fault, ws.ir, meta);
+        else hipLaunchKernelGGL(sort4_kernel<false>, dim3(g.nchunks), dim3(kS4Threads), 0, st, g, ws.S, ws.heads, ws.fault, ws.ir, meta);
         if (g_inject_sort_fault.exchange(0)) hipMemsetAsync(ws.fault, 1, 4, st); // zgpu_debug_inject_sort_fault(): exercise the engine's fallback without a real fault
     }
     prof_span_end(prof, st, ZGPU_STAGE_CHAIN, ev);

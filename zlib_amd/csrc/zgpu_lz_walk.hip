@@ -168,7 +168,7 @@ __device__ inline uint32_t sel_mask(unsigned long long m, uint32_t if_set, uint3
 // successor of each is looked up, and pointer jumping (N[i] = N[N[i]], in place) takes every start to the exit of its path in log2(depth) rounds: no serial
 // walk through the tile.  exits[k] = (neutral position the parse entered at h0 + k ends in) - h1, 0 .. 512.  T lanes, LDS from `pl` (the chunk bytes are dead).
 template <uint32_t T>
-__device__ inline void tile_exits(uint8_t *pl, const uint32_t *gm, const uint32_t *gs, uint32_t h0, uint32_t h1, uint32_t nent, uint16_t *exits, uint32_t tid)
+__device__ __forceinline__ void tile_exits(uint8_t *pl, const uint32_t *gm, const uint32_t *gs, uint32_t h0, uint32_t h1, uint32_t nent, uint16_t *exits, uint32_t tid)
 {
     constexpr uint32_t kWords = kChunkMax / 32;
     static_assert(kWords % T == 0 && T % 64 == 0 && T <= 1024, "workgroup size");
@@ -257,6 +257,7 @@ __device__ inline void tile_exits(uint8_t *pl, const uint32_t *gm, const uint32_
 // Once the walkers are done the neutral bitmap and the waves' rings and slots are dead as well: the parse's arrays lie over all of the workgroup's LDS
 // but the logs' counts -- J .. sh_entry in the first kP2LdsBytes, END behind them.
 static_assert(kP2LogLdsBytes <= kWOffLcnt, "the parse works in the memory of the chunk bytes, the neutral bitmap and the rings");
+// MODE 3: MODE 2 with the launch's tiles given row by row (TileRow), each tile a tile of its own stream.
 // MODE 1: a chunk, the rest of the parse behind its walkers (FUSE); 2: a TILE of a continuous stream (zgpu_cont.hip) -- walkers start at every possible
 // entry of the tile and at every 64th position of its range [h0, h1), stop at h1, and the workgroup ends with the tile's exit as a function of its entry.
 template <int MODE>
@@ -264,8 +265,8 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
                                                             uint32_t *__restrict__ gm_all, uint32_t *__restrict__ gs_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg)
 {
     // (gm_all, gs_all: MODE 2 -- the games by position and their bitmaps; MODE 1 -- the logs' records, lrec, and positions, lpos)
-    static_assert(MODE == 1 || MODE == 2, "a chunk or a tile");
-    constexpr bool FUSE = MODE == 1, TILE = MODE == 2;
+    static_assert(MODE == 1 || MODE == 2 || MODE == 3, "a chunk, a tile, a tile of a launch over many streams");
+    constexpr bool FUSE = MODE == 1, TILE = MODE >= 2, ROWS = MODE == 3;
     static_assert(!FUSE || kWNeuShift == 0, "a log holds kP2Win games: a position must start one game at most, so every neutral position is claimed");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t *d32 = lds;
@@ -275,7 +276,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t ring = (uint32_t)__builtin_amdgcn_readfirstlane(lds_off(lds) + kM3DataLds + 16 + kWNeuBytes + wave * kM3WaveLds), slot = ring + kRing * 4;
     uint64_t lo; uint32_t n;
-    chunk_span(g, c, lo, n);
+    chunk_span<ROWS>(g, c, lo, n);
     const uint8_t *src = g.in + lo;
     const uint16_t *S = S_all + (size_t)c * kSStride + kSPad;
     const uint32_t *ir = ir_all + (size_t)c * kChunkMax;
@@ -285,11 +286,14 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     uint32_t base = chunk_base(g, c);
     if (TILE) {
         uint64_t wb; uint32_t nl;
-        tile_span(g, tg, c, wb, nl, th0, th1, tnent);
+        tile_span<ROWS>(g, tg, c, wb, nl, th0, th1, tnent);
         tnent_all = tnent;
         if (tnent > th1 - th0) tnent = th1 - th0; // (walkers start inside the range only; an entry at or behind h1 passes the tile by)
+        if constexpr (ROWS) { base = g.rows[c].base; nil_local = g.rows[c].nil_local; } // (the tile's own stream's, zgpu_deflate_streams_plan.h)
+        else {
         base = (tg.abs0_nil && tg.abs0 + wb == 0) ? 0u : 1u; // only the stream's own position 0 is NIL; a tile's local 0 is out of every parsed position's reach
         if (tg.nil_pos >= wb && tg.nil_pos - wb < kChunkMax) nil_local = (uint32_t)(tg.nil_pos - wb);
+        }
     }
     const uint32_t npos = n >= 3 ? n - 2 : 0;
 #ifdef ZGPU_P2_TIME
@@ -637,6 +641,12 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         __syncthreads(); // every walker of the tile is done: gm / gs are complete
         W_TEND();
         tile_exits<kWThreads>(reinterpret_cast<uint8_t *>(lds), gm, gs, th0, th1, tnent_all, tg.exits + (size_t)c * kTileExitStride, tid);
+        if (ROWS && tnent_all == 1) { // a stream's first tile is entered at 0 whatever the tile in front of it in the launch did: its exit is a constant, and the chain over the launch's tiles (zgpu_cont.hip) restarts here
+            __syncthreads();
+            uint16_t *ex = tg.exits + (size_t)c * kTileExitStride;
+            const uint16_t v = __hip_atomic_load(ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (uint32_t k = 1 + tid; k < kTileEntries; k += kWThreads) ex[k] = v;
+        }
     }
     if (FUSE) {
         __syncthreads(); // every walker of the chunk is done: the logs and their counts are complete (and written: the barrier waits for the stores)
@@ -648,7 +658,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
         if (tid < kP2Wins) { atomicAdd(&walk_log_stats[0], (unsigned long long)lcnt[tid]); atomicMax(&walk_log_stats[1], (unsigned long long)lcnt[tid]); }
 #endif
         constexpr uint32_t kP2Threads = kWThreads;
-        constexpr bool LITE = true, FUSED = true, TILE = false, LOG = true;
+        constexpr bool LITE = true, FUSED = true, TILE = false, ROWS = false, LOG = true;
         const uint2 *recs = nullptr;
         const uint32_t *gmv_all = nullptr, *gsv_all = nullptr; // (the position-indexed form: tiles only)
         uint8_t *pl = reinterpret_cast<uint8_t *>(lds);
@@ -672,7 +682,8 @@ template <int MODE> static void launch_walk(const ChunkGeom &g, LevelCfg cfg, co
 void launch_walk_chunks(const ChunkGeom &g, LevelCfg cfg, const SortedWs &ws, uint32_t *tokens, ChunkMeta *meta, hipStream_t st) { launch_walk<1>(g, cfg, ws, tokens, meta, TileGeom{}, st); }
 void launch_walk_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, const SortedWs &ws, ChunkMeta *meta, hipStream_t st)
 {
-    launch_walk<2>(g, cfg, ws, nullptr, meta, tg, st); // (a tile's walkers write games and exits, no tokens)
+    if (geom_rows(g)) launch_walk<3>(g, cfg, ws, nullptr, meta, tg, st); // (many streams' tiles)
+    else launch_walk<2>(g, cfg, ws, nullptr, meta, tg, st); // (a tile's walkers write games and exits, no tokens)
 }
 
 } // namespace zgpu

@@ -126,6 +126,11 @@ def load_library():
     L.zgpu_deflate_batch_workspace_bytes.restype = u64
     L.zgpu_deflate_batch_enqueue.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, vp, vp, u64, u32, vp]
     L.zgpu_deflate_batch_packed_enqueue.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, vp, vp, u64, u32, vp]
+    L.zgpu_deflate_streams_bound.argtypes = [u64, u32]
+    L.zgpu_deflate_streams_bound.restype = u64
+    L.zgpu_deflate_streams_layout.argtypes = [vp, u64, u32, vp, C.POINTER(u64)]
+    L.zgpu_deflate_streams_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, C.POINTER(DeflateResult), vp]
+    L.zgpu_deflate_streams_host.argtypes = [vp, vp, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, C.POINTER(DeflateResult)]
     L.zgpu_engine_set_exact_sort.argtypes = [vp, C.c_int]
     L.zgpu_debug_sort_fallback.argtypes = [vp]
     L.zgpu_checksum_batch_host.argtypes = [vp, vp, u64, vp, u64, u32, vp]
@@ -365,6 +370,49 @@ class Engine:
         self.last = res
         raw = out[: res.out_bytes].tobytes()
         return [raw[int(ooffs[i]): int(ooffs[i + 1])] for i in range(len(buffers))]
+
+    def deflate_streams_host(self, items, level, wrap="zlib", strategy=0, flags=0, want_items=False):
+        """Batch of independent buffers of ANY length -> one complete stream per buffer (zgpu_deflate_streams_host): the bytes compress2() /
+        deflate(Z_FINISH) of the reference gives for that buffer alone, the tiles of all buffers sharing the launches.  Levels 4..9.  wrap as for
+        deflate_batch_host; flags: further ZGPU_F_* bits (F_CRC32).  want_items: also the records, a list of DeflateBatchItem."""
+        import numpy as np
+        flags = flags | F_FINAL | {"raw": 0, "zlib": F_ZLIB_WRAP, "gzip": F_GZIP_WRAP}[wrap]
+        n = len(items)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(b) for b in items])
+        blob = np.frombuffer(b"".join(bytes(b) for b in items) + b"\0", dtype=np.uint8)
+        ooffs = np.zeros(n + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        self._check(self.L.zgpu_deflate_streams_layout(offs.ctypes.data, n, flags, ooffs.ctypes.data, C.byref(total)))
+        cap = int(total.value)
+        out = np.empty(cap + 1, dtype=np.uint8)
+        recs = (DeflateBatchItem * max(n, 1))()
+        p = _Params(level, 0, flags, LZ_AUTO, strategy, 0)
+        res = DeflateResult()
+        self._check(self.L.zgpu_deflate_streams_host(self.h, blob.ctypes.data, offs.ctypes.data, n, C.byref(p), out.ctypes.data, cap, ooffs.ctypes.data, recs, C.byref(res)))
+        self.last = res
+        raw = out[: int(ooffs[n])].tobytes()
+        streams = [raw[int(ooffs[i]): int(ooffs[i + 1])] for i in range(n)]
+        return (streams, list(recs[:n])) if want_items else streams
+
+    def deflate_streams_layout(self, in_offsets, flags):
+        """Rooms that always suffice, from the sizes alone (zgpu_deflate_streams_layout): (out_offsets as a numpy uint64 array, total)."""
+        import numpy as np
+        offs = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        ooffs = np.zeros(n + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        self._check(self.L.zgpu_deflate_streams_layout(offs.ctypes.data, n, flags, ooffs.ctypes.data, C.byref(total)))
+        return ooffs, int(total.value)
+
+    def deflate_streams_device(self, d_in, in_bytes, d_in_offsets, n, level, d_out, out_cap, d_out_offsets, d_items, flags=F_FINAL, strategy=0, stream=None, lz_impl=LZ_AUTO):
+        """Device pointers as ints: d_in_offsets / d_out_offsets hold n + 1 uint64 (every room starts at a multiple of 4), d_items room for n
+        DeflateBatchItem.  Blocks until the records are written; returns the DeflateResult (reserved = records that are not ZGPU_OK)."""
+        p = _Params(level, 0, flags, lz_impl, strategy, 0)
+        res = DeflateResult()
+        self._check(self.L.zgpu_deflate_streams_device(self.h, d_in, in_bytes, d_in_offsets, n, C.byref(p), d_out, out_cap, d_out_offsets, d_items, C.byref(res), stream))
+        self.last = res
+        return res
 
     def inflate_batch_host(self, streams, out_caps, wrap="zlib", checks=0):
         """Batch of independent streams, one call (zgpu_inflate_batch_host).  out_caps: the room of each item (an int: the same for all).

@@ -2,7 +2,9 @@
  * each with the verdict compress2() / uncompress() (qcsrc/compress.c:22-58, qcsrc/uncompr.c:26-61) give it alone.
  *
  * Compress: the items of at most 64 KiB at levels 1-9 go to zgpu_deflate_segments_host with ZGPU_F_FINAL and the wrapper (every segment one
- * complete stream, byte for byte what compress2() of it emits); level 0 and larger items take the one-item path.  Uncompress: every item of
+ * complete stream, byte for byte what compress2() of it emits); larger items at levels 4-9 go to zgpu_deflate_streams_host, many continuous
+ * streams whose tiles share the launches, in calls of at most STREAMS_IN_MAX bytes of input; level 0, larger items at levels 1-3 and items of
+ * 4 GiB or more take the one-item path.  Uncompress: every item of
  * less than 512 MiB of input goes to zgpu_inflate_batch_host, the per-item codes are mapped the way uncompress() maps inflate()'s.
  * The batch calls use an engine of their own (created on first use, on the device ZAMD_DEVICE names, like the stream API's). */
 #include "../../include/zamd_batch.h"
@@ -15,6 +17,7 @@
 
 #define EXPORT __attribute__((visibility("default")))
 #define SEG_MAX 65536u
+#define STREAMS_IN_MAX (1ull << 30) /* input bytes of one zgpu_deflate_streams_host call (an item larger than that is a call of its own) */
 #define BATCH_IN_MAX (1ull << 29) /* the decoder's limit of compressed bytes per item */
 
 static pthread_mutex_t g_batch_lock = PTHREAD_MUTEX_INITIALIZER; /* one call at a time on the engine (one stream, one workspace) */
@@ -78,6 +81,59 @@ static int uncompress_one(Bytef *dest, uLongf *destLen, const Bytef *src, uLong 
     return inflateEnd(&st);
 }
 
+static uint64_t g_streams_calls, g_one_by_one; /* (diagnostic) */
+EXPORT unsigned long long zamd_compress2_batch_count(int which) { return which == 0 ? g_streams_calls : which == 1 ? g_one_by_one : 0; }
+
+static int engine_code(int rc);
+/* is item k of a compress batch one of the large items that go through zgpu_deflate_streams_host? */
+static int streams_item(uLong len, int level) { return level >= 4 && len > SEG_MAX && len <= 0xFFFFFFFFul; }
+
+/* the large items idx[0 .. m) as one zgpu_deflate_streams_host call; status and destLen of each as compress2() leaves them */
+static void compress_streams_call(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, const size_t *idx, size_t m, int level,
+                                  int windowBits, int *status)
+{
+    const uint32_t flags = ZGPU_F_FINAL | (windowBits == 15 ? ZGPU_F_ZLIB_WRAP : windowBits == 31 ? ZGPU_F_GZIP_WRAP : 0u);
+    uint64_t *ioff = malloc((m + 1) * sizeof *ioff), *ooff = malloc((m + 1) * sizeof *ooff);
+    zgpu_deflate_batch_item *items = malloc(m * sizeof *items);
+    uint8_t *in = NULL, *out = NULL;
+    uint64_t at = 0, cap = 0;
+    int rc = ioff && ooff && items ? ZGPU_OK : ZGPU_MEM_ERROR;
+    if (rc == ZGPU_OK) {
+        for (size_t i = 0; i < m; i++) { ioff[i] = at; at += sourceLen[idx[i]]; }
+        ioff[m] = at;
+        rc = zgpu_deflate_streams_layout(ioff, m, flags, ooff, &cap);
+    }
+    if (rc == ZGPU_OK) {
+        in = malloc(at + 1); out = malloc(cap + 1);
+        if (!in || !out) rc = ZGPU_MEM_ERROR;
+    }
+    if (rc == ZGPU_OK) {
+        for (size_t i = 0; i < m; i++) memcpy(in + ioff[i], source[idx[i]], sourceLen[idx[i]]);
+        zgpu_deflate_params p;
+        memset(&p, 0, sizeof p);
+        p.level = level; p.flags = flags; p.lz_impl = ZGPU_LZ_AUTO;
+        zgpu_deflate_result res;
+        memset(&res, 0, sizeof res);
+        zgpu_engine *e = zamd_batch_engine_lock();
+        if (!e) rc = ZGPU_ERRNO;
+        else {
+            rc = zgpu_deflate_streams_host(e, in, ioff, m, &p, out, cap, ooff, items, &res);
+            g_streams_calls++;
+            zamd_batch_engine_unlock();
+        }
+    }
+    for (size_t i = 0; i < m; i++) {
+        const size_t k = idx[i];
+        if (rc != ZGPU_OK) { status[k] = rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : engine_code(rc); continue; }
+        if (items[i].code != ZGPU_OK) { status[k] = items[i].code == ZGPU_BUF_ERROR ? Z_BUF_ERROR : Z_ERRNO; continue; }
+        if (items[i].out_bytes > destLen[k]) { status[k] = Z_BUF_ERROR; continue; }
+        memcpy(dest[k], out + ooff[i], items[i].out_bytes);
+        destLen[k] = items[i].out_bytes;
+        status[k] = Z_OK;
+    }
+    free(ioff); free(ooff); free(items); free(in); free(out);
+}
+
 static int engine_code(int rc) { return rc == ZGPU_MEM_ERROR ? Z_MEM_ERROR : rc == ZGPU_STREAM_ERROR ? Z_STREAM_ERROR : Z_ERRNO; }
 
 EXPORT int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int level,
@@ -133,8 +189,30 @@ EXPORT int zamd_compress2_batch(Bytef *const *dest, uLongf *destLen, const Bytef
         }
         free(in); free(out); free(seg); free(ooff); free(idx);
     }
+    { /* the large items at levels 4-9: many streams a call, at most STREAMS_IN_MAX bytes of input each */
+        size_t nl = 0;
+        for (size_t k = 0; k < n; k++) nl += streams_item(sourceLen[k], level) ? 1 : 0;
+        size_t *idx = nl ? malloc(nl * sizeof *idx) : NULL;
+        if (nl && !idx) {
+            for (size_t k = 0; k < n; k++)
+                if (streams_item(sourceLen[k], level)) status[k] = Z_MEM_ERROR;
+        } else if (nl) {
+            size_t m = 0;
+            uint64_t bytes = 0;
+            for (size_t k = 0; k < n; k++) {
+                if (!streams_item(sourceLen[k], level)) continue;
+                if (m && bytes + sourceLen[k] > STREAMS_IN_MAX) { compress_streams_call(dest, destLen, source, sourceLen, idx, m, level, windowBits, status); m = 0; bytes = 0; }
+                idx[m++] = k; bytes += sourceLen[k];
+            }
+            if (m) compress_streams_call(dest, destLen, source, sourceLen, idx, m, level, windowBits, status);
+        }
+        free(idx);
+    }
     for (size_t k = 0; k < n; k++)
-        if (!(level > 0 && sourceLen[k] <= SEG_MAX)) status[k] = compress_one(dest[k], &destLen[k], source[k], sourceLen[k], level, windowBits);
+        if (!(level > 0 && sourceLen[k] <= SEG_MAX) && !streams_item(sourceLen[k], level)) {
+            status[k] = compress_one(dest[k], &destLen[k], source[k], sourceLen[k], level, windowBits);
+            g_one_by_one++;
+        }
     return first_failure(status, n);
 }
 
