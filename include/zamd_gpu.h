@@ -338,6 +338,46 @@ int zgpu_deflate_streams_device(zgpu_engine *e, const void *d_in, uint64_t in_by
 int zgpu_deflate_streams_host(zgpu_engine *e, const void *in, const uint64_t *in_offsets, uint64_t n, const zgpu_deflate_params *p, void *out, uint64_t out_cap,
                               uint64_t *out_offsets, zgpu_deflate_batch_item *items, zgpu_deflate_result *res);
 
+/* ---- the same, stream-ordered: items of ANY length compressed on the caller's stream (zlib_amd/csrc/zgpu_deflate_streams_enqueue.hip) ----
+ * zgpu_deflate_streams_enqueue makes exactly what zgpu_deflate_streams_device makes -- item k = d_in[io[k] .. io[k+1]), 0 to below 2^32 bytes, becomes the
+ * same bytes in its room d_out[oo[k] .. oo[k+1]), with the same record -- as ONE chain of kernel launches on hip_stream (null: the engine's), and returns.
+ * The contract is that of zgpu_deflate_batch_enqueue above, word for word: the call does not synchronize, allocate, copy to or from host memory, record an
+ * event, use a second stream or time anything, and uses no device memory of the engine's.  The scratch is d_ws: 256-byte aligned, at least
+ * zgpu_deflate_streams_workspace_bytes(n, in_bytes, batch_tiles) bytes, a function of those three numbers alone (never of the level or the wrapper) that
+ * needs no engine and no GPU.  Two calls with different workspaces may be in flight on two streams of one engine; a call can wait behind the kernel that
+ * makes its input; it can be captured into a graph, though not as the first call of a process (code objects load, and two kernels' attributes are set, on
+ * first use).  Served and refused parameters are zgpu_deflate_streams_device's: levels 4..9, all five strategies, one wrapper at most, ZGPU_F_CRC32,
+ * zgpu_deflate_set_tuning, ZGPU_F_FINAL required; ZGPU_STREAM_ERROR with nothing enqueued for the rest, and for what the host can judge of the arguments:
+ * a null pointer that is needed, n >= 2^32, d_out not 4-byte aligned, d_ws not 256-byte aligned, ws_bytes too small.  n == 0 enqueues at most the launch
+ * that clears the summary.
+ * The plan is made on the device.  The host knows neither the items' sizes nor the number of tiles; it lays the tile list out for
+ * ntiles_max = in_bytes / 32512 + n tiles (a stream of L bytes has at most L / 32512 + 1) and enqueues ceil(ntiles_max / batch_tiles) rounds of launches;
+ * rows behind the real tiles are padding, for which every kernel leaves at its top.  batch_tiles = tiles per round: 0 selects 2,048, more than 32,768 is
+ * 32,768, and a round is never larger than ntiles_max.  A tile of a round costs 2,110,800 bytes of workspace (the sorted buckets 1,058,832, tokens
+ * 262,144, the streams' compact tokens 327,680, seven block slots 460,544, the rest 1,600); besides that the call needs 92 bytes an item and 46 per tile
+ * of ntiles_max.  The seven scans around block construction run as seven launches per round over all streams of the round.
+ * The host never sees the tables, so a bad entry fails its item, not the call: ZGPU_STREAM_ERROR, out_bytes = in_bytes = 0, adler32 = 1, crc32 = 0,
+ * data_type = 2 for an item whose input range runs backwards or leaves in_bytes, whose room runs backwards, leaves out_cap or does not start at a
+ * multiple of 4 (all counted in nbad_offsets), or that is 4 GiB or longer (ntoo_long).  Such an item has no tiles, reads nothing and writes nothing, and
+ * every other item is served as if it were not there.  Input ranges may overlap; when they ask for more than ntiles_max tiles, the items whose last
+ * tile -- counted over all items with good entries in table order -- lies behind ntiles_max fail as bad entries.  A room too small is ZGPU_BUF_ERROR
+ * with out_bytes = 0, as in the blocking call.
+ * Summary (optional): nfailed = records that are not ZGPU_OK, nbad_offsets, ntoo_long, total = the sum of out_bytes, overflow = 0, sort_fault as for
+ * zgpu_deflate_batch_enqueue: the fault word lies in d_ws, is cleared at the head and read by the last launch; raised, every record has code =
+ * ZGPU_ERRNO and the caller answers with zgpu_engine_set_exact_sort and enqueues again.
+ * Rooms without the host knowing the sizes: zgpu_deflate_streams_rooms_bound(n, in_bytes, flags) is a closed form that is at least
+ * zgpu_deflate_streams_layout's total for every table of n items that runs forward and ends inside in_bytes (equal for one item of in_bytes), and
+ * zgpu_deflate_streams_layout_enqueue writes d_out_offsets[0..n] on the device: rooms of zgpu_deflate_streams_bound each -- for a good table exactly what
+ * zgpu_deflate_streams_layout gives -- and a room of 0 for an entry that runs backwards or leaves in_bytes.
+ * Not served here: levels 0..3, a packed-output entry, preset dictionaries. */
+uint64_t zgpu_deflate_streams_workspace_bytes(uint64_t n, uint64_t in_bytes, uint32_t batch_tiles); /* 0: n >= 2^32 */
+uint64_t zgpu_deflate_streams_rooms_bound(uint64_t n, uint64_t in_bytes, uint32_t flags);
+int zgpu_deflate_streams_layout_enqueue(zgpu_engine *e, const uint64_t *d_in_offsets, uint64_t n, uint64_t in_bytes, uint32_t flags, uint64_t *d_out_offsets,
+                                        void *hip_stream);
+int zgpu_deflate_streams_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, const zgpu_deflate_params *p,
+                                 void *d_out, uint64_t out_cap, const uint64_t *d_out_offsets, zgpu_deflate_batch_item *d_items,
+                                 zgpu_deflate_batch_summary *d_summary, void *d_ws, uint64_t ws_bytes, uint32_t batch_tiles, void *hip_stream);
+
 /* ---- BGZF: blocked gzip, the container of bgzip, BAM, tabix and .vcf.gz (RFC 1952 + SAM specification 4.1) ----
  * A file is gzip members laid end to end, each at most 64 KiB long and decoding to at most 64 KiB, each carrying its own total length in its header
  * (BSIZE in the 'B' 'C' extra subfield), closed by a fixed 28-byte empty block.

@@ -115,8 +115,10 @@ __device__ inline void adler_sums(const uint8_t *src, uint32_t n, uint32_t t, ui
     for (uint32_t i = head + (nvec << 4) + t; i < n; i += stride) { const uint32_t b = src[i]; s1 += b; s2 += (uint64_t)(n - i) * b; }
 }
 
+// STATE (the stream-ordered batch compress, checksum_batch_enqueue below): state[k] != 0 marks an item the table check has failed -- it is not read
+template <bool STATE>
 __global__ void __launch_bounds__(256) check_short_kernel(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off, const uint64_t *__restrict__ piece0, uint64_t n,
-                                                          uint32_t checks, zgpu_check_item *items)
+                                                          uint32_t checks, zgpu_check_item *items, const uint32_t *__restrict__ state)
 {
     __shared__ uint32_t table[4][256];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -125,6 +127,7 @@ __global__ void __launch_bounds__(256) check_short_kernel(const uint8_t *__restr
         const uint64_t k = (uint64_t)blockIdx.x * kGroupItems + j * 4 + wave; // (the wave's own: no barrier below)
         if (k >= n) break;
         if (piece0[k + 1] != piece0[k]) continue; // a long item: the piece kernels'
+        if constexpr (STATE) { if (state[k] != 0) continue; }
         const uint64_t lo = off[k];
         const uint32_t len = (uint32_t)(off[k + 1] - lo);
         const uint8_t *src = in + lo;
@@ -150,7 +153,8 @@ __global__ void __launch_bounds__(256) check_short_kernel(const uint8_t *__restr
     }
 }
 
-// workgroup w: piece p0 + w of the call
+// workgroup w: piece p0 + w of the call.  BOUND: launched at an upper bound of the pieces, the number itself is piece0[n]
+template <bool BOUND>
 __global__ void __launch_bounds__(256) check_piece_kernel(const uint8_t *__restrict__ in, const uint64_t *__restrict__ off, const uint64_t *__restrict__ piece0, uint64_t n,
                                                           uint64_t p0, uint32_t checks, PiecePart *part)
 {
@@ -159,6 +163,7 @@ __global__ void __launch_bounds__(256) check_piece_kernel(const uint8_t *__restr
     __shared__ uint64_t red1[4], red2[4];
     const uint32_t tid = threadIdx.x;
     const uint64_t p = p0 + blockIdx.x;
+    if constexpr (BOUND) { if (p >= piece0[n]) return; } // (uniform, in front of every barrier)
     uint64_t k = 0, hi_k = n; // the last item whose first piece is at most p (items without pieces share their neighbour's number and lose)
     while (hi_k - k > 1) { const uint64_t mid = k + (hi_k - k) / 2; if (piece0[mid] <= p) k = mid; else hi_k = mid; }
     const uint64_t lo = off[k], len = off[k + 1] - lo, at = (p - piece0[k]) * kChunkMax;
@@ -232,18 +237,32 @@ int checksum_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, c
     ZGPU_HIP_CHECK(hipMemcpyAsync(&npieces, e->ck_piece0 + n, 8, hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     if (bad) return fail(e, ZGPU_STREAM_ERROR, "checksum batch offsets out of range");
-    hipLaunchKernelGGL(check_short_kernel, dim3((uint32_t)((n + kGroupItems - 1) / kGroupItems)), dim3(256), 0, st, d_in, d_off, e->ck_piece0.p, n, checks, d_items);
+    hipLaunchKernelGGL(check_short_kernel<false>, dim3((uint32_t)((n + kGroupItems - 1) / kGroupItems)), dim3(256), 0, st, d_in, d_off, e->ck_piece0.p, n, checks, d_items, nullptr);
     if (npieces) {
         if ((rc = e->ck_part.reserve(e, npieces * (sizeof(PiecePart) / sizeof(uint32_t))))) return rc;
         PiecePart *part = reinterpret_cast<PiecePart *>(e->ck_part.p);
         const uint64_t slab = 1ull << 24; // workgroups a launch
         for (uint64_t p0 = 0; p0 < npieces; p0 += slab)
-            hipLaunchKernelGGL(check_piece_kernel, dim3((uint32_t)(npieces - p0 < slab ? npieces - p0 : slab)), dim3(256), 0, st, d_in, d_off, e->ck_piece0.p, n, p0, checks, part);
+            hipLaunchKernelGGL(check_piece_kernel<false>, dim3((uint32_t)(npieces - p0 < slab ? npieces - p0 : slab)), dim3(256), 0, st, d_in, d_off, e->ck_piece0.p, n, p0, checks, part);
         hipLaunchKernelGGL(check_join_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_off, e->ck_piece0.p, n, part, checks, d_items);
     }
     ZGPU_HIP_CHECK(hipGetLastError());
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     return ZGPU_OK;
+}
+
+// The same without the round trip, for a call that may not wait (zgpu_deflate_streams_enqueue.hip): the plan is the caller's -- state[k] (0: served) and
+// piece0[0..n] over the served long items, made on the device -- and the piece kernel is launched at the host's upper bound of the pieces, npieces_max;
+// part: room for that many partials.  Launches only
+void checksum_batch_enqueue(const uint8_t *d_in, const uint64_t *d_off, const uint32_t *state, const uint64_t *piece0, uint64_t n, uint64_t npieces_max, uint32_t checks, void *part,
+                            zgpu_check_item *d_items, hipStream_t st)
+{
+    hipLaunchKernelGGL(check_short_kernel<true>, dim3((uint32_t)((n + kGroupItems - 1) / kGroupItems)), dim3(256), 0, st, d_in, d_off, piece0, n, checks, d_items, state);
+    const uint64_t slab = 1ull << 24;
+    for (uint64_t p0 = 0; p0 < npieces_max; p0 += slab)
+        hipLaunchKernelGGL(check_piece_kernel<true>, dim3((uint32_t)(npieces_max - p0 < slab ? npieces_max - p0 : slab)), dim3(256), 0, st, d_in, d_off, piece0, n, p0, checks,
+                           static_cast<PiecePart *>(part));
+    hipLaunchKernelGGL(check_join_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_off, piece0, n, static_cast<const PiecePart *>(part), checks, d_items);
 }
 
 } // namespace zgpu

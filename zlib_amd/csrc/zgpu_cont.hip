@@ -20,6 +20,7 @@
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
 #include "../../include/zamd_gpu.h"
+#include "zgpu_deflate_streams_plan.h"
 
 namespace zgpu {
 
@@ -51,17 +52,20 @@ __global__ void __launch_bounds__(64) chain_apply_kernel(const uint16_t *__restr
 
 // ------------------------------------------------------------------------------------------------- chain 2: tokens -> blocks
 // exclusive scan of the tiles' token counts behind the carried tokens (which become the front of the compact array)
-__global__ void __launch_bounds__(1024) cont_tokscan_kernel(const ChunkMeta *__restrict__ tmeta, uint32_t ntiles, ContState *st, uint32_t *__restrict__ tokoff,
-                                                            const uint32_t *__restrict__ carry, uint32_t *__restrict__ T)
+// (the bodies of the block layer's kernels are functions of the per-stream arguments: the kernels below call them with the host's arguments, the batched
+// kernels at the end of the file with arguments read from a part of a round.  NT: lanes of the workgroup, 1024 in the one-stream kernels)
+template <uint32_t NT>
+__device__ __forceinline__ void cont_tokscan_body(const ChunkMeta *__restrict__ tmeta, uint32_t ntiles, ContState *st, uint32_t *__restrict__ tokoff,
+                                                  const uint32_t *__restrict__ carry, uint32_t *__restrict__ T)
 {
-    __shared__ uint32_t part[1024];
-    const uint32_t tid = threadIdx.x, per = (ntiles + 1023) / 1024;
+    __shared__ uint32_t part[NT];
+    const uint32_t tid = threadIdx.x, per = (ntiles + NT - 1) / NT;
     const uint32_t a = tid * per < ntiles ? tid * per : ntiles, z = (tid + 1) * per < ntiles ? (tid + 1) * per : ntiles;
     uint32_t sum = 0;
     for (uint32_t i = a; i < z; i++) sum += tmeta[i].ntok;
     part[tid] = sum;
     __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
+    for (uint32_t d = 1; d < NT; d <<= 1) {
         const uint32_t add = tid >= d ? part[tid - d] : 0;
         __syncthreads();
         part[tid] += add;
@@ -70,8 +74,13 @@ __global__ void __launch_bounds__(1024) cont_tokscan_kernel(const ChunkMeta *__r
     const uint32_t cn = st->carry_n;
     uint32_t o = cn + part[tid] - sum;
     for (uint32_t i = a; i < z; i++) { tokoff[i] = o; o += tmeta[i].ntok; }
-    for (uint32_t j = tid; j < cn; j += 1024) T[j] = carry[j];
-    if (tid == 1023) { tokoff[ntiles] = cn + part[1023]; st->total = cn + part[1023]; }
+    for (uint32_t j = tid; j < cn; j += NT) T[j] = carry[j];
+    if (tid == NT - 1) { tokoff[ntiles] = cn + part[NT - 1]; st->total = cn + part[NT - 1]; }
+}
+__global__ void __launch_bounds__(1024) cont_tokscan_kernel(const ChunkMeta *__restrict__ tmeta, uint32_t ntiles, ContState *st, uint32_t *__restrict__ tokoff,
+                                                            const uint32_t *__restrict__ carry, uint32_t *__restrict__ T)
+{
+    cont_tokscan_body<1024>(tmeta, ntiles, st, tokoff, carry, T);
 }
 
 // a tile's tokens to their place in the compact array; for every block whose LAST token lies in this tile: where the block ends, how long that token is
@@ -79,34 +88,8 @@ constexpr uint32_t kMaxCuts = 6; // ceil(65536 / 16383) + 1
 __global__ void __launch_bounds__(256) cont_compact_kernel(ChunkGeom g, TileGeom tg, const uint32_t *__restrict__ tokens, const ChunkMeta *__restrict__ tmeta,
                                                            const uint32_t *__restrict__ tokoff, uint32_t *__restrict__ T, ContBlk *__restrict__ blk)
 {
-    __shared__ unsigned long long sums[kMaxCuts];
-    __shared__ uint32_t lastlen[kMaxCuts];
-    const uint32_t c = blockIdx.x, tid = threadIdx.x, n = tmeta[c].ntok, off = tokoff[c];
-    const uint32_t *tok = tokens + (size_t)c * kChunkMax;
-    uint32_t ncut = 0, istar[kMaxCuts];
-    for (uint32_t B = (off / kBlockTokens + 1) * kBlockTokens; B <= off + n && ncut < kMaxCuts; B += kBlockTokens) istar[ncut++] = B - 1 - off;
-    if (tid < kMaxCuts) { sums[tid] = 0; lastlen[tid] = 0; }
-    __syncthreads();
-    unsigned long long s[kMaxCuts] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t j = tid; j < n; j += 256) {
-        const uint32_t t = tok[j], len = (t >> 8) ? (t & 255u) + kMinMatch : 1u;
-        T[off + j] = t;
-        for (uint32_t q = 0; q < ncut; q++) { if (j <= istar[q]) s[q] += len; if (j == istar[q]) lastlen[q] = len; }
-    }
-    if (ncut == 0) return; // (uniform)
-    for (uint32_t q = 0; q < ncut; q++) {
-        unsigned long long v = s[q];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        if ((tid & 63) == 0 && v) atomicAdd(&sums[q], v);
-    }
-    __syncthreads();
-    if (tid < ncut) {
-        uint64_t wb; uint32_t nloc, h0, h1, ne;
-        tile_span(g, tg, c, wb, nloc, h0, h1, ne);
-        const uint64_t e_abs = tg.abs0 + wb + h0 + tg.entry[g.chunk0 + c];
-        ContBlk &b = blk[(off + istar[tid] + 1) / kBlockTokens - 1];
-        b.end_pos = e_abs + sums[tid]; b.last_len = lastlen[tid];
-    }
+    const uint32_t c = blockIdx.x;
+#include "zgpu_cont_compact_body.inc"
 }
 
 // slides of the reference's window that have happened when its loop stands at stream position ptop (deflate.c:1293: strstart >= wsize + MAX_DIST inside
@@ -125,8 +108,9 @@ __host__ __device__ inline uint64_t cont_special(uint64_t n)
 }
 
 // the batch's blocks.  seg_end: the stream position the segment ends at when this batch reaches it (the block that is filling is closed there), ~0: more follows
-__global__ void __launch_bounds__(256) cont_table_kernel(ContBlk *__restrict__ blk, ContState *st, const uint32_t *__restrict__ T, uint64_t seg_end, uint32_t final_block,
-                                                         uint64_t sp, uint32_t nblk_cap, uint32_t slow)
+// b: the block slot of the stream; true: it holds a block of this batch
+__device__ __forceinline__ bool cont_table_body(uint32_t b, ContBlk *__restrict__ blk, ContState *st, const uint32_t *__restrict__ T, uint64_t seg_end, uint32_t final_block,
+                                                uint64_t sp, uint32_t nblk_cap, uint32_t slow)
 {
     const uint32_t total = st->total;
     uint32_t nblk = total / kBlockTokens;
@@ -138,9 +122,8 @@ __global__ void __launch_bounds__(256) cont_table_kernel(ContBlk *__restrict__ b
         if (!full_last) nblk++;
     }
     if (nblk > nblk_cap) nblk = nblk_cap; // (cannot happen: the capacity is computed from the positions of the batch)
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b == 0) st->nblk = nblk;
-    if (b >= nblk) return;
+    if (b >= nblk) return false;
     ContBlk &k = blk[b];
     k.tok0 = b * kBlockTokens;
     const bool complete = (uint64_t)(b + 1) * kBlockTokens <= total;
@@ -156,6 +139,12 @@ __global__ void __launch_bounds__(256) cont_table_kernel(ContBlk *__restrict__ b
     const uint64_t ptop = k.end_pos - k.last_len + ((slow || !complete) ? 1 : 0);
     k.nostore = k.start_pos < 32768u * cont_slides(ptop, sp);
     k.nbits = 0; k.btype = 0; k.stored_len = 0; k.eob_len = 8;
+    return true;
+}
+__global__ void __launch_bounds__(256) cont_table_kernel(ContBlk *__restrict__ blk, ContState *st, const uint32_t *__restrict__ T, uint64_t seg_end, uint32_t final_block,
+                                                         uint64_t sp, uint32_t nblk_cap, uint32_t slow)
+{
+    cont_table_body(blockIdx.x * 256 + threadIdx.x, blk, st, T, seg_end, final_block, sp, nblk_cap, slow);
 }
 
 // ------------------------------------------------------------------------------------------------- chain 3: bit positions
@@ -163,11 +152,12 @@ __device__ inline uint64_t blk_advance(uint64_t pos, const ContBlk &k)
 {
     return k.btype ? pos + k.nbits : ((pos + 3 + 7) & ~7ull) + 32 + 8ull * k.stored_len; // trees.c:867-879: 3 header bits, bi_windup, LEN, NLEN, the bytes
 }
-__global__ void __launch_bounds__(1024) cont_bitscan_kernel(const ContBlk *__restrict__ blk, ContState *st, uint64_t *__restrict__ pos, uint64_t out_cap_bits)
+template <uint32_t NT>
+__device__ __forceinline__ void cont_bitscan_body(const ContBlk *__restrict__ blk, ContState *st, uint64_t *__restrict__ pos, uint64_t out_cap_bits)
 {
-    __shared__ uint32_t adv[1024][8];
-    __shared__ uint64_t segpos[1025];
-    const uint32_t tid = threadIdx.x, nblk = st->nblk, per = (nblk + 1023) / 1024;
+    __shared__ uint32_t adv[NT][8];
+    __shared__ uint64_t segpos[NT + 1];
+    const uint32_t tid = threadIdx.x, nblk = st->nblk, per = (nblk + NT - 1) / NT;
     const uint32_t a = tid * per < nblk ? tid * per : nblk, z = (tid + 1) * per < nblk ? (tid + 1) * per : nblk;
     for (uint32_t ph = 0; ph < 8; ph++) {
         uint64_t p = ph;
@@ -177,8 +167,8 @@ __global__ void __launch_bounds__(1024) cont_bitscan_kernel(const ContBlk *__res
     __syncthreads();
     if (tid == 0) {
         uint64_t p = st->out_bits;
-        for (uint32_t s = 0; s < 1024; s++) { segpos[s] = p; p += adv[s][p & 7]; }
-        segpos[1024] = p;
+        for (uint32_t s = 0; s < NT; s++) { segpos[s] = p; p += adv[s][p & 7]; }
+        segpos[NT] = p;
         st->out_bits = p;
         pos[nblk] = p;
         if (p > out_cap_bits) st->overflow = 1;
@@ -187,14 +177,18 @@ __global__ void __launch_bounds__(1024) cont_bitscan_kernel(const ContBlk *__res
     uint64_t p = segpos[tid];
     for (uint32_t i = a; i < z; i++) { pos[i] = p; p = blk_advance(p, blk[i]); }
 }
+__global__ void __launch_bounds__(1024) cont_bitscan_kernel(const ContBlk *__restrict__ blk, ContState *st, uint64_t *__restrict__ pos, uint64_t out_cap_bits)
+{
+    cont_bitscan_body<1024>(blk, st, pos, out_cap_bits);
+}
 
 // A word of the output belongs to one block alone when all its 32 bits do: such words are stored.  A word that holds a block boundary is ORed into by
 // every block that has bits in it, and is cleared here first -- except the word the batch starts in when earlier bits (the batch before, the stream's
 // header, the bits a flush left over) are in it already.
 __device__ inline bool word_is_inner(uint64_t w, uint64_t D, uint64_t E) { return 32 * w >= D && 32 * w + 32 <= E; }
-__global__ void __launch_bounds__(256) cont_edges_kernel(const ContState *st, const uint64_t *__restrict__ pos, uint32_t *__restrict__ out, uint64_t out_words)
+__device__ __forceinline__ void cont_edges_body(uint32_t b, const ContState *st, const uint64_t *__restrict__ pos, uint32_t *__restrict__ out, uint64_t out_words)
 {
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x, nblk = st->nblk;
+    const uint32_t nblk = st->nblk;
     if (b >= nblk) return;
     const uint64_t D = pos[b], E = pos[b + 1];
     if (E == D) return;
@@ -202,60 +196,25 @@ __global__ void __launch_bounds__(256) cont_edges_kernel(const ContState *st, co
     if (!word_is_inner(wf, D, E) && wf != keep && wf < out_words) out[wf] = 0;
     if (wl != wf && !word_is_inner(wl, D, E) && wl < out_words) out[wl] = 0;
 }
+__global__ void __launch_bounds__(256) cont_edges_kernel(const ContState *st, const uint64_t *__restrict__ pos, uint32_t *__restrict__ out, uint64_t out_words)
+{
+    cont_edges_body(blockIdx.x * 256 + threadIdx.x, st, pos, out, out_words);
+}
 __global__ void __launch_bounds__(256) cont_stitch_kernel(const ContBlk *__restrict__ blk, const ContState *st, const uint64_t *__restrict__ pos, const uint8_t *__restrict__ slots,
                                                           uint32_t slot_stride, const uint8_t *__restrict__ in, uint64_t abs0, uint32_t *__restrict__ out, uint64_t out_words)
 {
-    const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    if (b >= st->nblk) return;
-    const ContBlk &k = blk[b];
-    const uint64_t D = pos[b], E = pos[b + 1];
-    if (E == D) return;
-    const uint64_t wf = D >> 5, wl = (E - 1) >> 5;
-    if (k.btype) { // a coded block: its bits, from bit 0 of the slot, shifted to D
-        const uint32_t *S = reinterpret_cast<const uint32_t *>(slots + (size_t)b * slot_stride);
-        const uint32_t nsw = (k.nbits + 31) >> 5;
-        for (uint64_t w = wf + tid; w <= wl; w += 256) {
-            if (w >= out_words) break;
-            uint32_t v;
-            if (32 * w < D) v = S[0] << (uint32_t)(D - 32 * w);
-            else {
-                const uint64_t o = 32 * w - D;
-                const uint32_t sw = (uint32_t)(o >> 5), sh = (uint32_t)(o & 31), lo = S[sw], hi = sw + 1 < nsw ? S[sw + 1] : 0u;
-                v = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-            }
-            if (32 * w + 32 > E) v &= (1u << (uint32_t)(E - 32 * w)) - 1u;
-            if (word_is_inner(w, D, E)) out[w] = v; else atomicOr(&out[w], v);
-        }
-    } else { // a stored block (trees.c:867-879, 1197-1219): three header bits at D, zeros up to the byte boundary, LEN, ~LEN, the bytes of the input
-        const uint32_t ph = (uint32_t)(D & 7), hb = (ph + 3 + 7) >> 3, len = k.stored_len, hdr = k.eof << ph;
-        const uint64_t db0 = D >> 3, nb = hb + 4 + (uint64_t)len;
-        const uint8_t *src = in + (k.start_pos - abs0);
-        for (uint64_t w = wf + tid; w <= wl; w += 256) {
-            if (w >= out_words) break;
-            uint32_t v = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                const uint64_t a = 4 * w + j;
-                if (a < db0 || a - db0 >= nb) continue;
-                const uint64_t i = a - db0;
-                uint32_t byte;
-                if (i < hb) byte = (hdr >> (8 * (uint32_t)i)) & 255u;
-                else if (i < hb + 4) { const uint32_t f = (uint32_t)(i - hb), l16 = f < 2 ? len : ~len; byte = (l16 >> (8 * (f & 1))) & 255u; }
-                else byte = src[i - hb - 4];
-                v |= byte << (8 * j);
-            }
-            if (word_is_inner(w, D, E)) out[w] = v; else atomicOr(&out[w], v);
-        }
-    }
+    const uint32_t b = blockIdx.x;
+#include "zgpu_cont_stitch_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------- chain 4: to the next batch
 // the tokens behind the last emitted block wait in the carry buffer; the state moves on.  seg_end as in cont_table_kernel.
-__global__ void __launch_bounds__(1024) cont_carry_kernel(const ContBlk *__restrict__ blk, ContState *st, const uint32_t *__restrict__ T, uint32_t *__restrict__ carry, uint64_t seg_end)
+template <uint32_t NT>
+__device__ __forceinline__ void cont_carry_body(const ContBlk *__restrict__ blk, ContState *st, const uint32_t *__restrict__ T, uint32_t *__restrict__ carry, uint64_t seg_end)
 {
     const uint32_t tid = threadIdx.x, nblk = st->nblk, total = st->total, old_carry = st->carry_n;
     const uint32_t used = seg_end != ~0ull ? total : nblk * kBlockTokens, rem = total - used;
-    for (uint32_t j = tid; j < rem; j += 1024) carry[j] = T[used + j];
+    for (uint32_t j = tid; j < rem; j += NT) carry[j] = T[used + j];
     __syncthreads();
     if (tid == 0) {
         st->ntokens += total - old_carry;
@@ -263,6 +222,122 @@ __global__ void __launch_bounds__(1024) cont_carry_kernel(const ContBlk *__restr
         if (nblk) { st->block_start = blk[nblk - 1].end_pos; st->last_eob = blk[nblk - 1].eob_len; st->first_block = 0; }
         if (seg_end != ~0ull) st->block_start = seg_end;
     }
+}
+__global__ void __launch_bounds__(1024) cont_carry_kernel(const ContBlk *__restrict__ blk, ContState *st, const uint32_t *__restrict__ T, uint32_t *__restrict__ carry, uint64_t seg_end)
+{
+    cont_carry_body<1024>(blk, st, T, carry, seg_end);
+}
+
+// ------------------------------------------------------------------------------------------------- the block layer of MANY streams, batched
+// The stream-ordered batch call (zgpu_deflate_streams_enqueue.hip) cannot launch stream by stream: which streams a round of tiles holds is known on the
+// device only (StreamsRoundPart, zgpu_deflate_streams_plan.h; made by senq_round_kernel, zgpu_streams_batch.hip).  The seven scans above run here as seven
+// launches over ALL parts of a round: the bodies above with the arguments StreamBlocks (zgpu_deflate_streams.hip) would give them on the host, read from the
+// part -- part blockIdx.x for the three scans, the part found for a tile or a block slot for the others.  Launched at the host's upper bounds (a part per
+// tile, kSenqBlkPerTile block slots per tile); what belongs to nobody leaves at the top, uniformly per workgroup where a barrier follows.
+constexpr uint32_t kBatchScan = 256; // lanes of the batched scans: a part has a handful of tiles and blocks
+
+struct PartView { // a part with its stream's arguments
+    StreamsRoundPart p; StreamsPartArgs a; uint64_t in_lo, out_lo, out_words;
+};
+__device__ __forceinline__ PartView part_view(const ContBatch &q, uint32_t j)
+{
+    PartView v;
+    v.p = q.parts[j];
+    const uint64_t k = v.p.item;
+    v.in_lo = q.in_off[k];
+    v.a = senq_part_args(v.p, q.in_off[k + 1] - v.in_lo, q.tile0[k], q.t0);
+    v.out_lo = q.oo[k];
+    v.out_words = streams_room_cap(q.oo[k + 1] - v.out_lo, q.flags) >> 2;
+    return v;
+}
+// the last part with key <= x (x below the round's extent: there is one)
+__device__ __forceinline__ uint32_t part_of_tile(const ContBatch &q, uint32_t nparts, uint32_t c)
+{
+    uint32_t lo = 0, hi = nparts;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (q.parts[mid].c0 <= c) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ uint32_t part_of_slot(const ContBatch &q, uint32_t nparts, uint32_t s)
+{
+    uint32_t lo = 0, hi = nparts;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (q.parts[mid].boff <= s) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kBatchScan) cont_tokscan_batch_kernel(ContBatch q)
+{
+    if (blockIdx.x >= q.round->nparts) return;
+    const PartView v = part_view(q, blockIdx.x);
+    cont_tokscan_body<kBatchScan>(q.tmeta + v.p.c0, v.p.nt, q.st + v.p.item, q.tokoff + v.p.c0 + v.p.j, q.carry, q.T + v.p.toff);
+}
+__global__ void __launch_bounds__(256) cont_compact_batch_kernel(ContBatch q)
+{
+    const StreamsRound r = *q.round;
+    if (blockIdx.x >= r.nreal) return;
+    const PartView v = part_view(q, part_of_tile(q, r.nparts, blockIdx.x));
+    ChunkGeom g{}; TileGeom tg{};
+    g.in = q.in + v.in_lo; g.in_bytes = v.a.L; g.chunk_size = kChunkMax; g.final_chunk = ~0ull; g.block_tokens = kBlockTokens; g.slot_stride = kSlotStride;
+    g.tile_w0 = 0; g.tile_stride = kTileStride; g.chunk0 = v.a.chunk0; g.nchunks = v.p.nt;
+    tg.abs0 = 0; tg.e0 = 0; tg.end = v.a.L; tg.nil_pos = ~0ull; tg.abs0_nil = 1;
+    tg.entry = const_cast<uint16_t *>(q.entry) + q.tile0[v.p.item];
+    const uint32_t c = blockIdx.x - v.p.c0;
+    const uint32_t *tokens = q.tokens + (size_t)v.p.c0 * kChunkMax;
+    const ChunkMeta *tmeta = q.tmeta + v.p.c0;
+    const uint32_t *tokoff = q.tokoff + v.p.c0 + v.p.j;
+    uint32_t *T = q.T + v.p.toff;
+    ContBlk *blk = q.blk + v.p.boff;
+#include "zgpu_cont_compact_body.inc"
+}
+// ... with streams_blocks_kernel's work (zgpu_streams.hip) folded in: every slot of the launch learns whose it is, a block's tokens their place in the round's array
+__global__ void __launch_bounds__(256) cont_table_batch_kernel(ContBatch q)
+{
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= q.nslots_max) return;
+    const StreamsRound r = *q.round;
+    if (s >= r.nslots) { q.blk_item[s] = 0xFFFFFFFFu; return; }
+    const PartView v = part_view(q, part_of_slot(q, r.nparts, s));
+    ContBlk *blk = q.blk + v.p.boff;
+    const uint32_t b = s - v.p.boff;
+    const bool is_block = cont_table_body(b, blk, q.st + v.p.item, q.T + v.p.toff, v.a.seg_end, v.a.final_block, v.a.sp, v.p.nblk_cap, q.slow);
+    if (is_block) { blk[b].tok0 += v.p.toff; q.blk_item[s] = v.p.item; }
+    else q.blk_item[s] = 0xFFFFFFFFu;
+}
+__global__ void __launch_bounds__(kBatchScan) cont_bitscan_batch_kernel(ContBatch q)
+{
+    if (blockIdx.x >= q.round->nparts) return;
+    const PartView v = part_view(q, blockIdx.x);
+    cont_bitscan_body<kBatchScan>(q.blk + v.p.boff, q.st + v.p.item, q.pos + v.p.boff + v.p.j, v.out_words * 32);
+}
+__global__ void __launch_bounds__(256) cont_edges_batch_kernel(ContBatch q)
+{
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    const StreamsRound r = *q.round;
+    if (s >= r.nslots) return;
+    const PartView v = part_view(q, part_of_slot(q, r.nparts, s));
+    cont_edges_body(s - v.p.boff, q.st + v.p.item, q.pos + v.p.boff + v.p.j, reinterpret_cast<uint32_t *>(q.out + v.out_lo), v.out_words);
+}
+__global__ void __launch_bounds__(256) cont_stitch_batch_kernel(ContBatch q)
+{
+    const StreamsRound r = *q.round;
+    if (blockIdx.x >= r.nslots) return;
+    const PartView v = part_view(q, part_of_slot(q, r.nparts, blockIdx.x));
+    const uint32_t b = blockIdx.x - v.p.boff;
+    const ContBlk *blk = q.blk + v.p.boff;
+    const ContState *st = q.st + v.p.item;
+    const uint64_t *pos = q.pos + v.p.boff + v.p.j;
+    const uint8_t *slots = q.slots + (size_t)v.p.boff * kSlotStride;
+    const uint32_t slot_stride = kSlotStride;
+    const uint8_t *in = q.in + v.in_lo;
+    const uint64_t abs0 = 0, out_words = v.out_words;
+    uint32_t *out = reinterpret_cast<uint32_t *>(q.out + v.out_lo);
+#include "zgpu_cont_stitch_body.inc"
+}
+// (at most one stream is open at a round's end, the last part's: the one carry buffer serves; a stream that ends carries nothing)
+__global__ void __launch_bounds__(kBatchScan) cont_carry_batch_kernel(ContBatch q)
+{
+    if (blockIdx.x >= q.round->nparts) return;
+    const PartView v = part_view(q, blockIdx.x);
+    cont_carry_body<kBatchScan>(q.blk + v.p.boff, q.st + v.p.item, q.T + v.p.toff, q.carry, v.a.seg_end);
 }
 
 // ------------------------------------------------------------------------------------------------- launches
@@ -292,5 +367,21 @@ void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const 
     hipLaunchKernelGGL(cont_carry_kernel, dim3(1), dim3(1024), 0, s, blk, st, T, carry, seg_end);
 }
 uint64_t cont_special_pos(uint64_t n) { return cont_special(n); }
+
+// the round's tokens into blocks, behind the parse: launches 1-3 of the seven
+void launch_cont_batch_tokens(const ContBatch &q, uint32_t batch, hipStream_t s)
+{
+    hipLaunchKernelGGL(cont_tokscan_batch_kernel, dim3(batch), dim3(kBatchScan), 0, s, q);
+    hipLaunchKernelGGL(cont_compact_batch_kernel, dim3(batch), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(cont_table_batch_kernel, dim3((q.nslots_max + 255) / 256), dim3(256), 0, s, q);
+}
+// ... and the coded blocks into the rooms, behind block construction: launches 4-7
+void launch_cont_batch_stitch(const ContBatch &q, uint32_t batch, hipStream_t s)
+{
+    hipLaunchKernelGGL(cont_bitscan_batch_kernel, dim3(batch), dim3(kBatchScan), 0, s, q);
+    hipLaunchKernelGGL(cont_edges_batch_kernel, dim3((q.nslots_max + 255) / 256), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(cont_stitch_batch_kernel, dim3(q.nslots_max), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(cont_carry_batch_kernel, dim3(batch), dim3(kBatchScan), 0, s, q);
+}
 
 } // namespace zgpu

@@ -66,7 +66,7 @@ struct StreamBlocks {
     }
 };
 
-static const char *streams_refuse(const zgpu_engine *e, const zgpu_deflate_params *p)
+const char *streams_refuse(const zgpu_engine *e, const zgpu_deflate_params *p)
 {
     if (p->level < 4 || p->level > 9) return "many streams in one call: levels 4..9 (levels 0..3 are served one stream at a time)";
     if (p->strategy < 0 || p->strategy > (int)kFixed) return "strategy must be 0..4";

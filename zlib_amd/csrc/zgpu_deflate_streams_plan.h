@@ -46,7 +46,7 @@ __host__ __device__ inline uint32_t streams_head_bytes(uint32_t flags) { return 
 __host__ __device__ inline uint32_t streams_tail_bytes(uint32_t flags) { return (flags & ZGPU_F_ZLIB_WRAP) ? 4u : (flags & ZGPU_F_GZIP_WRAP) ? 8u : 0u; }
 // a room that always suffices for an item of item_bytes: the continuous stream's bound (deflateBound's arithmetic for blocks that may not be stored, a
 // word per block boundary) plus the wrapper, rounded up to the rooms' alignment
-inline uint64_t streams_bound(uint64_t item_bytes, uint32_t flags)
+__host__ __device__ inline uint64_t streams_bound(uint64_t item_bytes, uint32_t flags)
 {
     const uint64_t cont = item_bytes + ((item_bytes + 7) >> 3) + ((item_bytes + 63) >> 6) + 5 * (item_bytes / 16383 + 2) + 64; // zgpu_deflate_cont_bound
     return (cont + streams_head_bytes(flags) + streams_tail_bytes(flags) + 3) & ~3ull;
@@ -85,7 +85,7 @@ inline bool streams_tile_scan(const uint64_t *in_off, uint64_t n, uint64_t *tile
     return true;
 }
 // the item that holds tile t of the list (t < tile0[n]; items without tiles hold none)
-inline uint64_t streams_item_of(const uint64_t *tile0, uint64_t n, uint64_t t)
+__host__ __device__ inline uint64_t streams_item_of(const uint64_t *tile0, uint64_t n, uint64_t t)
 {
     uint64_t lo = 0, hi = n; // the last k with tile0[k] <= t
     while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (tile0[mid] <= t) lo = mid; else hi = mid; }
@@ -110,8 +110,8 @@ inline uint32_t streams_batch_tiles(uint64_t ntiles, const PlanEngine &eng, cons
 
 // What a stream's tiles [a, b) of one batch need of the batch's block-layer buffers: tokens (the carried ones, the positions the tiles parse -- a stream's
 // first tile twice as many --, the last game's overhang) and blocks
-inline uint32_t streams_tok_cap(uint32_t nt) { return (kStreamsCarry + kTileStride * (nt + 1) + kTileSlack + 3) & ~3u; }
-inline uint32_t streams_blk_cap(uint32_t nt) { return streams_tok_cap(nt) / kBlockTokens + 2; }
+__host__ __device__ inline uint32_t streams_tok_cap(uint32_t nt) { return (kStreamsCarry + kTileStride * (nt + 1) + kTileSlack + 3) & ~3u; }
+__host__ __device__ inline uint32_t streams_blk_cap(uint32_t nt) { return streams_tok_cap(nt) / kBlockTokens + 2; }
 
 // a stream's part of a batch as the device sees it: where its blocks and tokens lie in the batch's buffers (slots boff .., tokens toff ..), whose they are
 struct StreamsBlkPart { uint32_t boff, toff, item, pad; };
@@ -134,6 +134,193 @@ inline void streams_batch_needs(const uint64_t *tile0, uint64_t n, uint64_t t0, 
     for (uint64_t k = streams_item_of(tile0, n, t0); k < n && tile0[k] < t0 + nb; k++)
         if (streams_part(tile0, k, t0, nb, &pt)) { s++; t += streams_tok_cap((uint32_t)(pt.b - pt.a)); b += streams_blk_cap((uint32_t)(pt.b - pt.a)); }
     *nstreams = s; *ntok = t; *nblk = b;
+}
+
+// =====================================================================================================================================================
+// The stream-ordered call (zgpu_deflate_streams_enqueue, zgpu_deflate_streams_enqueue.hip): the host may not read the tables, so everything above that
+// streams_run decides on the host is decided on the device -- by the functions below, which the kernels of zgpu_streams_batch.hip call lane by lane and
+// tests/tools/deflate_streams_enqueue_plan_model.cpp calls in plain loops.  What the host does know is n, in_bytes and batch_tiles; it sizes by them.
+//
+// The tile count: streams_ntiles(L) <= L / kTileStride + 1 (L <= kTileH1: one tile at most; above, ceil(L / kTileStride) - 1 <= L / kTileStride), so the
+// tiles of items that do not overlap and end inside in_bytes are at most
+__host__ __device__ inline uint64_t senq_ntiles_max(uint64_t n, uint64_t in_bytes) { return in_bytes / kTileStride + n; }
+// The list never grows past that: items whose ranges overlap can ask for more, and an item with tiles whose last tile -- counted as if every item with
+// good offsets were served -- lies behind ntiles_max fails as a bad entry.  The served items with tiles are then a run from the front of the table.
+constexpr uint32_t kSenqDefaultBatch = 2048; // batch_tiles == 0: tiles of a round (about 2.2 MB of workspace each: senq_ws_plan)
+constexpr uint32_t kSenqMaxBatch = 32768;    // as streams_batch_tiles: a round's tokens are indexed with 32 bits
+constexpr uint32_t kSenqBlkPerTile = 7, kSenqTokPerTile = 81920; // streams_blk_cap(1), streams_tok_cap(1): a round's parts need at most this much per tile, whatever the parts are
+__host__ __device__ inline uint32_t senq_batch(uint64_t n, uint64_t in_bytes, uint32_t batch_tiles)
+{
+    uint64_t b = batch_tiles ? batch_tiles : kSenqDefaultBatch;
+    if (b > kSenqMaxBatch) b = kSenqMaxBatch;
+    const uint64_t m = senq_ntiles_max(n, in_bytes);
+    return (uint32_t)(m < b ? (m ? m : 1) : b);
+}
+__host__ __device__ inline uint64_t senq_rounds(uint64_t n, uint64_t in_bytes, uint32_t batch_tiles)
+{
+    const uint64_t b = senq_batch(n, in_bytes, batch_tiles);
+    return (senq_ntiles_max(n, in_bytes) + b - 1) / b;
+}
+
+// an item's state: what the table says of it
+constexpr uint32_t kSenqServed = 0, kSenqBad = 1, kSenqTooLong = 2;
+__host__ __device__ inline uint32_t senq_item_state(uint64_t lo, uint64_t hi, uint64_t in_bytes, uint64_t oa, uint64_t oz, uint64_t out_cap)
+{
+    if (hi < lo || hi > in_bytes || oz < oa || oz > out_cap || (oa & 3)) return kSenqBad;
+    return hi - lo > 0xffffffffull ? kSenqTooLong : kSenqServed;
+}
+// the tiles item k asks for
+__host__ __device__ inline uint64_t senq_item_tiles(uint32_t state, uint64_t lo, uint64_t hi) { return state == kSenqServed ? streams_ntiles(hi - lo) : 0; }
+// ... and whether it gets them: `end` = the tiles asked for by the items up to and including this one
+__host__ __device__ inline bool senq_item_fits(uint64_t nt, uint64_t end, uint64_t ntiles_max) { return nt == 0 || end <= ntiles_max; }
+// 64 KiB pieces of an item's checksums (zgpu_checksum.hip: items of at most 4096 bytes have none).  pieces <= tiles for every length, so the served items'
+// pieces are at most ntiles_max too
+__host__ __device__ inline uint64_t senq_item_pieces(uint64_t L) { return L <= 4096 ? 0 : (L + kChunkMax - 1) / kChunkMax; }
+
+// The whole scan as one loop: state[k], tile0[0..n], piece0[0..n]; returns the number of tiles.  (The kernel does the same with a workgroup's scan.)
+inline uint64_t senq_tile_scan(const uint64_t *in_off, const uint64_t *oo, uint64_t n, uint64_t in_bytes, uint64_t out_cap, uint32_t *state, uint64_t *tile0, uint64_t *piece0)
+{
+    const uint64_t m = senq_ntiles_max(n, in_bytes);
+    uint64_t asked = 0, at = 0, pc = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        uint32_t s = senq_item_state(in_off[k], in_off[k + 1], in_bytes, oo[k], oo[k + 1], out_cap);
+        const uint64_t nt = senq_item_tiles(s, in_off[k], in_off[k + 1]);
+        asked += nt;
+        if (!senq_item_fits(nt, asked, m)) s = kSenqBad;
+        state[k] = s; tile0[k] = at; piece0[k] = pc;
+        if (s == kSenqServed) { at += nt; pc += senq_item_pieces(in_off[k + 1] - in_off[k]); }
+    }
+    tile0[n] = at; piece0[n] = pc;
+    return at;
+}
+
+// A padding row: the list is laid out for ntiles_max tiles in whole rounds, and the rows behind the real tiles are tiles that parse nothing -- no bytes,
+// an empty range.  Every kernel of the chain leaves at its top for such a row; its exit row is all 0 and it has no tokens (streams_pad_kernel)
+__host__ __device__ inline TileRow streams_pad_row() { TileRow r; r.lo = 0; r.n = 0; r.h0 = 0; r.h1 = 0; r.nent = 1; r.base = 0; r.nil_local = ~0u; return r; }
+__host__ __device__ inline bool streams_row_is_pad(const TileRow &r) { return r.n == 0; } // (a real tile has at least one byte)
+// row t of the padded list
+__host__ __device__ inline TileRow senq_tile_row(const uint64_t *in_off, const uint64_t *tile0, uint64_t n, uint64_t t)
+{
+    if (n == 0 || t >= tile0[n]) return streams_pad_row();
+    const uint64_t k = streams_item_of(tile0, n, t);
+    return streams_tile_row(in_off[k], in_off[k + 1] - in_off[k], t - tile0[k]);
+}
+
+// A round = tiles [t0, t0 + batch) of the padded list, of which the first nreal are real.  Its parts as the batched block layer reads them: what
+// StreamBlocks (zgpu_deflate_streams.hip) derives on the host for one stream of a batch
+struct StreamsRoundPart {
+    uint32_t boff, toff; // where the part's blocks and tokens lie in the round's buffers (exclusive sums of the caps of the parts in front)
+    uint32_t item;       // whose tiles
+    uint32_t c0, nt;     // tiles [c0, c0 + nt) of the round
+    uint32_t ends;       // the stream's last tile is among them
+    uint32_t nblk_cap;   // streams_blk_cap(nt)
+    uint32_t j;          // the part's number in the round (its pos[] and tokoff[] run one entry longer than its blocks and tiles)
+};
+struct StreamsRound { uint32_t nparts, nreal, nslots, ntok; }; // parts, real tiles, block slots and token room in use
+__host__ __device__ inline uint32_t senq_round_real(uint64_t ntiles, uint64_t t0, uint32_t batch) { return (uint32_t)(ntiles <= t0 ? 0 : ntiles - t0 < batch ? ntiles - t0 : batch); }
+// does a part begin at tile c of the round (c < nreal)?  fills all but boff, toff and j
+__host__ __device__ inline bool senq_part_at(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t nreal, uint32_t c, StreamsRoundPart *p)
+{
+    const uint64_t t = t0 + c, k = streams_item_of(tile0, n, t);
+    if (c != 0 && tile0[k] != t) return false;
+    const uint64_t end = tile0[k + 1] < t0 + nreal ? tile0[k + 1] : t0 + nreal;
+    p->item = (uint32_t)k; p->c0 = c; p->nt = (uint32_t)(end - t); p->ends = end == tile0[k + 1] ? 1u : 0u; p->nblk_cap = streams_blk_cap(p->nt);
+    return true;
+}
+// the round's plan as one loop (the kernel: the same with a workgroup's scan over the tiles)
+inline StreamsRound senq_round_plan(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t batch, StreamsRoundPart *parts)
+{
+    StreamsRound r{0, senq_round_real(tile0[n], t0, batch), 0, 0};
+    for (uint32_t c = 0; c < r.nreal; c++) {
+        StreamsRoundPart p{};
+        if (!senq_part_at(tile0, n, t0, r.nreal, c, &p)) continue;
+        p.boff = r.nslots; p.toff = r.ntok; p.j = r.nparts;
+        parts[r.nparts++] = p;
+        r.nslots += p.nblk_cap; r.ntok += streams_tok_cap(p.nt);
+    }
+    return r;
+}
+// what the batched block layer takes from a part: the stream's own geometry (its tile numbers, its end) -- StreamBlocks' constructor
+struct StreamsPartArgs { uint64_t L, seg_end, sp; uint64_t chunk0; uint32_t final_block; };
+__host__ __device__ inline StreamsPartArgs senq_part_args(const StreamsRoundPart &p, uint64_t L, uint64_t tile0_item, uint64_t t0)
+{
+    StreamsPartArgs a;
+    a.L = L; a.seg_end = p.ends ? L : ~0ull; a.final_block = p.ends;
+    // cont_special (zgpu_cont.hip): the position 32768 k + 65274 in [L - 261, L]
+    a.sp = ~0ull;
+    if (p.ends && L >= 65274u) { const uint64_t s = (L - 65274u) / 32768u * 32768u + 65274u; if (s + 261u >= L) a.sp = s; }
+    a.chunk0 = t0 + p.c0 - tile0_item; // the stream's own number of the part's first tile
+    return a;
+}
+
+// ---- rooms without the host knowing the sizes ----
+// at least streams_layout's total for every table of n items that runs forward and ends inside in_bytes (a sum of floors is at most the floor of the
+// sum, and the total is a multiple of 4); equal to it for one item of in_bytes
+__host__ __device__ inline uint64_t senq_rooms_bound(uint64_t n, uint64_t in_bytes, uint32_t flags)
+{
+    const uint64_t s = in_bytes;
+    return (s + ((s + 7 * n) >> 3) + ((s + 63 * n) >> 6) + 5 * (s / 16383 + 2 * n) + (64 + streams_head_bytes(flags) + streams_tail_bytes(flags) + 3) * n) & ~3ull;
+}
+// the room zgpu_deflate_streams_layout_enqueue gives entry k: 0 for one that runs backwards or leaves in_bytes
+__host__ __device__ inline uint64_t senq_room(uint64_t lo, uint64_t hi, uint64_t in_bytes, uint32_t flags) { return hi < lo || hi > in_bytes ? 0 : streams_bound(hi - lo, flags); }
+
+// ---- the workspace: host arithmetic on (n, in_bytes, batch_tiles) alone ----
+struct SenqRegion { uint64_t off, bytes; };
+enum {
+    kSwCnt, kSwState, kSwTile0, kSwPiece0, kSwRows, kSwEntry, kSwSt, kSwCheck, kSwCkPart, kSwRound, kSwParts, kSwTokoff, kSwBlkItem, kSwExits, kSwComp, kSwGentry, kSwCarry,
+    kSwT, kSwBlk, kSwPos, kSwSlots, kSwTokens, kSwMeta, kSwSorted, kSwRegions
+};
+// the counters (uint64_t each, cleared by the call's first launch); the first three are streams_finish_kernel's totals
+constexpr uint32_t kScntTotal = 0, kScntTokens = 1, kScntFailed = 2, kScntBadOffsets = 3, kScntTooLong = 4;
+struct SenqWsPlan {
+    SenqRegion r[kSwRegions];
+    uint64_t ntiles_max, rounds, total; // total 0: n >= 2^32
+    uint32_t batch;
+};
+inline const char *senq_region_name(int i)
+{
+    static const char *const names[kSwRegions] = {"cnt", "state", "tile0", "piece0", "rows", "entry", "st", "check", "ckpart", "round", "parts", "tokoff", "blk_item", "exits", "comp",
+                                                  "gentry", "carry", "T", "blk", "pos", "slots", "tokens", "meta", "sorted"};
+    return i >= 0 && i < kSwRegions ? names[i] : "";
+}
+constexpr uint64_t kSenqSortedChunk = 1058832, kSenqSortedOnce = 256 + 1024; // SortedWs (zgpu_lz_sorted.h; zgpu_deflate_batch_plan.h states the same numbers)
+// What a tile of a round costs: the sorted buckets 1,058,832, its tokens 262,144, the compact tokens 327,680, seven block slots 460,544, seven blocks'
+// records 392 + 28 + 64, exits 1,044, meta, part and offsets 72 -- 2,110,800 bytes; what the call costs besides: 92 bytes an item (state, tile0, piece0,
+// its ContState, its checksums) and 46 per tile of ntiles_max (row, entry, checksum partial)
+inline SenqWsPlan senq_ws_plan(uint64_t n, uint64_t in_bytes, uint32_t batch_tiles)
+{
+    SenqWsPlan p{};
+    if (n >= (1ull << 32)) return p;
+    p.ntiles_max = senq_ntiles_max(n, in_bytes); p.batch = senq_batch(n, in_bytes, batch_tiles); p.rounds = senq_rounds(n, in_bytes, batch_tiles);
+    const uint64_t b = p.batch, nt = p.rounds * b, groups = (b + 255) / 256;
+    uint64_t off = 0;
+    auto carve = [&](int i, uint64_t bytes) { p.r[i] = SenqRegion{off, bytes}; off = (off + bytes + 255) & ~255ull; };
+    carve(kSwCnt, 256);
+    carve(kSwState, n * 4);
+    carve(kSwTile0, (n + 1) * 8);
+    carve(kSwPiece0, (n + 1) * 8);
+    carve(kSwRows, nt * sizeof(TileRow));
+    carve(kSwEntry, (nt + 2) * 2);
+    carve(kSwSt, n * sizeof(ContState));
+    carve(kSwCheck, n * 8);
+    carve(kSwCkPart, p.ntiles_max * 12);
+    carve(kSwRound, 256);
+    carve(kSwParts, b * sizeof(StreamsRoundPart));
+    carve(kSwTokoff, (2 * b + 1) * 4);
+    carve(kSwBlkItem, kSenqBlkPerTile * b * 4);
+    carve(kSwExits, b * kTileExitStride * 2);
+    carve(kSwComp, groups * kTileExitStride * 2);
+    carve(kSwGentry, (groups + 1) * 2);
+    carve(kSwCarry, (uint64_t)kStreamsCarry * 4);
+    carve(kSwT, b * kSenqTokPerTile * 4);
+    carve(kSwBlk, kSenqBlkPerTile * b * sizeof(ContBlk));
+    carve(kSwPos, (kSenqBlkPerTile * b + b + 1) * 8);
+    carve(kSwSlots, kSenqBlkPerTile * b * kSlotStride);
+    carve(kSwTokens, b * kChunkMax * 4);
+    carve(kSwMeta, b * sizeof(ChunkMeta));
+    carve(kSwSorted, kSenqSortedOnce + b * kSenqSortedChunk);
+    p.total = off;
+    return p;
 }
 
 } // namespace zgpu

@@ -158,6 +158,9 @@ int write_trailer(zgpu_engine *e, bool gz, uint32_t adler, uint32_t crc, uint64_
 struct PlanEngine; // zgpu_deflate_plan.h
 PlanEngine plan_engine(const zgpu_engine *e, const LevelCfg *cfg);
 
+// ---- zgpu_deflate_streams.hip ----
+const char *streams_refuse(const zgpu_engine *e, const zgpu_deflate_params *p); // why the batch compress of many streams does not serve these parameters, nullptr: it does
+
 // ---- zgpu_deflate_cont.hip ----
 int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const zgpu_deflate_params *p, uint8_t *d_out, uint64_t out_cap, zgpu_deflate_result *res, hipStream_t st);
 
@@ -230,6 +233,19 @@ void launch_cont_tokens(const ChunkGeom &g, const TileGeom &tg, const uint32_t *
 void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const uint8_t *slots, uint32_t slot_stride, const uint8_t *in, uint64_t abs0, uint8_t *out, uint64_t out_cap,
                         uint32_t nblk_cap, const uint32_t *T, uint32_t *carry, uint64_t seg_end, hipStream_t s);
 
+// the batched block layer: one round of a stream-ordered call over many streams (zgpu_deflate_streams_enqueue.hip), everything in device memory
+struct StreamsRoundPart; struct StreamsRound; // zgpu_deflate_streams_plan.h
+struct ContBatch {
+    const StreamsRoundPart *parts; const StreamsRound *round; // the round's parts and their number, made on the device
+    const uint64_t *in_off, *oo, *tile0; uint64_t t0;          // the caller's tables, the tiles in front of every item, the round's first tile in the list
+    const uint8_t *in; uint8_t *out; uint32_t flags, slow, nslots_max;
+    ContState *st; const uint16_t *entry;                      // per item; per tile of the list
+    const uint32_t *tokens; const ChunkMeta *tmeta;            // per tile of the round
+    uint32_t *tokoff, *carry, *T; ContBlk *blk; uint64_t *pos; const uint8_t *slots; uint32_t *blk_item;
+};
+void launch_cont_batch_tokens(const ContBatch &q, uint32_t batch, hipStream_t s);
+void launch_cont_batch_stitch(const ContBatch &q, uint32_t batch, hipStream_t s);
+
 // ---- zgpu_streams.hip ----
 void launch_streams_head(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out, uint16_t *entry0,
                          unsigned long long *totals, hipStream_t s);
@@ -239,6 +255,22 @@ void launch_streams_blocks(const StreamsBlkPart *parts, uint32_t nparts, uint32_
 void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st, const zgpu_check_item *chk, bool want_crc,
                            uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s);
 void launch_streams_pack(const uint8_t *rooms, const uint64_t *oo, const uint64_t *po, uint64_t n, uint64_t total, uint8_t *packed, hipStream_t s);
+// ... of the stream-ordered call: state[k] != 0 marks an item the device's table check has failed
+void launch_streams_head_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out,
+                               uint16_t *entry0, hipStream_t s);
+void launch_streams_finish_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st,
+                                 const zgpu_check_item *chk, bool want_crc, uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *cnt, hipStream_t s);
+
+// ---- zgpu_streams_batch.hip: the stream-ordered call's plan, made on the device ----
+void launch_senq_clear(unsigned long long *cnt, uint32_t *fault, zgpu_deflate_batch_summary *summary, hipStream_t s);
+void launch_senq_scan(const uint64_t *in_off, const uint64_t *oo, uint64_t n, uint64_t in_bytes, uint64_t out_cap, uint32_t *state, uint64_t *tile0, uint64_t *piece0,
+                      unsigned long long *cnt, hipStream_t s);
+void launch_senq_rows(const uint64_t *in_off, const uint64_t *tile0, uint64_t n, uint64_t nrows, TileRow *rows, hipStream_t s);
+// a round's parts and their number; the exit rows and records of its padding rows (rows, exits, meta: the round's)
+void launch_senq_round(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t batch, const TileRow *rows, StreamsRoundPart *parts, StreamsRound *round, uint16_t *exits, ChunkMeta *meta,
+                       hipStream_t s);
+void launch_senq_layout(const uint64_t *in_off, uint64_t n, uint64_t in_bytes, uint32_t flags, uint64_t *oo, hipStream_t s);
+void launch_senq_summary(const uint32_t *fault, uint64_t n, const unsigned long long *cnt, zgpu_deflate_batch_item *items, zgpu_deflate_batch_summary *summary, hipStream_t s);
 
 // ---- zgpu_inflate.hip ----
 // One launch of the decoder, inflate_kernel_t: segments [chunk0, chunk0 + nchunks) of `offsets`, one workgroup each, records to status[0, nchunks).  The
@@ -278,5 +310,7 @@ int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
 
 // ---- zgpu_checksum.hip ----
 int checksum_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_off, uint64_t n, uint32_t checks, zgpu_check_item *d_items, hipStream_t st);
+void checksum_batch_enqueue(const uint8_t *d_in, const uint64_t *d_off, const uint32_t *state, const uint64_t *piece0, uint64_t n, uint64_t npieces_max, uint32_t checks, void *part,
+                            zgpu_check_item *d_items, hipStream_t st);
 
 } // namespace zgpu

@@ -13,6 +13,7 @@
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t lo; uint32_t n;
     chunk_span<ROWS>(g, c, lo, n);
+    if constexpr (ROWS) { if (n == 0) return; } // a padding row (zgpu_deflate_streams_plan.h, streams_pad_row): a tile that parses nothing; no barrier, no LDS use above
     ParseCtx cx;
     cx.rec = LITE ? nullptr : recs + (size_t)c * kChunkMax;
     const uint32_t *gmv = LITE ? gmv_all + (size_t)c * kChunkMax : nullptr, *gsv = LITE ? gsv_all + (size_t)c * kP2Words : nullptr;

@@ -56,6 +56,7 @@ __global__ void __launch_bounds__(kSortThreads) sort_kernel(ChunkGeom g, uint16_
     __shared__ __attribute__((aligned(16))) uint16_t out_stage[kSuperS];
     __shared__ uint8_t tag[4096];
     __shared__ uint32_t wave_tot[kSortWaves];
+    if constexpr (ROWS) { if (g.rows[blockIdx.x].n == 0) return; } // a padding row (zgpu_deflate_streams_plan.h, streams_pad_row): a tile that parses nothing
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t lo; uint32_t n;
     chunk_span<ROWS>(g, c, lo, n);
@@ -248,6 +249,7 @@ __global__ void __launch_bounds__(kS4Threads) sort4_kernel(ChunkGeom g, uint16_t
     __shared__ uint32_t wave_tot[kS4Waves];
     __shared__ uint32_t token;
     __shared__ __attribute__((aligned(8))) uint32_t heads[kChunkMax / 32]; // bit i: S[i] is the first entry of its bucket
+    if constexpr (ROWS) { if (g.rows[blockIdx.x].n == 0) return; } // a padding row (zgpu_deflate_streams_plan.h, streams_pad_row): a tile that parses nothing
     const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     S_T0();
     uint64_t lo; uint32_t n;

@@ -269,6 +269,7 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
     constexpr bool FUSE = MODE == 1, TILE = MODE >= 2, ROWS = MODE == 3;
     static_assert(!FUSE || kWNeuShift == 0, "a log holds kP2Win games: a position must start one game at most, so every neutral position is claimed");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    if constexpr (ROWS) { if (g.rows[blockIdx.x].n == 0) return; } // a padding row (zgpu_deflate_streams_plan.h, streams_pad_row): a tile that parses nothing
     uint32_t *d32 = lds;
     uint32_t *ctrl = lds + kM3DataLds / 4; // [0]: next block to hand out
     uint32_t *NEU = ctrl + 4;              // bit p: some walker stands, or stood, at p with nothing in hand

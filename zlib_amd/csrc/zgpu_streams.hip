@@ -17,12 +17,9 @@ struct StreamsHead {
 };
 
 // item k's state and header.  A room that cannot hold the smallest stream: overflow from the start, nothing written
-__global__ void __launch_bounds__(256) streams_head_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, uint64_t n, StreamsHead h, ContState *__restrict__ st,
-                                                           uint8_t *__restrict__ out, uint16_t *__restrict__ entry0, unsigned long long *__restrict__ totals)
+__device__ __forceinline__ void streams_head_item(uint64_t k, const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const StreamsHead &h, ContState *__restrict__ st,
+                                                  uint8_t *__restrict__ out)
 {
-    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k == 0) { *entry0 = 0; totals[0] = 0; totals[1] = 0; totals[2] = 0; }
-    if (k >= n) return;
     const uint64_t L = in_off[k + 1] - in_off[k], room = oo[k + 1] - oo[k];
     ContState s{};
     s.out_bits = h.head_bits; s.data_type = 2; s.last_eob = 8; s.first_block = 1;
@@ -33,6 +30,25 @@ __global__ void __launch_bounds__(256) streams_head_kernel(const uint64_t *__res
     } else if (streams_room_cap(room, h.flags) == 0) s.overflow = 1;
     else for (uint32_t i = 0; i < h.head_words; i++) w[i] = h.head[i];
     st[k] = s;
+}
+__global__ void __launch_bounds__(256) streams_head_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, uint64_t n, StreamsHead h, ContState *__restrict__ st,
+                                                           uint8_t *__restrict__ out, uint16_t *__restrict__ entry0, unsigned long long *__restrict__ totals)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k == 0) { *entry0 = 0; totals[0] = 0; totals[1] = 0; totals[2] = 0; }
+    if (k >= n) return;
+    streams_head_item(k, in_off, oo, h, st, out);
+}
+// the stream-ordered call (zgpu_deflate_streams_enqueue.hip): the same for the items the device's table check serves (state 0); a failed item gets a state
+// that says nothing and writes nothing.  The counters are cleared by the launch in front
+__global__ void __launch_bounds__(256) streams_head_state_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const uint32_t *__restrict__ state, uint64_t n,
+                                                                 StreamsHead h, ContState *__restrict__ st, uint8_t *__restrict__ out, uint16_t *__restrict__ entry0)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k == 0) *entry0 = 0;
+    if (k >= n) return;
+    if (state[k] != kSenqServed) { ContState s{}; s.data_type = 2; st[k] = s; return; }
+    streams_head_item(k, in_off, oo, h, st, out);
 }
 
 // a stream's first tile is entered at 0: the chain over the launch's tiles has left the exit of the tile in front there
@@ -57,12 +73,10 @@ __global__ void __launch_bounds__(256) streams_blocks_kernel(const StreamsBlkPar
 }
 
 // item k's trailer and record; totals: [0] bytes of all streams, [1] tokens, [2] records that are not ZGPU_OK
-__global__ void __launch_bounds__(256) streams_finish_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, uint64_t n, StreamsHead h, const ContState *__restrict__ st,
-                                                             const zgpu_check_item *__restrict__ chk, uint32_t want_crc, uint8_t *__restrict__ out,
-                                                             zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ totals)
+__device__ __forceinline__ void streams_finish_item(uint64_t k, const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const StreamsHead &h, const ContState *__restrict__ st,
+                                                    const zgpu_check_item *__restrict__ chk, uint32_t want_crc, uint8_t *__restrict__ out,
+                                                    zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ totals)
 {
-    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
     const uint64_t L = in_off[k + 1] - in_off[k];
     const ContState s = st[k];
     zgpu_deflate_batch_item it{};
@@ -84,6 +98,30 @@ __global__ void __launch_bounds__(256) streams_finish_kernel(const uint64_t *__r
     }
     atomicAdd(&totals[1], (unsigned long long)s.ntokens);
     items[k] = it;
+}
+__global__ void __launch_bounds__(256) streams_finish_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, uint64_t n, StreamsHead h, const ContState *__restrict__ st,
+                                                             const zgpu_check_item *__restrict__ chk, uint32_t want_crc, uint8_t *__restrict__ out,
+                                                             zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ totals)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    streams_finish_item(k, in_off, oo, h, st, chk, want_crc, out, items, totals);
+}
+// the stream-ordered call: a failed item's record is the failed record of the other enqueue calls -- it has read nothing and written nothing
+__global__ void __launch_bounds__(256) streams_finish_state_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const uint32_t *__restrict__ state, uint64_t n,
+                                                                   StreamsHead h, const ContState *__restrict__ st, const zgpu_check_item *__restrict__ chk, uint32_t want_crc,
+                                                                   uint8_t *__restrict__ out, zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ cnt)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    if (state[k] != kSenqServed) {
+        zgpu_deflate_batch_item r{};
+        r.code = ZGPU_STREAM_ERROR; r.data_type = 2; r.adler32 = 1;
+        items[k] = r;
+        atomicAdd(&cnt[kScntFailed], 1ull);
+        return;
+    }
+    streams_finish_item(k, in_off, oo, h, st, chk, want_crc, out, items, cnt);
 }
 
 // the host entry's packing: the streams out of their rooms, back to back.  A workgroup fills 4096 bytes of the packed output, a lane 16 of them
@@ -144,6 +182,17 @@ void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, uint64_t 
                            uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s)
 {
     hipLaunchKernelGGL(streams_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, n, make_head(fh, flags), st, chk, want_crc ? 1u : 0u, out, items, totals);
+}
+void launch_streams_head_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out,
+                               uint16_t *entry0, hipStream_t s)
+{
+    hipLaunchKernelGGL(streams_head_state_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, state, n, make_head(fh, flags), st, out, entry0);
+}
+void launch_streams_finish_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st,
+                                 const zgpu_check_item *chk, bool want_crc, uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *cnt, hipStream_t s)
+{
+    hipLaunchKernelGGL(streams_finish_state_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, state, n, make_head(fh, flags), st, chk, want_crc ? 1u : 0u, out,
+                       items, cnt);
 }
 void launch_streams_pack(const uint8_t *rooms, const uint64_t *oo, const uint64_t *po, uint64_t n, uint64_t total, uint8_t *packed, hipStream_t s)
 {

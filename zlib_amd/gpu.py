@@ -131,6 +131,12 @@ def load_library():
     L.zgpu_deflate_streams_layout.argtypes = [vp, u64, u32, vp, C.POINTER(u64)]
     L.zgpu_deflate_streams_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, C.POINTER(DeflateResult), vp]
     L.zgpu_deflate_streams_host.argtypes = [vp, vp, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, C.POINTER(DeflateResult)]
+    L.zgpu_deflate_streams_workspace_bytes.argtypes = [u64, u64, u32]
+    L.zgpu_deflate_streams_workspace_bytes.restype = u64
+    L.zgpu_deflate_streams_rooms_bound.argtypes = [u64, u64, u32]
+    L.zgpu_deflate_streams_rooms_bound.restype = u64
+    L.zgpu_deflate_streams_layout_enqueue.argtypes = [vp, vp, u64, u64, u32, vp, vp]
+    L.zgpu_deflate_streams_enqueue.argtypes = [vp, vp, u64, vp, u64, C.POINTER(_Params), vp, u64, vp, vp, vp, vp, u64, u32, vp]
     L.zgpu_engine_set_exact_sort.argtypes = [vp, C.c_int]
     L.zgpu_debug_sort_fallback.argtypes = [vp]
     L.zgpu_checksum_batch_host.argtypes = [vp, vp, u64, vp, u64, u32, vp]
@@ -576,6 +582,28 @@ class Engine:
         p = _Params(level, 0, flags, lz_impl, strategy, prime)
         self._check(self.L.zgpu_deflate_batch_packed_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, C.byref(p), d_out, out_cap, d_out_offsets, d_items, d_summary, d_ws,
                                                              ws_bytes, batch_items, stream))
+
+    # ---- stream-ordered batch compress of items of any length ----
+    def deflate_streams_workspace_bytes(self, n, in_bytes, batch_tiles=0):
+        """Bytes of caller-owned device workspace a zgpu_deflate_streams_enqueue call needs: a function of n, in_bytes and batch_tiles (0: 2048 tiles a round) alone."""
+        return int(self.L.zgpu_deflate_streams_workspace_bytes(n, in_bytes, batch_tiles))
+
+    def deflate_streams_rooms_bound(self, n, in_bytes, flags):
+        """An out_cap that holds the rooms of every table of n items that runs forward and ends inside in_bytes (closed form, no table needed)."""
+        return int(self.L.zgpu_deflate_streams_rooms_bound(n, in_bytes, flags))
+
+    def deflate_streams_layout_enqueue(self, d_in_offsets, n, in_bytes, flags, d_out_offsets, stream=None):
+        """Enqueues the rooms' table: d_out_offsets receives n + 1 uint64, what deflate_streams_layout gives a good table; a bad entry gets a room of 0."""
+        self._check(self.L.zgpu_deflate_streams_layout_enqueue(self.h, d_in_offsets, n, in_bytes, flags, d_out_offsets, stream))
+
+    def deflate_streams_enqueue(self, d_in, in_bytes, d_in_offsets, n, level, d_out, out_cap, d_out_offsets, d_items, d_ws, ws_bytes, flags=F_FINAL, strategy=0, batch_tiles=0,
+                                d_summary=None, stream=None, lz_impl=LZ_AUTO, prime=0):
+        """Device pointers as ints.  Item k = d_in[io[k], io[k+1]), of any length, becomes the stream deflate_streams_device gives it, in its room d_out[oo[k], oo[k+1]);
+        d_items: room for n DeflateBatchItem, d_ws: 256-byte aligned workspace of deflate_streams_workspace_bytes(n, in_bytes, batch_tiles), d_summary: room for a
+        DeflateBatchSummary or None.  Enqueues on `stream` (an int; None: the engine's) and returns: nothing is read back."""
+        p = _Params(level, 0, flags, lz_impl, strategy, prime)
+        self._check(self.L.zgpu_deflate_streams_enqueue(self.h, d_in, in_bytes, d_in_offsets, n, C.byref(p), d_out, out_cap, d_out_offsets, d_items, d_summary, d_ws, ws_bytes,
+                                                        batch_tiles, stream))
 
     def set_exact_sort(self, on):
         """on: the engine's calls sort with the ballot-ranked sort (what a caller does after a batch's summary said sort_fault); off: the fast sort again."""
