@@ -1,8 +1,9 @@
 """What the stream-ordered batch compress of items of any length decides from plain numbers (zlib_amd/csrc/zgpu_deflate_streams_plan.h, the part behind
 "the stream-ordered call"): the host's upper bound of the tiles, the workspace, the rooms' bound, and the plan the DEVICE makes from the caller's tables --
 item states, the tiles and checksum pieces in front of every item, the rows of the padded tile list, the parts of every round.  The kernels call these
-functions lane by lane; tests/tools/deflate_streams_enqueue_plan_model.cpp calls them in loops and compares them with the host plan of the blocking call
-(streams_tile_scan, streams_tile_row, streams_part, streams_batch_needs).  No GPU is used.  The model is built twice, once with ASan + UBSan."""
+functions lane by lane; tests/tools/deflate_streams_enqueue_plan_model.cpp calls them in loops and compares the device's judgement of the tables with the
+host's (streams_tile_scan, streams_tile_row) and the round plan both calls share (streams_round_plan, streams_part_args) with a derivation by brute force
+written out in the tool.  No GPU is used.  The model is built twice, once with ASan + UBSan."""
 import os
 import random
 import subprocess
@@ -137,10 +138,28 @@ def test_scan_of_explicit_tables(model):
     assert (got[6]["states"], got[6]["tile0"], got[6]["piece0"]) == ("0,0,0,0,0", "0,0,1,2,4,%d" % (4 + ntiles(130367)), "0,0,0,0,1,3")
 
 
+# (batch, seed, count): tables, tiles, rounds, parts, open_parts, pad_rows -- what the tool printed of these tables while the blocking call still had a
+# part arithmetic of its own, which was the other side of the comparison then; the brute-force derivation must walk the very same tables and parts
+PLAN_COUNTS = {
+    (1, 12, 400): (400, 16548, 21697, 16548, 12659, 5149),
+    (2, 13, 400): (400, 17251, 11291, 10578, 6625, 5325),
+    (3, 14, 400): (400, 17875, 7827, 8606, 4547, 5582),
+    (7, 18, 400): (400, 19103, 3676, 6171, 2048, 6558),
+    (64, 75, 400): (400, 19098, 606, 4232, 97, 12149),
+    (3, 5, 150): (150, 6764, 2958, 3239, 1707, 2109),
+    (64, 6, 150): (150, 7073, 227, 1661, 38, 4616),
+}
+
+
+def plan_counts(d):
+    return tuple(int(d[k]) for k in ("tables", "tiles", "rounds", "parts", "open_parts", "pad_rows"))
+
+
 @pytest.mark.parametrize("batch", [1, 2, 3, 7, 64])
 def test_device_plan_equals_the_host_plan(model, batch):
     d = kv(model(["plan %d %d 400" % (batch, 11 + batch)])[0])
     assert int(d["mismatches"]) == 0, d
+    assert plan_counts(d) == PLAN_COUNTS[(batch, 11 + batch, 400)], d
     assert int(d["tables"]) == 400 and int(d["parts"]) > 400 and int(d["pad_rows"]) > 0, d
     if batch < 64:
         assert int(d["open_parts"]) > 0, d  # rounds that end inside streams
@@ -158,3 +177,4 @@ def test_model_under_the_sanitizers(model):
     plain, san = model(rows), model(rows, san=True)
     assert plain == san
     assert all(int(kv(x)["mismatches"]) == 0 for x in san[:3])
+    assert plan_counts(kv(san[0])) == PLAN_COUNTS[(3, 5, 150)] and plan_counts(kv(san[1])) == PLAN_COUNTS[(64, 6, 150)]

@@ -141,6 +141,22 @@ def test_batch_ends_inside_streams(eng, monkeypatch, tiles):
         assert z == want(6, "raw", 0)
 
 
+@pytest.mark.parametrize("tiles", [None, "259", "260"])
+def test_a_part_longer_than_the_scans_lanes(eng, monkeypatch, tiles):
+    """3b. an item of 301 tiles and some 370 blocks among short ones (tests/streams_long_fixtures.py): the batched scans' 256 lanes take runs of tiles and
+    of blocks.  One batch (a part of 301 tiles), batches of 259 (the long item's first part: 256 tiles) and of 260 (257).  Every item is the product's
+    one-call continuous stream of that item, every record ZGPU_OK with zlib's adler32, and zlib gives the item back"""
+    import streams_long_fixtures as LF
+    LF.one_call_streams(eng)  # (made with the knob unset or not: the one-stream path does not read the streams' parts)
+    if tiles is None:
+        monkeypatch.delenv("ZGPU_CONT_BATCH_TILES", raising=False)
+    else:
+        monkeypatch.setenv("ZGPU_CONT_BATCH_TILES", tiles)
+    z, recs = eng.deflate_streams_host(list(LF.items()), 6, wrap="zlib", want_items=True)
+    assert eng.last.nchunks == 307
+    LF.check(z, [(r.code, r.adler32) for r in recs])
+
+
 def catalogue_rows():
     return [c for c in BC.catalogue() if not c.calls and c.level >= 4]
 

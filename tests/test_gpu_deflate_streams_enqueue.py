@@ -194,6 +194,20 @@ def test_rounds_give_the_same_bytes(eng, batch_tiles):
     run(eng, ITEMS, 6, WRAP_FLAGS["gzip"], batch_tiles=batch_tiles)
 
 
+@pytest.mark.parametrize("batch_tiles", [0, 259, 260])
+def test_a_part_longer_than_the_scans_lanes(eng, batch_tiles):
+    """2b. an item of 301 tiles and some 370 blocks among short ones (tests/streams_long_fixtures.py): the batched scans' 256 lanes take runs of tiles and
+    of blocks.  One round (a part of 301 tiles), rounds of 259 (the long item's first part: 256 tiles) and of 260 (257).  Every item is the product's
+    one-call continuous stream of that item, every record ZGPU_OK with zlib's adler32, and zlib gives the item back"""
+    import streams_long_fixtures as LF
+    LF.one_call_streams(eng)
+    d = Dev(eng, list(LF.items()), WRAP_FLAGS["zlib"], batch_tiles=batch_tiles)
+    d.enqueue(6)
+    recs, summary, out = d.results()
+    assert summary[:3] == (0, 0, 0) and summary[4:] == (0, 0), summary
+    LF.check([out[d.oo[k]: d.oo[k] + recs[k][3]].tobytes() for k in range(d.n)], [(r[0], r[5]) for r in recs])
+
+
 @pytest.mark.parametrize("batch_tiles", [0, 1])
 def test_block_catalogue_as_one_call(eng, batch_tiles):
     """3. the rows test_block_catalogue_as_one_batch selects, grouped by (level, strategy, wbits), one enqueue per group: (len, sha) of tests/golden/block_kat.json"""

@@ -6,9 +6,10 @@
 //                                 needs: parts, tokoff, blk_item, T, blk, pos, slots (bytes)
 //   "rooms FLAGS IN_BYTES L0 .."  senq_rooms_bound(n, IN_BYTES, FLAGS) and streams_layout's total for items of these lengths
 //   "scan IN_BYTES OUT_CAP IO0 .. / OO0 .."   senq_tile_scan of an explicit table: states, tile0, piece0
-//   "plan BATCH SEED COUNT"       COUNT random good tables (empty items, one-tile items, long ones): the device plan against the host plan of zgpu_deflate_streams.hip --
-//                                 senq_tile_scan against streams_tile_scan, senq_tile_row against streams_tile_row (and padding rows behind), senq_round_plan against
-//                                 streams_part and streams_batch_needs, senq_part_args against what StreamBlocks derives; prints what was compared and the mismatches
+//   "plan BATCH SEED COUNT"       COUNT random good tables (empty items, one-tile items, long ones): the device's judgement of the tables against the host's -- senq_tile_scan
+//                                 against streams_tile_scan, senq_tile_row against streams_tile_row (and padding rows behind) -- and the round plan both calls share
+//                                 (streams_round_plan, streams_part_args) against a derivation by brute force written out here: the round's tiles one by one, each tile's
+//                                 item by a linear walk, runs of one item grouped into parts, the caps as numbers; prints what was compared and the mismatches
 //   "overlap SEED COUNT"          COUNT random tables whose ranges overlap or run backwards, rooms bad here and there: the tiles and pieces of the served stay within
 //                                 ntiles_max, a failed item has none, the states are senq_item_state's or bad by the list's cap
 // Built for the host only (tests/test_deflate_streams_enqueue_plan_cpu.py); no HIP call is made.
@@ -39,6 +40,16 @@ static uint64_t random_len()
 }
 
 static bool row_eq(const TileRow &a, const TileRow &b) { return a.lo == b.lo && a.n == b.n && a.h0 == b.h0 && a.h1 == b.h1 && a.nent == b.nent && a.base == b.base && a.nil_local == b.nil_local; }
+
+// the round plan by brute force, with nothing of the header's round plan in it
+struct BrutePart { uint64_t item, a, b; }; // tiles [a, b) of the list belong to `item`
+static uint64_t brute_item_of(const std::vector<uint64_t> &tile0, uint64_t n, uint64_t t)
+{
+    for (uint64_t k = 0; k < n; k++) if (tile0[k] <= t && t < tile0[k + 1]) return k;
+    return n;
+}
+static uint64_t brute_tok_cap(uint64_t nt) { return (16384 + 32512 * (nt + 1) + 512 + 3) & ~3ull; }
+static uint64_t brute_blk_cap(uint64_t nt) { return brute_tok_cap(nt) / 16383 + 2; }
 
 static void plan(uint32_t batch, uint64_t seed, uint64_t count)
 {
@@ -71,32 +82,37 @@ static void plan(uint32_t batch, uint64_t seed, uint64_t count)
         std::vector<StreamsRoundPart> rp(b);
         for (uint64_t r = 0; r < nr; r++) {
             const uint64_t t0 = r * b;
-            const StreamsRound rd = senq_round_plan(tile0.data(), n, t0, (uint32_t)b, rp.data());
+            const StreamsRound rd = streams_round_plan(tile0.data(), n, t0, (uint32_t)b, rp.data());
             rounds++;
             const uint32_t nb = (uint32_t)(nt <= t0 ? 0 : nt - t0 < b ? nt - t0 : b);
             if (rd.nreal != nb) bad++;
             if (nb == 0) { if (rd.nparts || rd.nslots || rd.ntok) bad++; continue; }
-            uint64_t s, t, bl;
-            streams_batch_needs(h_tile0.data(), n, t0, nb, &s, &t, &bl);
-            if (s != rd.nparts || t != rd.ntok || bl != rd.nslots) bad++;
+            std::vector<BrutePart> bp;
+            for (uint64_t t = t0; t < t0 + nb; t++) {
+                const uint64_t k = brute_item_of(h_tile0, n, t);
+                if (!bp.empty() && bp.back().item == k) bp.back().b = t + 1; else bp.push_back(BrutePart{k, t, t + 1});
+            }
+            uint64_t t = 0, bl = 0;
+            for (const BrutePart &pt : bp) { t += brute_tok_cap(pt.b - pt.a); bl += brute_blk_cap(pt.b - pt.a); }
+            if (bp.size() != rd.nparts || t != rd.ntok || bl != rd.nslots) bad++;
             if (rd.nslots > (uint64_t)kSenqBlkPerTile * nb || rd.ntok > (uint64_t)kSenqTokPerTile * nb || rd.nparts > nb) bad++;
             uint32_t j = 0; uint64_t toff = 0, boff = 0;
-            StreamsPart pt;
-            for (uint64_t k = streams_item_of(h_tile0.data(), n, t0); k < n && h_tile0[k] < t0 + nb; k++) {
-                if (!streams_part(h_tile0.data(), k, t0, nb, &pt)) continue;
+            for (const BrutePart &pt : bp) {
                 if (j >= rd.nparts) { bad++; break; }
+                const uint64_t k = pt.item;
+                const bool ends = pt.b == h_tile0[k + 1];
                 const StreamsRoundPart &p = rp[j];
                 const uint32_t pnt = (uint32_t)(pt.b - pt.a);
                 parts++;
-                if (!pt.ends) mid++;
-                if (p.item != k || p.c0 != pt.a - t0 || p.nt != pnt || (p.ends != 0) != pt.ends || p.boff != boff || p.toff != toff || p.j != j || p.nblk_cap != streams_blk_cap(pnt)) bad++;
-                // StreamBlocks (zgpu_deflate_streams.hip): L, seg_here, the stream's own number of the part's first tile, the special position
+                if (!ends) mid++;
+                if (p.item != k || p.c0 != pt.a - t0 || p.nt != pnt || (p.ends != 0) != ends || p.boff != boff || p.toff != toff || p.j != j || p.nblk_cap != brute_blk_cap(pnt)) bad++;
+                // what a one-stream launch gets from the host: L, the segment's end, the stream's own number of the part's first tile, the special position
                 const uint64_t L = io[k + 1] - io[k];
-                const StreamsPartArgs a = senq_part_args(p, L, tile0[k], t0);
+                const StreamsPartArgs a = streams_part_args(p, L, tile0[k], t0);
                 uint64_t sp = ~0ull;
-                if (pt.ends && L >= 65274u) { const uint64_t q = (L - 65274u) / 32768u * 32768u + 65274u; if (q + 261u >= L) sp = q; } // cont_special (zgpu_cont.hip)
-                if (a.L != L || a.seg_end != (pt.ends ? L : ~0ull) || a.chunk0 != pt.a - h_tile0[k] || a.final_block != (pt.ends ? 1u : 0u) || a.sp != sp) bad++;
-                toff += streams_tok_cap(pnt); boff += streams_blk_cap(pnt); j++;
+                if (ends && L >= 65274u) { const uint64_t q = (L - 65274u) / 32768u * 32768u + 65274u; if (q + 261u >= L) sp = q; } // the position 32768 k + 65274 in [L - 261, L]
+                if (a.L != L || a.seg_end != (ends ? L : ~0ull) || a.chunk0 != pt.a - h_tile0[k] || a.final_block != (ends ? 1u : 0u) || a.sp != sp) bad++;
+                toff += brute_tok_cap(pnt); boff += brute_blk_cap(pnt); j++;
             }
             if (j != rd.nparts) bad++;
         }

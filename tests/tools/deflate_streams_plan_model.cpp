@@ -4,8 +4,8 @@
 //                               (streams_tile_row at buffer offset 1000) differs from what tile_span gives that feed's tile -- window start, window length, h0,
 //                               h1, entries -- or whose base / nil_local differ from the walkers' own arithmetic, and the first and the last row
 //   "layout FLAGS L0 L1 ..."    the rooms of items of these lengths: out_offsets, the total, the bound of each item
-//   "batches BATCH L0 L1 ..."   the tiles of these items in batches of BATCH: per batch the parts item:a-b (a '.' behind a part whose stream ends there) and the
-//                               block layer's needs streams/tokens/blocks
+//   "batches BATCH L0 L1 ..."   the tiles of these items in batches of BATCH, by the round plan (streams_round_plan): per batch the parts item:a-b in tiles of
+//                               the list (a '.' behind a part whose stream ends there) and the block layer's needs parts/tokens/block slots
 // Built for the host only (tests/test_deflate_streams_plan_cpu.py); no HIP call is made.
 #include "../../zlib_amd/csrc/zgpu_deflate_streams_plan.h"
 #include <cstdio>
@@ -78,15 +78,13 @@ int main(int argc, char **argv)
             for (uint64_t k = 0; k < n; k++) off[k + 1] = off[k] + v[k + 1];
             const bool ok = streams_tile_scan(off.data(), n, tile0.data());
             printf("ok=%d ntiles=%llu", ok ? 1 : 0, (unsigned long long)tile0[n]);
-            for (uint64_t t0 = 0; ok && t0 < tile0[n]; t0 += batch) {
-                const uint32_t nb = (uint32_t)(tile0[n] - t0 < batch ? tile0[n] - t0 : batch);
+            std::vector<StreamsRoundPart> parts((size_t)(tile0[n] < batch ? tile0[n] : batch) + 1); // (a part per tile at the most)
+            for (uint64_t t0 = 0; ok && batch && t0 < tile0[n]; t0 += batch) {
+                const StreamsRound rd = streams_round_plan(tile0.data(), n, t0, batch, parts.data());
                 printf(" |");
-                StreamsPart pt;
-                for (uint64_t k = streams_item_of(tile0.data(), n, t0); k < n && tile0[k] < t0 + nb; k++)
-                    if (streams_part(tile0.data(), k, t0, nb, &pt)) printf(" %llu:%llu-%llu%s", (unsigned long long)pt.item, (unsigned long long)pt.a, (unsigned long long)pt.b, pt.ends ? "." : "");
-                uint64_t s, t, b;
-                streams_batch_needs(tile0.data(), n, t0, nb, &s, &t, &b);
-                printf(" needs=%llu/%llu/%llu", (unsigned long long)s, (unsigned long long)t, (unsigned long long)b);
+                for (uint32_t j = 0; j < rd.nparts; j++)
+                    printf(" %u:%llu-%llu%s", parts[j].item, (unsigned long long)(t0 + parts[j].c0), (unsigned long long)(t0 + parts[j].c0 + parts[j].nt), parts[j].ends ? "." : "");
+                printf(" needs=%u/%u/%u", rd.nparts, rd.ntok, rd.nslots);
             }
             printf("\n");
         } else { fprintf(stderr, "bad row: %s\n", argv[a]); return 2; }

@@ -99,13 +99,7 @@ __host__ __device__ inline uint64_t cont_slides(uint64_t ptop, uint64_t sp)
 {
     return (ptop >= 65275u ? (ptop - 65275u) / 32768u + 1u : 0u) + (ptop == sp ? 1u : 0u);
 }
-// sp for a segment that ends at stream position n: the position 32768 k + 65274 in [n - 261, n], ~0 if there is none
-__host__ __device__ inline uint64_t cont_special(uint64_t n)
-{
-    if (n < 65274u) return ~0ull;
-    const uint64_t sp = (n - 65274u) / 32768u * 32768u + 65274u;
-    return sp + 261u >= n ? sp : ~0ull;
-}
+// (sp for a segment that ends at stream position n: cont_special, zgpu_deflate_plan.h)
 
 // the batch's blocks.  seg_end: the stream position the segment ends at when this batch reaches it (the block that is filling is closed there), ~0: more follows
 // b: the block slot of the stream; true: it holds a block of this batch
@@ -229,12 +223,14 @@ __global__ void __launch_bounds__(1024) cont_carry_kernel(const ContBlk *__restr
 }
 
 // ------------------------------------------------------------------------------------------------- the block layer of MANY streams, batched
-// The stream-ordered batch call (zgpu_deflate_streams_enqueue.hip) cannot launch stream by stream: which streams a round of tiles holds is known on the
-// device only (StreamsRoundPart, zgpu_deflate_streams_plan.h; made by senq_round_kernel, zgpu_streams_batch.hip).  The seven scans above run here as seven
-// launches over ALL parts of a round: the bodies above with the arguments StreamBlocks (zgpu_deflate_streams.hip) would give them on the host, read from the
-// part -- part blockIdx.x for the three scans, the part found for a tile or a block slot for the others.  Launched at the host's upper bounds (a part per
-// tile, kSenqBlkPerTile block slots per tile); what belongs to nobody leaves at the top, uniformly per workgroup where a barrier follows.
-constexpr uint32_t kBatchScan = 256; // lanes of the batched scans: a part has a handful of tiles and blocks
+// Both batch calls over many streams use this: the seven scans above as seven launches over ALL parts of a round of tiles, whatever the number of
+// streams.  A part (StreamsRoundPart, zgpu_deflate_streams_plan.h) is one stream's tiles in the round; the bodies above get the arguments a one-stream
+// launch would get from the host, read from the part (streams_part_args) -- part blockIdx.x for the three scans, the part found for a tile or a block
+// slot for the others.  The blocking call (zgpu_deflate_streams.hip) plans the rounds on the host, uploads parts and records and launches at the exact
+// extents; the stream-ordered call (zgpu_deflate_streams_enqueue.hip) has them made on the device (senq_round_kernel, zgpu_streams_batch.hip) and
+// launches at the host's upper bounds, a part per tile and kSenqBlkPerTile block slots per tile.  What belongs to nobody leaves at the top, uniformly
+// per workgroup where a barrier follows.
+constexpr uint32_t kBatchScan = 256; // lanes of the batched scans: most parts have a handful of tiles and blocks, a lane of a long part takes a run of them
 
 struct PartView { // a part with its stream's arguments
     StreamsRoundPart p; StreamsPartArgs a; uint64_t in_lo, out_lo, out_words;
@@ -245,7 +241,7 @@ __device__ __forceinline__ PartView part_view(const ContBatch &q, uint32_t j)
     v.p = q.parts[j];
     const uint64_t k = v.p.item;
     v.in_lo = q.in_off[k];
-    v.a = senq_part_args(v.p, q.in_off[k + 1] - v.in_lo, q.tile0[k], q.t0);
+    v.a = streams_part_args(v.p, q.in_off[k + 1] - v.in_lo, q.tile0[k], q.t0);
     v.out_lo = q.oo[k];
     v.out_words = streams_room_cap(q.oo[k + 1] - v.out_lo, q.flags) >> 2;
     return v;
@@ -288,7 +284,8 @@ __global__ void __launch_bounds__(256) cont_compact_batch_kernel(ContBatch q)
     ContBlk *blk = q.blk + v.p.boff;
 #include "zgpu_cont_compact_body.inc"
 }
-// ... with streams_blocks_kernel's work (zgpu_streams.hip) folded in: every slot of the launch learns whose it is, a block's tokens their place in the round's array
+// ... and what ONE block-construction launch over all streams needs: every slot of the launch learns whose it is (blk_item: the item, ~0 for a slot behind
+// its stream's last block), a block's tokens their place in the round's array
 __global__ void __launch_bounds__(256) cont_table_batch_kernel(ContBatch q)
 {
     const uint32_t s = blockIdx.x * 256 + threadIdx.x;
@@ -368,20 +365,21 @@ void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const 
 }
 uint64_t cont_special_pos(uint64_t n) { return cont_special(n); }
 
-// the round's tokens into blocks, behind the parse: launches 1-3 of the seven
-void launch_cont_batch_tokens(const ContBatch &q, uint32_t batch, hipStream_t s)
+// the round's tokens into blocks, behind the parse: launches 1-3 of the seven.  nparts_max, ntiles_max: what the host knows of the round's parts and
+// real tiles -- the numbers themselves (the blocking call) or bounds of them (the stream-ordered call); block slots: q.nslots_max
+void launch_cont_batch_tokens(const ContBatch &q, uint32_t nparts_max, uint32_t ntiles_max, hipStream_t s)
 {
-    hipLaunchKernelGGL(cont_tokscan_batch_kernel, dim3(batch), dim3(kBatchScan), 0, s, q);
-    hipLaunchKernelGGL(cont_compact_batch_kernel, dim3(batch), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(cont_tokscan_batch_kernel, dim3(nparts_max), dim3(kBatchScan), 0, s, q);
+    hipLaunchKernelGGL(cont_compact_batch_kernel, dim3(ntiles_max), dim3(256), 0, s, q);
     hipLaunchKernelGGL(cont_table_batch_kernel, dim3((q.nslots_max + 255) / 256), dim3(256), 0, s, q);
 }
 // ... and the coded blocks into the rooms, behind block construction: launches 4-7
-void launch_cont_batch_stitch(const ContBatch &q, uint32_t batch, hipStream_t s)
+void launch_cont_batch_stitch(const ContBatch &q, uint32_t nparts_max, hipStream_t s)
 {
-    hipLaunchKernelGGL(cont_bitscan_batch_kernel, dim3(batch), dim3(kBatchScan), 0, s, q);
+    hipLaunchKernelGGL(cont_bitscan_batch_kernel, dim3(nparts_max), dim3(kBatchScan), 0, s, q);
     hipLaunchKernelGGL(cont_edges_batch_kernel, dim3((q.nslots_max + 255) / 256), dim3(256), 0, s, q);
     hipLaunchKernelGGL(cont_stitch_batch_kernel, dim3(q.nslots_max), dim3(256), 0, s, q);
-    hipLaunchKernelGGL(cont_carry_batch_kernel, dim3(batch), dim3(kBatchScan), 0, s, q);
+    hipLaunchKernelGGL(cont_carry_batch_kernel, dim3(nparts_max), dim3(kBatchScan), 0, s, q);
 }
 
 } // namespace zgpu

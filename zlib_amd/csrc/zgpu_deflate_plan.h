@@ -281,6 +281,16 @@ struct ContPlan {
     uint32_t batch_fit = ~0u; // what the device's memory admits
 };
 
+// The special position of a segment that ends at stream position n: the position 32768 k + 65274 in [n - 261, n], ~0 if there is none.  Less than
+// MIN_LOOKAHEAD is left there, so the reference slides its window one loop top early (zgpu_cont.hip, cont_slides) and the position's first candidate,
+// exactly MAX_DIST back, is NIL.  Every user of the position calls this one function
+__host__ __device__ inline uint64_t cont_special(uint64_t n)
+{
+    if (n < 65274u) return ~0ull;
+    const uint64_t sp = (n - 65274u) / 32768u * 32768u + 65274u;
+    return sp + 261u >= n ? sp : ~0ull;
+}
+
 // levels 1-3 with Z_HUFFMAN_ONLY: no match is ever looked for, no chain ever asked: the walkers' path (every byte a literal) serves it
 inline bool cont_fast_lz(const LevelCfg &cfg) { return !cfg.slow && cfg.strategy != kHuffmanOnly; }
 

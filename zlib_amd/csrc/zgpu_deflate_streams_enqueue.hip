@@ -3,14 +3,14 @@
 // copy to or from the host, no event, no second stream, no timing, and no device memory of the engine's: the scratch is the caller's workspace, laid out by
 // senq_ws_plan (zgpu_deflate_streams_plan.h).  No kernel lives here.
 //
-// The blocking call (streams_run, zgpu_deflate_streams.hip) reads its tables, plans on the host and launches the block layer stream by stream.  Here the
-// host knows three numbers -- n, in_bytes, batch_tiles -- and sizes and launches by them alone:
+// The blocking call (streams_run, zgpu_deflate_streams.hip) reads its tables, plans its rounds on the host and launches the same kernels at the exact
+// extents.  Here the plan is made on the device; the host knows three numbers -- n, in_bytes, batch_tiles -- and sizes and launches by them alone:
 //   the tiles    at most ntiles_max = in_bytes / kTileStride + n; the list is laid out for that many, in whole rounds of `batch` tiles, and the rows behind
 //                the real tiles are padding rows, for which every kernel of the chain leaves at its top
 //   the plan     senq_scan_kernel, senq_rows_kernel once; senq_round_kernel per round (zgpu_streams_batch.hip)
 //   the LZ stage launch_lz_tiles / launch_lz_tiles_parse over the round's rows, as the blocking call's
-//   the blocks   seven launches per round over all of its streams (launch_cont_batch_*, zgpu_cont.hip) around ONE block-construction launch, all at the
-//                host's upper bounds: a part per tile, kSenqBlkPerTile block slots per tile
+//   the blocks   the blocking call's: seven launches per round over all of its streams (launch_cont_batch_*, zgpu_cont.hip) around ONE block-construction
+//                launch -- but all at the host's upper bounds: a part per tile, kSenqBlkPerTile block slots per tile
 //   checksums    checksum_batch_enqueue (zgpu_checksum.hip) at the upper bound of pieces, ntiles_max
 #include "zgpu_engine.h"
 #include "zgpu_deflate_streams_plan.h"
@@ -98,11 +98,9 @@ int zgpu_deflate_streams_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_b
     launch_senq_clear(w.cnt, fault, d_summary, st);
     launch_senq_scan(d_in_offsets, d_out_offsets, n, in_bytes, out_cap, w.state, w.tile0, w.piece0, w.cnt, st);
     launch_senq_rows(d_in_offsets, w.tile0, n, pl.rounds * batch, w.rows, st);
-    launch_streams_head_state(d_in_offsets, d_out_offsets, w.state, n, fh, p->flags, w.st, out, w.entry, st);
-    ChunkGeom g{}; TileGeom tg{};
-    g.in = in; g.in_bytes = in_bytes; g.chunk_size = kChunkMax; g.final_chunk = ~0ull; g.block_tokens = kBlockTokens; g.slot_stride = kSlotStride;
-    g.tile_stride = kTileStride; // (with g.rows: the tiles come row by row)
-    tg.nil_pos = ~0ull; tg.exits = w.exits; tg.entry = w.entry;
+    launch_streams_head(d_in_offsets, d_out_offsets, w.state, n, fh, p->flags, w.st, out, w.entry, nullptr, st); // (the counters: cleared above)
+    ChunkGeom g; TileGeom tg;
+    streams_list_geom(in, in_bytes, w.exits, w.entry, &g, &tg);
     ContBatch q{};
     q.parts = w.parts; q.round = w.round; q.in_off = d_in_offsets; q.oo = d_out_offsets; q.tile0 = w.tile0; q.in = in; q.out = out; q.flags = p->flags; q.slow = cfg.slow != 0;
     q.nslots_max = nslots_max; q.st = w.st; q.entry = w.entry; q.tokens = w.tokens; q.tmeta = w.meta; q.tokoff = w.tokoff; q.carry = w.carry; q.T = w.T; q.blk = w.blk; q.pos = w.pos;
@@ -116,13 +114,13 @@ int zgpu_deflate_streams_enqueue(zgpu_engine *e, const void *d_in, uint64_t in_b
         launch_lz_tiles(g, tg, cfg, w.sorted, w.meta, w.comp, w.gentry, st, nullptr, e->exact_sort); // (no engine: no stage timer, no event)
         launch_streams_entry(g.rows, batch, w.entry + t0, st);
         launch_lz_tiles_parse(g, tg, cfg, w.sorted, w.tokens, w.meta, st, nullptr);
-        launch_cont_batch_tokens(q, batch, st);
+        launch_cont_batch_tokens(q, batch, batch, st);
         launch_huffman_streams(g, w.T, nslots_max, w.blk, w.st, w.blk_item, w.slots, st, cfg.strategy == kFixed); // (g: block_tokens and slot_stride only)
         launch_cont_batch_stitch(q, batch, st);
     }
     // checksums of every served item, trailers, records; the sort's self-check and the summary
     checksum_batch_enqueue(in, d_in_offsets, w.state, w.piece0, n, pl.ntiles_max, want_crc ? 3u : 1u, w.ckpart, w.check, st);
-    launch_streams_finish_state(d_in_offsets, d_out_offsets, w.state, n, fh, p->flags, w.st, w.check, want_crc, out, d_items, w.cnt, st);
+    launch_streams_finish(d_in_offsets, d_out_offsets, w.state, n, fh, p->flags, w.st, w.check, want_crc, out, d_items, w.cnt, st);
     launch_senq_summary(fault, n, w.cnt, d_items, d_summary, st);
     ZGPU_HIP_CHECK(hipGetLastError());
     return ZGPU_OK;

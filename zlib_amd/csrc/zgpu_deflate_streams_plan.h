@@ -1,11 +1,13 @@
-// zgpu_deflate_streams_plan.h -- internal (not installed): what a batch compress of many independent streams (zgpu_deflate_streams_*,
-// zgpu_deflate_streams.hip) decides from plain numbers -- how many tiles a stream of a given length has, the row of the per-tile table for each of
-// them, the rooms of the output and their bound, where the batches of tiles end and which streams a batch holds.  No HIP call, no getenv;
+// zgpu_deflate_streams_plan.h -- internal (not installed): what a batch compress of many independent streams decides from plain numbers.  Two calls share it.
+// The BLOCKING call (zgpu_deflate_streams_device / _host, streams_run in zgpu_deflate_streams.hip) reads its tables, so the HOST decides everything in the
+// first part of this header: how many tiles a stream of a given length has, the row of the per-tile table for each of them, the rooms of the output and
+// their bound, where the batches of tiles end, and the round plan -- which streams a batch holds (its parts) and what they need of the block layer's
+// buffers.  The stream-ordered call (second part) decides the same things with the same functions, on the device.  No HIP call, no getenv;
 // tests/tools/deflate_streams_plan_model.cpp prints the same numbers on a machine without a GPU.
 //
 // Every stream of the call is a fresh one-feed FINISH stream (zgpu_cont.hip): stream position 0 is its first byte, the parse enters its first tile at 0,
 // later tiles start every kTileStride bytes, and the parse runs up to the stream's end.  The tiles of all streams, stream after stream, form ONE list;
-// a batch of tiles is a run of that list and may begin and end inside a stream.
+// a batch of tiles (a round) is a run of that list and may begin and end inside a stream.
 #pragma once
 #include "zgpu_deflate_plan.h"
 
@@ -16,12 +18,11 @@ constexpr uint32_t kStreamsCarry = 16384; // tokens of the block that is still f
 // tiles of a stream of L bytes: what plan_cont gives a fresh stream's one FINISH feed
 __host__ __device__ inline uint64_t streams_ntiles(uint64_t L) { return L == 0 ? 0 : L <= kTileH1 ? 1 : (L - kTileH1 + kTileStride - 1) / kTileStride + 1; }
 
-// the one position of a stream of n bytes whose first candidate, exactly MAX_DIST back, is NIL: 32768 k + 65274 in [n - 261, n) (zgpu_cont.hip, cont_special); ~0: none
+// the one position of a stream of n bytes whose first candidate, exactly MAX_DIST back, is NIL: cont_special (zgpu_deflate_plan.h), if it is below n; ~0: none
 __host__ __device__ inline uint64_t streams_special(uint64_t n)
 {
-    if (n < 65274u) return ~0ull;
-    const uint64_t sp = (n - 65274u) / 32768u * 32768u + 65274u;
-    return (sp + 261u >= n && sp < n) ? sp : ~0ull;
+    const uint64_t sp = cont_special(n);
+    return sp < n ? sp : ~0ull;
 }
 
 // tile ti of the stream in[off, off + L): the row that says of it what ChunkGeom's and TileGeom's scalars say of tile ti of a one-stream launch
@@ -113,33 +114,57 @@ inline uint32_t streams_batch_tiles(uint64_t ntiles, const PlanEngine &eng, cons
 __host__ __device__ inline uint32_t streams_tok_cap(uint32_t nt) { return (kStreamsCarry + kTileStride * (nt + 1) + kTileSlack + 3) & ~3u; }
 __host__ __device__ inline uint32_t streams_blk_cap(uint32_t nt) { return streams_tok_cap(nt) / kBlockTokens + 2; }
 
-// a stream's part of a batch as the device sees it: where its blocks and tokens lie in the batch's buffers (slots boff .., tokens toff ..), whose they are
-struct StreamsBlkPart { uint32_t boff, toff, item, pad; };
-
-// One batch of the list: tiles [t0, t0 + nb); its streams are the items k0 .. with tiles in it
-struct StreamsPart { uint64_t item; uint64_t a, b; bool ends; }; // tiles [a, b) of the list belong to `item`; ends: the stream's last tile is among them
-// the part of item k in the batch, false: none
-inline bool streams_part(const uint64_t *tile0, uint64_t k, uint64_t t0, uint32_t nb, StreamsPart *out)
+// A round = tiles [t0, t0 + batch) of the list, of which the first nreal exist (the blocking call's batches are all real; the stream-ordered call pads
+// its list).  Its parts -- a part is the tiles of ONE stream in the round -- as the batched block layer reads them (cont_*_batch_kernel, zgpu_cont.hip)
+struct StreamsRoundPart {
+    uint32_t boff, toff; // where the part's blocks and tokens lie in the round's buffers (exclusive sums of the caps of the parts in front)
+    uint32_t item;       // whose tiles
+    uint32_t c0, nt;     // tiles [c0, c0 + nt) of the round
+    uint32_t ends;       // the stream's last tile is among them
+    uint32_t nblk_cap;   // streams_blk_cap(nt)
+    uint32_t j;          // the part's number in the round (its pos[] and tokoff[] run one entry longer than its blocks and tiles)
+};
+struct StreamsRound { uint32_t nparts, nreal, nslots, ntok; }; // parts, real tiles, block slots and token room in use (sums of the parts' caps)
+__host__ __device__ inline uint32_t streams_round_real(uint64_t ntiles, uint64_t t0, uint32_t batch) { return (uint32_t)(ntiles <= t0 ? 0 : ntiles - t0 < batch ? ntiles - t0 : batch); }
+// does a part begin at tile c of the round (c < nreal)?  fills all but boff, toff and j
+__host__ __device__ inline bool streams_part_at(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t nreal, uint32_t c, StreamsRoundPart *p)
 {
-    const uint64_t a = tile0[k] > t0 ? tile0[k] : t0, b = tile0[k + 1] < t0 + nb ? tile0[k + 1] : t0 + nb;
-    if (a >= b) return false;
-    out->item = k; out->a = a; out->b = b; out->ends = b == tile0[k + 1];
+    const uint64_t t = t0 + c, k = streams_item_of(tile0, n, t);
+    if (c != 0 && tile0[k] != t) return false;
+    const uint64_t end = tile0[k + 1] < t0 + nreal ? tile0[k + 1] : t0 + nreal;
+    p->item = (uint32_t)k; p->c0 = c; p->nt = (uint32_t)(end - t); p->ends = end == tile0[k + 1] ? 1u : 0u; p->nblk_cap = streams_blk_cap(p->nt);
     return true;
 }
-// the block layer's needs of the batch [t0, t0 + nb): streams in it, tokens, blocks (sums of the parts' caps)
-inline void streams_batch_needs(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t nb, uint64_t *nstreams, uint64_t *ntok, uint64_t *nblk)
+// the round's plan as one loop: the blocking call's, and what senq_round_kernel (zgpu_streams_batch.hip) does with a workgroup's scan over the tiles
+inline StreamsRound streams_round_plan(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t batch, StreamsRoundPart *parts)
 {
-    uint64_t s = 0, t = 0, b = 0;
-    StreamsPart pt;
-    for (uint64_t k = streams_item_of(tile0, n, t0); k < n && tile0[k] < t0 + nb; k++)
-        if (streams_part(tile0, k, t0, nb, &pt)) { s++; t += streams_tok_cap((uint32_t)(pt.b - pt.a)); b += streams_blk_cap((uint32_t)(pt.b - pt.a)); }
-    *nstreams = s; *ntok = t; *nblk = b;
+    StreamsRound r{0, streams_round_real(tile0[n], t0, batch), 0, 0};
+    for (uint32_t c = 0; c < r.nreal; c++) {
+        StreamsRoundPart p{};
+        if (!streams_part_at(tile0, n, t0, r.nreal, c, &p)) continue;
+        p.boff = r.nslots; p.toff = r.ntok; p.j = r.nparts;
+        parts[r.nparts++] = p;
+        r.nslots += p.nblk_cap; r.ntok += streams_tok_cap(p.nt);
+    }
+    return r;
+}
+// what the batched block layer takes from a part: the stream's own geometry (its length, its end, its special position, its own number of the part's
+// first tile) -- the arguments a one-stream launch of the same kernels gets from the host
+struct StreamsPartArgs { uint64_t L, seg_end, sp; uint64_t chunk0; uint32_t final_block; };
+__host__ __device__ inline StreamsPartArgs streams_part_args(const StreamsRoundPart &p, uint64_t L, uint64_t tile0_item, uint64_t t0)
+{
+    StreamsPartArgs a;
+    a.L = L; a.seg_end = p.ends ? L : ~0ull; a.final_block = p.ends;
+    a.sp = p.ends ? cont_special(L) : ~0ull;
+    a.chunk0 = t0 + p.c0 - tile0_item;
+    return a;
 }
 
 // =====================================================================================================================================================
-// The stream-ordered call (zgpu_deflate_streams_enqueue, zgpu_deflate_streams_enqueue.hip): the host may not read the tables, so everything above that
-// streams_run decides on the host is decided on the device -- by the functions below, which the kernels of zgpu_streams_batch.hip call lane by lane and
-// tests/tools/deflate_streams_enqueue_plan_model.cpp calls in plain loops.  What the host does know is n, in_bytes and batch_tiles; it sizes by them.
+// The stream-ordered call (zgpu_deflate_streams_enqueue, zgpu_deflate_streams_enqueue.hip): the host may not read the tables, so the DEVICE makes the
+// plan above -- the kernels of zgpu_streams_batch.hip call the same functions lane by lane -- after judging every table entry itself.  The host knows n,
+// in_bytes and batch_tiles only and decides what follows from them: an upper bound of the tiles, the rounds and their padding rows, a bound of the rooms,
+// the workspace.  tests/tools/deflate_streams_enqueue_plan_model.cpp calls all of it in plain loops.
 //
 // The tile count: streams_ntiles(L) <= L / kTileStride + 1 (L <= kTileH1: one tile at most; above, ceil(L / kTileStride) - 1 <= L / kTileStride), so the
 // tiles of items that do not overlap and end inside in_bytes are at most
@@ -204,53 +229,6 @@ __host__ __device__ inline TileRow senq_tile_row(const uint64_t *in_off, const u
     if (n == 0 || t >= tile0[n]) return streams_pad_row();
     const uint64_t k = streams_item_of(tile0, n, t);
     return streams_tile_row(in_off[k], in_off[k + 1] - in_off[k], t - tile0[k]);
-}
-
-// A round = tiles [t0, t0 + batch) of the padded list, of which the first nreal are real.  Its parts as the batched block layer reads them: what
-// StreamBlocks (zgpu_deflate_streams.hip) derives on the host for one stream of a batch
-struct StreamsRoundPart {
-    uint32_t boff, toff; // where the part's blocks and tokens lie in the round's buffers (exclusive sums of the caps of the parts in front)
-    uint32_t item;       // whose tiles
-    uint32_t c0, nt;     // tiles [c0, c0 + nt) of the round
-    uint32_t ends;       // the stream's last tile is among them
-    uint32_t nblk_cap;   // streams_blk_cap(nt)
-    uint32_t j;          // the part's number in the round (its pos[] and tokoff[] run one entry longer than its blocks and tiles)
-};
-struct StreamsRound { uint32_t nparts, nreal, nslots, ntok; }; // parts, real tiles, block slots and token room in use
-__host__ __device__ inline uint32_t senq_round_real(uint64_t ntiles, uint64_t t0, uint32_t batch) { return (uint32_t)(ntiles <= t0 ? 0 : ntiles - t0 < batch ? ntiles - t0 : batch); }
-// does a part begin at tile c of the round (c < nreal)?  fills all but boff, toff and j
-__host__ __device__ inline bool senq_part_at(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t nreal, uint32_t c, StreamsRoundPart *p)
-{
-    const uint64_t t = t0 + c, k = streams_item_of(tile0, n, t);
-    if (c != 0 && tile0[k] != t) return false;
-    const uint64_t end = tile0[k + 1] < t0 + nreal ? tile0[k + 1] : t0 + nreal;
-    p->item = (uint32_t)k; p->c0 = c; p->nt = (uint32_t)(end - t); p->ends = end == tile0[k + 1] ? 1u : 0u; p->nblk_cap = streams_blk_cap(p->nt);
-    return true;
-}
-// the round's plan as one loop (the kernel: the same with a workgroup's scan over the tiles)
-inline StreamsRound senq_round_plan(const uint64_t *tile0, uint64_t n, uint64_t t0, uint32_t batch, StreamsRoundPart *parts)
-{
-    StreamsRound r{0, senq_round_real(tile0[n], t0, batch), 0, 0};
-    for (uint32_t c = 0; c < r.nreal; c++) {
-        StreamsRoundPart p{};
-        if (!senq_part_at(tile0, n, t0, r.nreal, c, &p)) continue;
-        p.boff = r.nslots; p.toff = r.ntok; p.j = r.nparts;
-        parts[r.nparts++] = p;
-        r.nslots += p.nblk_cap; r.ntok += streams_tok_cap(p.nt);
-    }
-    return r;
-}
-// what the batched block layer takes from a part: the stream's own geometry (its tile numbers, its end) -- StreamBlocks' constructor
-struct StreamsPartArgs { uint64_t L, seg_end, sp; uint64_t chunk0; uint32_t final_block; };
-__host__ __device__ inline StreamsPartArgs senq_part_args(const StreamsRoundPart &p, uint64_t L, uint64_t tile0_item, uint64_t t0)
-{
-    StreamsPartArgs a;
-    a.L = L; a.seg_end = p.ends ? L : ~0ull; a.final_block = p.ends;
-    // cont_special (zgpu_cont.hip): the position 32768 k + 65274 in [L - 261, L]
-    a.sp = ~0ull;
-    if (p.ends && L >= 65274u) { const uint64_t s = (L - 65274u) / 32768u * 32768u + 65274u; if (s + 261u >= L) a.sp = s; }
-    a.chunk0 = t0 + p.c0 - tile0_item; // the stream's own number of the part's first tile
-    return a;
 }
 
 // ---- rooms without the host knowing the sizes ----

@@ -45,7 +45,7 @@ struct Carve {
 
 } // namespace zgpu
 
-namespace zgpu { struct StreamsBlkPart; }
+namespace zgpu { struct StreamsRoundPart; struct StreamsRound; } // zgpu_deflate_streams_plan.h
 struct StageSpan { int stage; hipEvent_t a, b; };
 
 struct zgpu_engine {
@@ -93,10 +93,11 @@ struct zgpu_engine {
     uint32_t ct_tiles() const { return ct_tokoff.cap ? (uint32_t)(ct_tokoff.cap - 1) : 0; } // (ct_tokoff: a word per tile and one more)
     DevBuf<zgpu::ChunkMeta> ct_ckmeta;
     DevBuf<uint64_t> ct_excl;
-    // many streams in one call (zgpu_deflate_streams.hip): per call -- the tiles' rows and entries, a state and the checksums per item, the totals; per
-    // batch of tiles -- the token offsets (a word per tile and one more per stream); the host entry's tables, rooms' records and packed streams
+    // many streams in one call (zgpu_deflate_streams.hip): per call -- the tiles' rows and entries, a state and the checksums per item, the totals, the
+    // plan (the parts of every batch back to back, a record per batch, the tiles in front of every item); per batch of tiles -- the token offsets (a
+    // word per tile and one more per stream), whose every block slot is; the host entry's tables, rooms' records and packed streams
     DevBuf<zgpu::TileRow> ds_rows; DevBuf<uint16_t> ds_entry; DevBuf<zgpu::ContState> ds_st; DevBuf<zgpu_check_item> ds_check; DevBuf<unsigned long long> ds_totals;
-    DevBuf<uint32_t> ds_tokoff, ds_blk_item; DevBuf<zgpu::StreamsBlkPart> ds_parts; // (ds_parts: per call, the streams' parts of every batch)
+    DevBuf<uint32_t> ds_tokoff, ds_blk_item; DevBuf<zgpu::StreamsRoundPart> ds_parts; DevBuf<zgpu::StreamsRound> ds_rounds; DevBuf<uint64_t> ds_tile0;
     DevBuf<uint64_t> ds_in_off, ds_oo, ds_po; DevBuf<zgpu_deflate_batch_item> ds_items; DevBuf<uint8_t> ds_packed;
     // ... levels 1-3: the rounds of fastwin_tile_kernel (the per-batch ones are one group)
     DevBuf<uint16_t> cf_exit_a, cf_exit_b; DevBuf<uint32_t> cf_ins0, cf_ins1, cf_prev, cf_prev2, cf_hist, cf_count;
@@ -160,6 +161,7 @@ PlanEngine plan_engine(const zgpu_engine *e, const LevelCfg *cfg);
 
 // ---- zgpu_deflate_streams.hip ----
 const char *streams_refuse(const zgpu_engine *e, const zgpu_deflate_params *p); // why the batch compress of many streams does not serve these parameters, nullptr: it does
+void streams_list_geom(const uint8_t *d_in, uint64_t in_bytes, uint16_t *exits, uint16_t *entry, ChunkGeom *g, TileGeom *tg); // a list of tiles that comes row by row: what both batch calls give the LZ stage
 
 // ---- zgpu_deflate_cont.hip ----
 int deflate_cont_oneshot(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const zgpu_deflate_params *p, uint8_t *d_out, uint64_t out_cap, zgpu_deflate_result *res, hipStream_t st);
@@ -233,33 +235,26 @@ void launch_cont_tokens(const ChunkGeom &g, const TileGeom &tg, const uint32_t *
 void launch_cont_stitch(const ContBlk *blk, ContState *st, uint64_t *pos, const uint8_t *slots, uint32_t slot_stride, const uint8_t *in, uint64_t abs0, uint8_t *out, uint64_t out_cap,
                         uint32_t nblk_cap, const uint32_t *T, uint32_t *carry, uint64_t seg_end, hipStream_t s);
 
-// the batched block layer: one round of a stream-ordered call over many streams (zgpu_deflate_streams_enqueue.hip), everything in device memory
-struct StreamsRoundPart; struct StreamsRound; // zgpu_deflate_streams_plan.h
+// the batched block layer: one round (batch of tiles) of a batch call over many streams, everything in device memory
 struct ContBatch {
-    const StreamsRoundPart *parts; const StreamsRound *round; // the round's parts and their number, made on the device
+    const StreamsRoundPart *parts; const StreamsRound *round; // the round's parts and their number (streams_round_plan on the host, senq_round_kernel on the device)
     const uint64_t *in_off, *oo, *tile0; uint64_t t0;          // the caller's tables, the tiles in front of every item, the round's first tile in the list
     const uint8_t *in; uint8_t *out; uint32_t flags, slow, nslots_max;
     ContState *st; const uint16_t *entry;                      // per item; per tile of the list
     const uint32_t *tokens; const ChunkMeta *tmeta;            // per tile of the round
     uint32_t *tokoff, *carry, *T; ContBlk *blk; uint64_t *pos; const uint8_t *slots; uint32_t *blk_item;
 };
-void launch_cont_batch_tokens(const ContBatch &q, uint32_t batch, hipStream_t s);
-void launch_cont_batch_stitch(const ContBatch &q, uint32_t batch, hipStream_t s);
+void launch_cont_batch_tokens(const ContBatch &q, uint32_t nparts_max, uint32_t ntiles_max, hipStream_t s); // (the launches' extents: the round's numbers, or bounds of them)
+void launch_cont_batch_stitch(const ContBatch &q, uint32_t nparts_max, hipStream_t s);
 
 // ---- zgpu_streams.hip ----
-void launch_streams_head(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out, uint16_t *entry0,
+// state: nullptr, or the stream-ordered call's table check (state[k] != 0 marks an item it has failed); totals: cleared by the head launch unless nullptr
+void launch_streams_head(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out, uint16_t *entry0,
                          unsigned long long *totals, hipStream_t s);
 void launch_streams_entry(const TileRow *rows, uint32_t ntiles, uint16_t *entry, hipStream_t s);
-struct StreamsBlkPart; // zgpu_deflate_streams_plan.h
-void launch_streams_blocks(const StreamsBlkPart *parts, uint32_t nparts, uint32_t nslots, const ContState *st, ContBlk *blk, uint32_t *blk_item, hipStream_t s);
-void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st, const zgpu_check_item *chk, bool want_crc,
-                           uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s);
+void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st,
+                           const zgpu_check_item *chk, bool want_crc, uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s);
 void launch_streams_pack(const uint8_t *rooms, const uint64_t *oo, const uint64_t *po, uint64_t n, uint64_t total, uint8_t *packed, hipStream_t s);
-// ... of the stream-ordered call: state[k] != 0 marks an item the device's table check has failed
-void launch_streams_head_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out,
-                               uint16_t *entry0, hipStream_t s);
-void launch_streams_finish_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st,
-                                 const zgpu_check_item *chk, bool want_crc, uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *cnt, hipStream_t s);
 
 // ---- zgpu_streams_batch.hip: the stream-ordered call's plan, made on the device ----
 void launch_senq_clear(unsigned long long *cnt, uint32_t *fault, zgpu_deflate_batch_summary *summary, hipStream_t s);

@@ -1,8 +1,8 @@
-// zgpu_streams.hip -- the small kernels of the batch compress of many independent streams (zgpu_deflate_streams.hip is the host side,
-// zgpu_deflate_streams_plan.h the plan): where every stream starts (its state, its header), what closes it (trailer, record), the entries of the
-// streams' first tiles, and the packing of the finished streams for the host entry.  The tiles themselves are sorted, walked and parsed by the ROWS
-// instantiations of sort4_kernel, walk_kernel and parse2_kernel; the blocks' scans are zgpu_cont.hip's kernels, stream by stream, and the blocks of all
-// streams of a batch are coded by one launch of huffman_kernel<true, true>, which streams_blocks_kernel here prepares.
+// zgpu_streams.hip -- the small kernels of the batch compress of many independent streams, for both of its calls (zgpu_deflate_streams.hip is the
+// blocking call's host side, zgpu_deflate_streams_enqueue.hip the stream-ordered call's, zgpu_deflate_streams_plan.h the plan): where every stream starts
+// (its state, its header), what closes it (trailer, record), the entries of the streams' first tiles, and the packing of the finished streams for the
+// host entry.  The tiles themselves are sorted, walked and parsed by the ROWS instantiations of sort4_kernel, walk_kernel and parse2_kernel; the blocks'
+// scans are the batched kernels of zgpu_cont.hip, and the blocks of all streams of a batch are coded by one launch of huffman_kernel<true, true>.
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
 #include "zgpu_deflate_streams_plan.h"
@@ -31,23 +31,17 @@ __device__ __forceinline__ void streams_head_item(uint64_t k, const uint64_t *__
     else for (uint32_t i = 0; i < h.head_words; i++) w[i] = h.head[i];
     st[k] = s;
 }
-__global__ void __launch_bounds__(256) streams_head_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, uint64_t n, StreamsHead h, ContState *__restrict__ st,
-                                                           uint8_t *__restrict__ out, uint16_t *__restrict__ entry0, unsigned long long *__restrict__ totals)
+// state: the stream-ordered call's table check (nullptr: the blocking call, whose host has checked the tables) -- an item it has failed (state[k] != 0)
+// gets a state that says nothing and writes nothing.  totals: the blocking call's counters, cleared here (nullptr: the stream-ordered call clears its
+// own in senq_clear_kernel, the launch in front)
+__global__ void __launch_bounds__(256) streams_head_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const uint32_t *__restrict__ state, uint64_t n,
+                                                           StreamsHead h, ContState *__restrict__ st, uint8_t *__restrict__ out, uint16_t *__restrict__ entry0,
+                                                           unsigned long long *__restrict__ totals)
 {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k == 0) { *entry0 = 0; totals[0] = 0; totals[1] = 0; totals[2] = 0; }
+    if (k == 0) { *entry0 = 0; if (totals) { totals[0] = 0; totals[1] = 0; totals[2] = 0; } }
     if (k >= n) return;
-    streams_head_item(k, in_off, oo, h, st, out);
-}
-// the stream-ordered call (zgpu_deflate_streams_enqueue.hip): the same for the items the device's table check serves (state 0); a failed item gets a state
-// that says nothing and writes nothing.  The counters are cleared by the launch in front
-__global__ void __launch_bounds__(256) streams_head_state_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const uint32_t *__restrict__ state, uint64_t n,
-                                                                 StreamsHead h, ContState *__restrict__ st, uint8_t *__restrict__ out, uint16_t *__restrict__ entry0)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k == 0) *entry0 = 0;
-    if (k >= n) return;
-    if (state[k] != kSenqServed) { ContState s{}; s.data_type = 2; st[k] = s; return; }
+    if (state && state[k] != kSenqServed) { ContState s{}; s.data_type = 2; st[k] = s; return; }
     streams_head_item(k, in_off, oo, h, st, out);
 }
 
@@ -56,20 +50,6 @@ __global__ void __launch_bounds__(256) streams_entry_kernel(const TileRow *__res
 {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t < ntiles && rows[t].nent == 1) entry[t] = 0;
-}
-
-// Behind the streams' cont_table_kernel launches of a batch: every block slot of the batch learns whose it is (blk_item: the item, ~0 for a slot behind
-// its stream's last block) and its tokens' place in the batch's token array, so that ONE block-construction launch serves all streams
-__global__ void __launch_bounds__(256) streams_blocks_kernel(const StreamsBlkPart *__restrict__ parts, uint32_t nparts, uint32_t nslots, const ContState *__restrict__ st,
-                                                             ContBlk *__restrict__ blk, uint32_t *__restrict__ blk_item)
-{
-    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= nslots) return;
-    uint32_t lo = 0, hi = nparts; // the last part with boff <= c
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (parts[mid].boff <= c) lo = mid; else hi = mid; }
-    const StreamsBlkPart p = parts[lo];
-    if (c - p.boff < st[p.item].nblk) { blk[c].tok0 += p.toff; blk_item[c] = p.item; }
-    else blk_item[c] = 0xFFFFFFFFu;
 }
 
 // item k's trailer and record; totals: [0] bytes of all streams, [1] tokens, [2] records that are not ZGPU_OK
@@ -99,29 +79,21 @@ __device__ __forceinline__ void streams_finish_item(uint64_t k, const uint64_t *
     atomicAdd(&totals[1], (unsigned long long)s.ntokens);
     items[k] = it;
 }
-__global__ void __launch_bounds__(256) streams_finish_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, uint64_t n, StreamsHead h, const ContState *__restrict__ st,
-                                                             const zgpu_check_item *__restrict__ chk, uint32_t want_crc, uint8_t *__restrict__ out,
-                                                             zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ totals)
+// state as for streams_head_kernel: a failed item's record is the failed record of the other enqueue calls -- it has read nothing and written nothing
+__global__ void __launch_bounds__(256) streams_finish_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const uint32_t *__restrict__ state, uint64_t n,
+                                                             StreamsHead h, const ContState *__restrict__ st, const zgpu_check_item *__restrict__ chk, uint32_t want_crc,
+                                                             uint8_t *__restrict__ out, zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ totals)
 {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    streams_finish_item(k, in_off, oo, h, st, chk, want_crc, out, items, totals);
-}
-// the stream-ordered call: a failed item's record is the failed record of the other enqueue calls -- it has read nothing and written nothing
-__global__ void __launch_bounds__(256) streams_finish_state_kernel(const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ oo, const uint32_t *__restrict__ state, uint64_t n,
-                                                                   StreamsHead h, const ContState *__restrict__ st, const zgpu_check_item *__restrict__ chk, uint32_t want_crc,
-                                                                   uint8_t *__restrict__ out, zgpu_deflate_batch_item *__restrict__ items, unsigned long long *__restrict__ cnt)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    if (state[k] != kSenqServed) {
+    if (state && state[k] != kSenqServed) {
         zgpu_deflate_batch_item r{};
         r.code = ZGPU_STREAM_ERROR; r.data_type = 2; r.adler32 = 1;
         items[k] = r;
-        atomicAdd(&cnt[kScntFailed], 1ull);
+        atomicAdd(&totals[kScntFailed], 1ull);
         return;
     }
-    streams_finish_item(k, in_off, oo, h, st, chk, want_crc, out, items, cnt);
+    streams_finish_item(k, in_off, oo, h, st, chk, want_crc, out, items, totals);
 }
 
 // the host entry's packing: the streams out of their rooms, back to back.  A workgroup fills 4096 bytes of the packed output, a lane 16 of them
@@ -165,34 +137,20 @@ static StreamsHead make_head(const FrameHead &fh, uint32_t flags)
     return h;
 }
 
-void launch_streams_head(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out, uint16_t *entry0,
+void launch_streams_head(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out, uint16_t *entry0,
                          unsigned long long *totals, hipStream_t s)
 {
-    hipLaunchKernelGGL(streams_head_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, n, make_head(fh, flags), st, out, entry0, totals);
+    hipLaunchKernelGGL(streams_head_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, state, n, make_head(fh, flags), st, out, entry0, totals);
 }
 void launch_streams_entry(const TileRow *rows, uint32_t ntiles, uint16_t *entry, hipStream_t s)
 {
     hipLaunchKernelGGL(streams_entry_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, s, rows, ntiles, entry);
 }
-void launch_streams_blocks(const StreamsBlkPart *parts, uint32_t nparts, uint32_t nslots, const ContState *st, ContBlk *blk, uint32_t *blk_item, hipStream_t s)
+void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st,
+                           const zgpu_check_item *chk, bool want_crc, uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s)
 {
-    if (nslots) hipLaunchKernelGGL(streams_blocks_kernel, dim3((nslots + 255) / 256), dim3(256), 0, s, parts, nparts, nslots, st, blk, blk_item);
-}
-void launch_streams_finish(const uint64_t *in_off, const uint64_t *oo, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st, const zgpu_check_item *chk, bool want_crc,
-                           uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *totals, hipStream_t s)
-{
-    hipLaunchKernelGGL(streams_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, n, make_head(fh, flags), st, chk, want_crc ? 1u : 0u, out, items, totals);
-}
-void launch_streams_head_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, ContState *st, uint8_t *out,
-                               uint16_t *entry0, hipStream_t s)
-{
-    hipLaunchKernelGGL(streams_head_state_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, state, n, make_head(fh, flags), st, out, entry0);
-}
-void launch_streams_finish_state(const uint64_t *in_off, const uint64_t *oo, const uint32_t *state, uint64_t n, const FrameHead &fh, uint32_t flags, const ContState *st,
-                                 const zgpu_check_item *chk, bool want_crc, uint8_t *out, zgpu_deflate_batch_item *items, unsigned long long *cnt, hipStream_t s)
-{
-    hipLaunchKernelGGL(streams_finish_state_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, state, n, make_head(fh, flags), st, chk, want_crc ? 1u : 0u, out,
-                       items, cnt);
+    hipLaunchKernelGGL(streams_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in_off, oo, state, n, make_head(fh, flags), st, chk, want_crc ? 1u : 0u, out, items,
+                       totals);
 }
 void launch_streams_pack(const uint8_t *rooms, const uint64_t *oo, const uint64_t *po, uint64_t n, uint64_t total, uint8_t *packed, hipStream_t s)
 {

@@ -86,21 +86,21 @@ __global__ void __launch_bounds__(256) senq_rows_kernel(const uint64_t *__restri
     if (t < nrows) rows[t] = senq_tile_row(in_off, tile0, n, t);
 }
 
-// one workgroup: the round [t0, t0 + batch) of the padded list.  senq_round_plan with a scan in place of the running sums: a part begins at a tile
+// one workgroup: the round [t0, t0 + batch) of the padded list.  streams_round_plan with a scan in place of the running sums: a part begins at a tile
 __global__ void __launch_bounds__(1024) senq_round_kernel(const uint64_t *__restrict__ tile0, uint64_t n, uint64_t t0, uint32_t batch, StreamsRoundPart *__restrict__ parts,
                                                           StreamsRound *__restrict__ round)
 {
     __shared__ uint64_t part[1024];
-    const uint32_t tid = threadIdx.x, nreal = senq_round_real(tile0[n], t0, batch), per = (nreal + 1023) / 1024;
+    const uint32_t tid = threadIdx.x, nreal = streams_round_real(tile0[n], t0, batch), per = (nreal + 1023) / 1024;
     const uint32_t a = tid * per < nreal ? tid * per : nreal, z = (tid + 1) * per < nreal ? (tid + 1) * per : nreal;
     uint64_t tj = 0, blk = 0; // tokens | parts << 32 (a round's tokens stay below 2^32: kSenqMaxBatch), block slots
     StreamsRoundPart p;
     for (uint32_t c = a; c < z; c++)
-        if (senq_part_at(tile0, n, t0, nreal, c, &p)) { tj += streams_tok_cap(p.nt) + (1ull << 32); blk += p.nblk_cap; }
+        if (streams_part_at(tile0, n, t0, nreal, c, &p)) { tj += streams_tok_cap(p.nt) + (1ull << 32); blk += p.nblk_cap; }
     uint64_t tj_all, blk_all;
     uint64_t tj0 = scan1024(part, tid, tj, &tj_all), b0 = scan1024(part, tid, blk, &blk_all);
     for (uint32_t c = a; c < z; c++)
-        if (senq_part_at(tile0, n, t0, nreal, c, &p)) {
+        if (streams_part_at(tile0, n, t0, nreal, c, &p)) {
             p.toff = (uint32_t)tj0; p.j = (uint32_t)(tj0 >> 32); p.boff = (uint32_t)b0;
             parts[p.j] = p;
             tj0 += streams_tok_cap(p.nt) + (1ull << 32); b0 += p.nblk_cap;
