@@ -27,7 +27,10 @@ unsigned long long zamd_compress2_batch_count(int which);
 
 /* windowBits 15 zlib, 31 gzip, 47 either (by the magic), -15 raw deflate.  status[k] as uncompress() (qcsrc/uncompr.c:50-56) gives it:
  * Z_OK (destLen[k] = the decoded size), Z_BUF_ERROR when destLen[k] is too small, Z_DATA_ERROR for a damaged or truncated stream and for one
- * that needs a preset dictionary.  Items of 512 MiB of input or more are served one by one. */
+ * that needs a preset dictionary.  Items of 512 MiB of input or more are served one by one.  Items of any size below that share the one engine
+ * call: one workgroup decodes an item of less than 128 KiB of deflate data, a longer one is decoded in pieces, the pieces of all long items in shared
+ * launches (zgpu_inflate_batch_host in zamd_gpu.h; zamd_uncompress_batch_packed's decode and the ZIP batch read likewise).  The sizing pass and the
+ * integrity test below still give every item to one workgroup. */
 int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits,
                           int *status);
 

@@ -453,7 +453,9 @@ int zgpu_inflate_stream_host3(zgpu_engine *e, const void *in, uint64_t in_bytes,
 /* Test hook: the next launch of the fast position sort reports that its self-check failed (the LDS did not serve an atomic's lanes in
  * lane order), so that the engine's fallback -- redo the call with the ballot-ranked sort, and keep to it -- can be exercised. */
 void zgpu_debug_inject_sort_fault(void);
-uint64_t zgpu_inflate_spec_count(int which); /* 0: decoded in pieces, 1: one-workgroup decodes */
+uint64_t zgpu_inflate_spec_count(int which); /* 0: decoded in pieces, 1: one-workgroup decodes (both: zgpu_inflate_stream_host*);
+                                              * 2: long items of blocking batch decodes decoded in pieces, 3: long items of them that fell back
+                                              * to the one-workgroup decoder (zgpu_inflate_batch_*, see there) */
 const char *zgpu_inflate_message(uint32_t index);
 /* Preset dictionary of the inflate calls that follow (inflateSetDictionary, qcsrc/inflate.c:1200-1236): the first segment of a
  * call may reach back into its last min(len, 32768) bytes.  Stays set until replaced; len 0 clears it. */
@@ -480,7 +482,15 @@ int zgpu_inflate_set_checks(zgpu_engine *e, uint32_t mask);
  *   adler32 / crc32  of the decoded bytes: checks takes ZGPU_CHECK_* bits; the check the wrapper needs is always computed (AUTO: both); a check
  *              that is not computed reads adler32 = 1 / crc32 = 0.
  * The call fails only for bad arguments (offsets that run backwards or leave their buffer), allocation or HIP errors; *nfailed (optional)
- * receives the number of items whose code is not ZGPU_OK.  The device entry blocks until the records are in d_items. */
+ * receives the number of items whose code is not ZGPU_OK.  The device entry blocks until the records are in d_items.
+ * Long items: an item whose deflate data (the item behind its header) has ZGPU_BATCH_PIECES_MIN_BYTES bytes or more -- an environment variable read at
+ * every call, 131072 unless set, 0: no item -- is not decoded by one workgroup from end to end but in pieces that start at block boundaries found by
+ * search, the pieces of all long items of the call in shared launches (zlib_amd/csrc/zgpu_inflate_batch_pieces.hip).  Records and bytes are those of the
+ * one-workgroup decoder: a long item whose pieces do not chain cleanly into its room (damage, truncation, a room too small) is decoded again by it,
+ * once.  ZGPU_BATCH_PIECES_ROUND_BYTES (default 512 MiB) caps the output room one round of the piece path serves; scratch the engine cannot reserve
+ * sends a round's items to the one-workgroup decoder and is no error.  This covers the blocking decode only (these two calls, the decode half of
+ * zgpu_inflate_batch_packed_*, zgpu_bgzf_*, the final decode of zgpu_gzip_inflate_*): the *_enqueue calls, the sizing pass and the integrity test
+ * give every item to one workgroup (one wave) as before.  zgpu_inflate_spec_count(2) / (3) count the long items decoded in pieces / fallen back. */
 #define ZGPU_WRAP_RAW 0
 #define ZGPU_WRAP_ZLIB 1
 #define ZGPU_WRAP_GZIP 2

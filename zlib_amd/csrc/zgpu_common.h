@@ -75,7 +75,33 @@ struct SpecArgs {
     uint32_t page_cap;
     uint16_t *tails;      // per segment: the ring when it ended, oldest symbol first = the last 32 KiB of the segment's output
     SpecEnd *ends;
+    const struct PieceRow *rows = nullptr; // the pieces of MANY streams (zgpu_inflate_batch_pieces.hip): segment gc is rows[gc], the offsets table is not read
 };
+// The piece path of the batch decode (zgpu_inflate_batch_pieces.hip; the numbers behind it: zgpu_inflate_pieces_plan.h).  Positions are those of the call's
+// input buffer: bits for starts, bytes for ends.
+struct PieceTarget { uint64_t lo_bit, hi_bit, limit; }; // one block finder: the bits it scans, the byte behind its item (nothing is read behind it)
+struct PieceRow {                                        // one piece slot
+    uint64_t start, stop; // as two neighbours of a start table (bit 62: the LEN of a stored block); stop of an item's last piece: the bit behind the item
+    uint64_t in_end;      // the byte behind the piece's item
+    uint32_t item;        // its long item in the round's list; kPieceNoItem: the slot is not used
+    uint32_t first;       // 1: the first piece of its item -- nothing lies in front of it
+};
+constexpr uint32_t kPieceNoItem = 0xFFFFFFFFu;
+struct PieceItem {                                       // one long item
+    uint64_t body_lo, in_hi, out_lo, out_hi;
+    uint64_t total;       // chain: bytes the chained pieces decoded to
+    uint64_t end_bit;     // chain: where the final block ends
+    uint32_t k;           // the item's index in the call
+    uint32_t target0, slot0; // its first finder and first piece slot in the round
+    uint32_t ntargets, piece_cap;
+    uint32_t npieces;     // select: slots in use; chain: pieces up to the one with the final block
+    uint32_t clean;       // chain: 1 -- every piece chained, the total fits the room, no page was missing; resolve clears bit 0 through `bad`
+    uint32_t bad;         // resolve: a marker reached in front of the item's first byte
+};
+// the list of a call's long items, filled by the header kernel (min_bytes 0: no item is long, nothing is touched).  hdr: eight counters of the call,
+// zeroed with the call's others -- long items, their finders, their piece slots, their rooms, decoded in pieces, fell back, gathered in this round
+struct PiecesList { unsigned long long *hdr; PieceItem *items; uint64_t min_bytes, max_long; };
+constexpr uint32_t kHdrLong = 0, kHdrTargets = 1, kHdrSlots = 2, kHdrRoom = 3, kHdrClean = 4, kHdrFell = 5, kHdrGathered = 6;
 
 // the header every segment of a wrapped segment call starts with (zgpu_stitch.hip, frame_kernel); bgzf: the last two of its bytes are BSIZE,
 // the block's total length - 1, which frame_kernel fills in per segment

@@ -289,12 +289,30 @@ int output_checksums(zgpu_engine *e, const uint8_t *d_out, uint64_t nbytes, uint
 int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_offsets, uint64_t nchunks, uint32_t chunk_size, uint8_t *d_out, uint64_t out_cap,
                 zgpu_inflate_result *res, hipStream_t st, uint32_t stream_mode = 0, const uint64_t *h_offsets = nullptr, bool open_end = false, uint8_t *h_dst = nullptr, uint64_t h_cap = 0);
 
+// ---- zgpu_inflate_stream.hip: the kernels of a stream decoded in pieces, over the pieces of many streams ----
+void launch_spec_find_table(const uint8_t *d_in, uint64_t in_bytes, const PieceTarget *table, uint32_t ntargets, uint64_t *found, hipStream_t st);
+void launch_spec_resolve_items(const SpecArgs &sp, uint32_t nslots, uint32_t nitems, const uint2 *ranges, const uint8_t *entry, uint8_t *windows, const uint64_t *out_start,
+                               PieceItem *items, uint8_t *d_out, hipStream_t st);
+
+// ---- zgpu_inflate_batch_pieces.hip: the long items of a blocking batch decode, in pieces ----
+struct BatchPiecesKnobs { uint64_t min_bytes, round_bytes; };
+BatchPiecesKnobs batch_pieces_knobs(); // ZGPU_BATCH_PIECES_MIN_BYTES, ZGPU_BATCH_PIECES_ROUND_BYTES, read at EVERY call (the tests switch them within one process)
+uint64_t batch_pieces_count(int which); // 0: items decoded in pieces, 1: long items that fell back to the one-workgroup decoder
+size_t batch_pieces_scratch_bytes(uint64_t max_long); // the room the piece path wants at `scr` (256-byte aligned) for a call with room for max_long long items
+PieceItem *batch_pieces_items(uint8_t *scr);           // ... and where the list the header kernel fills (PiecesList::items) lies in it
+// d_hdr: the call's eight counters (PiecesList::hdr) and hdr what the caller read of them behind the header kernel (hdr[kHdrLong]: the number of long
+// items, not 0).  Round by round find, select, decode, chain, windows and resolve over the pieces of all long items, the records of the clean ones to
+// status[k], the others through one more kInfBatch launch; states[k].code of every long item is put back to the header's ZGPU_OK (the caller's first
+// merge has put the empty segment's verdict there), so that the caller's second merge takes the record.  Ends with a read-back of the counters
+int batch_pieces_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t max_long, uint8_t *scr, unsigned long long *d_hdr,
+                     const unsigned long long *hdr, BatchItemState *states, InfStatus *status, uint64_t round_bytes, int ring_kb, hipStream_t st);
+
 // ---- zgpu_inflate_batch.hip ----
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,
                       const uint64_t *d_out_off, zgpu_inflate_item *d_items, uint64_t *nfailed, hipStream_t st);
 int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,
                              uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_lo, const uint64_t *d_out_hi, zgpu_inflate_item *d_items, uint64_t *nfailed,
-                             const BatchItemState **states, hipStream_t st);
+                             const BatchItemState **states, hipStream_t st, bool no_pieces = false);
 int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, uint64_t *nfailed,
                             hipStream_t st);
 int inflate_batch_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, zgpu_inflate_item *d_items,

@@ -293,7 +293,7 @@ static int gzip_inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_byt
     const BatchItemState *states = nullptr;
     uint64_t nfailed = 0;
     if ((rc = inflate_batch_run_ranges(e, d_in, in_bytes, e->bz_pos, e->gz_in_end, ncand, ZGPU_WRAP_GZIP, 0, d_out, out_cap, e->gz_trial, e->gz_trial + 1, e->gz_items, &nfailed,
-                                       &states, st)))
+                                       &states, st, /* no_pieces: the candidates overlap in the input */ true)))
         return rc;
     // ---- link, reach, order ----
     hipLaunchKernelGGL(gzip_link_kernel, dim3(ngrid), dim3(256), 0, st, states, e->gz_items.p, e->bz_pos.p, nc, in_bytes, e->gz_next.p, e->bz_jump_a.p, e->bz_reach.p);

@@ -90,6 +90,9 @@ __device__ inline void block_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0
 // the finder believes in -- and ends at the first block boundary at or behind bit offsets[gc + 1], or with the final block; nothing is known about
 // the 32 KiB in front of it, so the ring holds 16-bit symbols (byte, or marker = index into that unknown window) and goes to pages of
 // kOutHalf symbols taken from a pool as it fills, the segment's place in the output being unknown too.
+// SPEC with sp.rows (the pieces of MANY streams, zgpu_inflate_batch_pieces.hip): segment gc is rows[gc] -- its start and stop bits, the byte behind ITS
+// stream (no read and no stop bit lies behind it, where the next stream's bytes are) and whether it is its stream's first piece (then nothing lies in
+// front of it: reach is the dictionary's, which a batch does not have).  A row that belongs to no item ends its workgroup before the first barrier.
 // RING: bytes of output the workgroup keeps in LDS.  32768 is the farthest a distance reaches: every match copies from the ring.  A smaller ring
 // (chunks placed directly at their offset of the destination only) lets more segments share a CU; a match that reaches farther back than RING reads its
 // source from the destination itself, where every byte older than the ring has been flushed: the lanes that hold such matches ask for their first 32 bytes
@@ -149,7 +152,13 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     const uint64_t gc = chunk0 + c;
     const uint32_t start_bits = stream_mode >> 8; // (a whole-stream call: the stream begins at that bit of its first byte)
     stream_mode &= 255u;
-    uint64_t seg_lo = BATCH ? offsets[4 * gc] : offsets[gc], seg_hi = BATCH ? offsets[4 * gc + 1] : offsets[gc + 1];
+    // SPEC, the pieces of many streams (sp.rows): the segment's two starts, the end of its own stream and whether anything lies in front of it come from
+    // its row; a slot that is not in use ends here, before the first barrier
+    const bool rowed = SPEC && sp.rows != nullptr;
+    if (rowed && sp.rows[gc].item == kPieceNoItem) return;
+    uint64_t seg_lo = rowed ? sp.rows[gc].start : BATCH ? offsets[4 * gc] : offsets[gc], seg_hi = rowed ? sp.rows[gc].stop : BATCH ? offsets[4 * gc + 1] : offsets[gc + 1];
+    const uint64_t spec_end = rowed ? sp.rows[gc].in_end : in_bytes; // SPEC: the byte behind the stream the segment belongs to
+    const bool spec_first = rowed ? sp.rows[gc].first != 0 : gc == 0; // SPEC: the stream's first segment
     uint32_t bit_lead = 0, stop_bits = 0xFFFFFFFFu; // SPEC: bits of the first byte in front of the start; where the next segment starts, in bits from seg_lo
     bool bad_table;
     bool at_len = false; // SPEC: the piece starts at the LEN field of a stored block (its header bits lie in front, the piece before checks them)
@@ -158,8 +167,8 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
         // boundary that can be that block's: 3 header bits and up to 7 of padding in front of LEN
         at_len = (seg_lo >> 62) & 1u;
         const uint64_t s0 = seg_lo & ~(3ull << 62), s1 = ((seg_hi >> 62) & 1u) ? (seg_hi & ~(3ull << 62)) - 10 : seg_hi;
-        bad_table = s0 >= s1 || s1 > in_bytes * 8 || s1 - (s0 & ~7ull) >= (1ull << 31);
-        seg_lo = s0 >> 3; seg_hi = in_bytes - seg_lo < (1ull << 28) ? in_bytes : seg_lo + (1ull << 28);
+        bad_table = s0 >= s1 || s1 > spec_end * 8 || spec_end > in_bytes || s1 - (s0 & ~7ull) >= (1ull << 31);
+        seg_lo = s0 >> 3; seg_hi = spec_end - seg_lo < (1ull << 28) ? spec_end : seg_lo + (1ull << 28);
         bit_lead = (uint32_t)(s0 & 7u); stop_bits = bad_table ? 0u : (uint32_t)(s1 - seg_lo * 8);
     } else {
         // the table may arrive next to the data from anywhere: an entry that does not lie inside the input, runs backwards or is longer than
@@ -179,7 +188,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     const uint32_t chunk_size = compact ? kChunkMax : whole ? 0xFFFF0000u : chunk_size_arg;
     // a preset dictionary (inflateSetDictionary, inflate.c:1200-1236) is what the window holds before the first byte: in the ring it
     // sits right below position 0, and the first segment may reach that much farther back
-    const uint32_t reach = BATCH ? 0u : (gc == 0) ? dict_len : SPEC ? kOutRing : 0u;
+    const uint32_t reach = BATCH ? 0u : (SPEC ? spec_first : gc == 0) ? dict_len : SPEC ? kOutRing : 0u;
     if (threadIdx.x == 0) { L.abort_flag = 0; L.end_bits = 0; L.end_final = 0; }
     INF_T0();
 
@@ -465,7 +474,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     uint32_t o = 0;       // bytes produced
     if (SPEC) {
         for (uint32_t i = lane; i < kOutRing; i += 64) L.out[i] = (ring_t)(0x8000u | i); // slot i, never written, is byte i of the window in front
-        if (gc == 0) for (uint32_t i = lane; i < dict_len; i += 64) L.out[(kOutRing - dict_len + i) & (kOutRing - 1)] = dict[i];
+        if (spec_first) for (uint32_t i = lane; i < dict_len; i += 64) L.out[(kOutRing - dict_len + i) & (kOutRing - 1)] = dict[i];
     } else
     for (uint32_t i = lane; i < reach; i += 64) L.out[(kOutRing - reach + i) & (kOutRing - 1)] = dict[i];
     uint32_t flushed = 0; // bytes already copied from the LDS ring to the destination (a multiple of kOutHalf until the end)

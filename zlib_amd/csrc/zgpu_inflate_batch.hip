@@ -1,13 +1,15 @@
 // zgpu_inflate_batch.hip -- batch of independent streams (zgpu_inflate_batch_*): item k = in[in_off[k], in_off[k+1]) -> out[out_off[k], out_off[k+1]), every
 // item a stream of its own with its own verdict.  The header kernel reads each item's wrapper (qcsrc/inflate.c:589-760), the decoder (zgpu_inflate.hip) runs
 // in BATCH mode (one workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and
-// the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.  The sizing pass and the integrity test (further down) run
+// the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.  Items of 128 KiB of deflate data or more are decoded in
+// pieces instead (zgpu_inflate_batch_pieces.hip), blocking decode only, and rejoin the chain at the merge kernel.  The sizing pass and the integrity test (further down) run
 // the same header kernel and the decoder in its SIZES / VERIFY mode: neither has a destination, the second still has its trailers compared.
 // The stream-ordered calls (zgpu_inflate_batch_*_enqueue, at the end) put the same chains on the caller's stream with the caller's workspace in place of
 // the engine's scratch and read nothing back; their decode runs the decoder in its FOLD mode, which checks the bytes while it stores them.
 #include "zgpu_common.h"
 #include "zgpu_engine.h"
 #include "zgpu_inflate_batch_plan.h"
+#include "zgpu_inflate_pieces_plan.h"
 #include "../../include/zamd_gpu.h"
 #include <cstring>
 #include <vector>
@@ -28,9 +30,14 @@ __device__ inline uint32_t crc_bytes(uint32_t c, const uint8_t *p, uint64_t n) /
 // bad[0] |= 1: an offsets table that runs backwards or leaves its buffer (a bad argument of the call; such an item is made empty here).
 // Item k reads in[in_lo[k], in_hi[k]) and owns out[out_lo[k], out_hi[k]): four tables, so that a caller whose items overlap (zgpu_gzip.hip) can say
 // so; an offsets table of n + 1 entries is (off, off + 1).
+// pl (the blocking decode with long items in pieces, zgpu_inflate_batch_pieces.hip): an item whose header is fine and whose body -- what lies behind the
+// header, trailer included -- is long (pieces_long) leaves the segment table for the list of long items: its entry is made empty, so the one-workgroup
+// decoder's launch over the table does nothing for it, and its record there is overwritten by the piece path.  The list's order is that of the
+// atomic counter, not the items': nothing depends on it.  A list that is full (max_long = in_bytes / min_bytes: only items that overlap pass it) keeps
+// the rest where they are.
 __global__ void __launch_bounds__(256) batch_header_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *in_lo, const uint64_t *in_hi, uint64_t n,
                                                            uint32_t wrap, uint64_t out_cap, const uint64_t *out_lo, const uint64_t *out_hi, uint64_t *seg,
-                                                           BatchItemState *items, uint32_t *bad)
+                                                           BatchItemState *items, uint32_t *bad, PiecesList pl = PiecesList{})
 {
     const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -78,6 +85,16 @@ __global__ void __launch_bounds__(256) batch_header_kernel(const uint8_t *__rest
     BatchItemState s{};
     s.in_lo = lo; s.in_hi = hi; s.body_lo = lo + pos; s.out_lo = ol; s.kind = kind; s.code = code; s.msg = msg;
     items[k] = s;
+    if (pl.min_bytes && code == ZGPU_OK && pieces_long(hi - body, pl.min_bytes)) {
+        const unsigned long long j = atomicAdd(&pl.hdr[kHdrLong], 1ull);
+        if (j >= pl.max_long) { atomicAdd(&pl.hdr[kHdrLong], ~0ull); return; } // (no room in the list: the count goes back, the item stays with the one-workgroup decoder)
+        const PiecesGeom g = pieces_geom(hi - body);
+        PieceItem it{};
+        it.body_lo = body; it.in_hi = hi; it.out_lo = ol; it.out_hi = oh; it.k = (uint32_t)k; it.ntargets = g.ntargets; it.piece_cap = g.piece_cap;
+        pl.items[j] = it;
+        seg[4 * k] = 0; seg[4 * k + 1] = 0; seg[4 * k + 2] = 0; seg[4 * k + 3] = 0;
+        atomicAdd(&pl.hdr[kHdrTargets], (unsigned long long)g.ntargets); atomicAdd(&pl.hdr[kHdrSlots], (unsigned long long)g.piece_cap); atomicAdd(&pl.hdr[kHdrRoom], (unsigned long long)(oh - ol));
+    }
 }
 
 // the decoder's verdict behind the header's; how many 64 KiB pieces of output the item's checks read
@@ -134,9 +151,10 @@ struct BatchScratch {
     uint64_t *seg; BatchItemState *items; InfStatus *status;
     unsigned long long *cnt; // 256 bytes: [0] pieces (a packed call: the layout's total), [1] failed items, [2] bad offsets
     uint64_t *tab; uint32_t *map; ChunkMeta *meta; // decode only: the piece boundaries, the piece list, the pieces' checksums (verify: meta alone, the items' checksums)
+    uint8_t *long_items;                           // decode with long items in pieces only: the scratch of zgpu_inflate_batch_pieces.hip
 };
 enum BatchScratchKind { kScratchSizes, kScratchDecode, kScratchVerify };
-static int batch_scratch(zgpu_engine *e, uint64_t n, BatchScratchKind kind, uint64_t max_pieces, BatchScratch *s)
+static int batch_scratch(zgpu_engine *e, uint64_t n, BatchScratchKind kind, uint64_t max_pieces, BatchScratch *s, size_t long_bytes = 0)
 {
     Carve at;
     const bool decode = kind == kScratchDecode;
@@ -144,6 +162,7 @@ static int batch_scratch(zgpu_engine *e, uint64_t n, BatchScratchKind kind, uint
     size_t o_tab = 0, o_map = 0, o_meta = 0;
     if (decode) { o_tab = at((max_pieces + n + 1) * 8); o_map = at(max_pieces * 4); o_meta = at(max_pieces * sizeof(ChunkMeta)); }
     if (kind == kScratchVerify) o_meta = at(n * sizeof(ChunkMeta));
+    const size_t o_long = long_bytes ? at(long_bytes) : 0;
     if (e->inf_status.reserve(e, at.off)) return ZGPU_MEM_ERROR;
     uint8_t *scr = e->inf_status;
     *s = BatchScratch{};
@@ -151,6 +170,7 @@ static int batch_scratch(zgpu_engine *e, uint64_t n, BatchScratchKind kind, uint
     s->status = reinterpret_cast<InfStatus *>(scr + o_status); s->cnt = reinterpret_cast<unsigned long long *>(scr + o_cnt);
     if (decode) { s->tab = reinterpret_cast<uint64_t *>(scr + o_tab); s->map = reinterpret_cast<uint32_t *>(scr + o_map); }
     if (kind != kScratchSizes) s->meta = reinterpret_cast<ChunkMeta *>(scr + o_meta);
+    if (long_bytes) s->long_items = scr + o_long;
     return ZGPU_OK;
 }
 
@@ -164,9 +184,13 @@ int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, co
 // The same with every item's input end and output end given on their own (device tables of n entries each): items may overlap in the input.
 // *states (optional): the items' BatchItemState records in the engine's scratch, good until the next inflate call -- `used` and `out_bytes` of an
 // item whose range was too small (ZGPU_BUF_ERROR) are there.
+// Long items (a deflate body of ZGPU_BATCH_PIECES_MIN_BYTES or more, 128 KiB unless set; 0: none) are decoded in pieces by zgpu_inflate_batch_pieces.hip,
+// the pieces of all of them in shared launches; the short ones, and the long ones that fall back, by the one-workgroup decoder as ever.  A call whose
+// whole input is shorter than the threshold is launch for launch what it was.  no_pieces: the caller's items overlap in the input (the trial decode of
+// zgpu_gzip.hip, most of whose candidates are no members at all): every item to the one-workgroup decoder.
 int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_lo, const uint64_t *d_in_hi, uint64_t n, int wrap, uint32_t checks,
                              uint8_t *d_out, uint64_t out_cap, const uint64_t *d_out_lo, const uint64_t *d_out_hi, zgpu_inflate_item *d_items, uint64_t *nfailed,
-                             const BatchItemState **states, hipStream_t st)
+                             const BatchItemState **states, hipStream_t st, bool no_pieces)
 {
     if (!e) return ZGPU_STREAM_ERROR;
     if (nfailed) *nfailed = 0;
@@ -179,12 +203,18 @@ int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     // the check each item's wrapper needs is always computed (AUTO: both), the others when asked for
     const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
     const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    // long items in pieces: only a call whose input can hold one (the block finder reads the input in 16-byte vectors: an input that is not aligned goes the old way)
+    const BatchPiecesKnobs kn = batch_pieces_knobs();
+    const bool pieces = !no_pieces && kn.min_bytes && in_bytes >= kn.min_bytes && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
+    const uint64_t max_long = pieces ? (in_bytes / kn.min_bytes < n ? in_bytes / kn.min_bytes : n) : 0;
     BatchScratch s;
-    if (int rc = batch_scratch(e, n, kScratchDecode, (out_cap >> 16) + n, &s)) return rc;
+    if (int rc = batch_scratch(e, n, kScratchDecode, (out_cap >> 16) + n, &s, pieces ? batch_pieces_scratch_bytes(max_long) : 0)) return rc;
     ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
     const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    unsigned long long *d_hl = s.cnt + 8; // the piece path's eight counters: zeroed with the call's, fetched with them
+    const PiecesList pl = pieces ? PiecesList{d_hl, batch_pieces_items(s.long_items), kn.min_bytes, max_long} : PiecesList{};
     hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_lo, d_in_hi, n, (uint32_t)wrap, out_cap, d_out_lo, d_out_hi, s.seg, s.items,
-                       reinterpret_cast<uint32_t *>(s.cnt + 2));
+                       reinterpret_cast<uint32_t *>(s.cnt + 2), pl);
     const int ring_kb = inflate_ring_kb(); // (items go straight to their place: the small rings serve them as they serve chunks)
     hipEvent_t ev{};
     prof_span_begin(e, st, &ev);
@@ -193,13 +223,24 @@ int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
         launch_inflate_decode(kInfBatch, ring_kb, InfLaunch{d_in, in_bytes, s.seg, c0, nb, d_out, out_cap, s.status + c0}, SpecArgs{}, st);
     }
     prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
-    hipLaunchKernelGGL(batch_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
-    hipLaunchKernelGGL(batch_piece_scan_kernel, dim3(1), dim3(1024), 0, st, s.items, n, s.cnt);
-    hipLaunchKernelGGL(batch_piece_fill_kernel, dim3(ngrid), dim3(256), 0, st, s.items, n, s.tab, s.map);
-    ZGPU_HIP_CHECK(hipGetLastError());
-    unsigned long long h[3] = {0, 0, 0};
-    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, sizeof h, hipMemcpyDeviceToHost, st));
-    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    unsigned long long h[16] = {};
+    const unsigned long long *hl = h + 8;
+    // The call's one round trip before the checks.  With long items possible it also fetches their number (the header kernel has counted them: a call that
+    // has none pays 104 bytes more of this copy and nothing else); when there are some, the piece path runs now, the long items' records replace
+    // the empty ones the decoder's launch left, and the merge, the piece table and the round trip are taken again.
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(batch_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
+        hipLaunchKernelGGL(batch_piece_scan_kernel, dim3(1), dim3(1024), 0, st, s.items, n, s.cnt);
+        hipLaunchKernelGGL(batch_piece_fill_kernel, dim3(ngrid), dim3(256), 0, st, s.items, n, s.tab, s.map);
+        ZGPU_HIP_CHECK(hipGetLastError());
+        ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, (pieces && pass == 0) ? sizeof h : 3 * sizeof h[0], hipMemcpyDeviceToHost, st));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+        if (h[2] || pass == 1 || !pieces || hl[kHdrLong] == 0) break;
+        prof_span_begin(e, st, &ev);
+        const int prc = batch_pieces_run(e, d_in, in_bytes, d_out, out_cap, max_long, s.long_items, d_hl, hl, s.items, s.status, kn.round_bytes, ring_kb, st);
+        prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+        if (prc) return prc;
+    }
     if (h[2]) { collect_spans(e); return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range"); }
     if (h[0]) {
         ChunkGeom g{}; g.in = d_out; g.in_bytes = out_cap; g.seg_off = s.tab; g.chunk0 = 0; g.final_chunk = ~0ull; g.chunk_size = kChunkMax;
@@ -209,7 +250,7 @@ int inflate_batch_run_ranges(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     }
     launch_batch_finish(s.items, n, s.meta, d_in, do_adler, do_crc, d_items, s.cnt + 1, st);
     ZGPU_HIP_CHECK(hipGetLastError());
-    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, 3 * sizeof h[0], hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     collect_spans(e);
     if (nfailed) *nfailed = h[1];

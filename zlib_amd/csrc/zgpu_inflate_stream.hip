@@ -113,14 +113,20 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_find_time(unsi
 #else
 #define FT(i) do { } while (0)
 #endif
-__global__ void __launch_bounds__(64) spec_find_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t spacing, uint32_t ntargets, uint64_t *found)
+// table (the finders of MANY streams, zgpu_inflate_batch_pieces.hip): finder blockIdx.x scans bits [lo_bit, hi_bit) of the buffer, lo_bit a multiple of 128,
+// and its stream ends at byte `limit`, which stands in for in_bytes in every bound below: a finder never looks past the item it belongs to.
+__global__ void __launch_bounds__(64) spec_find_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, uint64_t spacing, uint32_t ntargets, uint64_t *found,
+                                                       const PieceTarget *__restrict__ table = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     InflateLdsFind &L = *reinterpret_cast<InflateLdsFind *>(lds_raw);
     const uint32_t t = blockIdx.x + 1, lane = threadIdx.x;
     if (t > ntargets) return;
-    const uint64_t total_bits = in_bytes * 8, lo_bit = (uint64_t)t * spacing * 8;
-    const uint64_t hi_bit = (uint64_t)(t + 1) * spacing * 8 < total_bits ? (uint64_t)(t + 1) * spacing * 8 : total_bits;
+    const uint64_t buf_bytes = in_bytes;
+    if (table) { const uint64_t lim = table[t - 1].limit; in_bytes = lim < in_bytes ? lim : in_bytes; }
+    const uint64_t total_bits = in_bytes * 8, lo_bit = table ? table[t - 1].lo_bit : (uint64_t)t * spacing * 8;
+    const uint64_t hi_raw = table ? table[t - 1].hi_bit : (uint64_t)(t + 1) * spacing * 8;
+    const uint64_t hi_bit = hi_raw < total_bits ? hi_raw : total_bits;
     const uint32_t *g32 = reinterpret_cast<const uint32_t *>(in); // (the input buffer is a device allocation: aligned)
     const uint64_t gdwords = (in_bytes + 3) >> 2;
     uint64_t result = ~0ull;
@@ -170,9 +176,9 @@ __global__ void __launch_bounds__(64) spec_find_kernel(const uint8_t *__restrict
     };
     uint64_t stored = ~0ull;
     {
-        const uint64_t lo_byte = (uint64_t)t * spacing, hi_byte = hi_bit >> 3;
+        const uint64_t lo_byte = lo_bit >> 3, hi_byte = hi_bit >> 3;
         for (uint64_t o0 = lo_byte; o0 < hi_byte && stored == ~0ull; o0 += 256) {
-            const uint64_t o = o0 + lane * 4, wi = o >> 2; // (lo_byte is a multiple of 4096, t >= 1: wi >= 1)
+            const uint64_t o = o0 + lane * 4, wi = o >> 2; // (lo_byte is a multiple of 4096 -- table: of 16, behind its item's first byte --, t >= 1: wi >= 1)
             const uint32_t dp = wi - 1 < gdwords ? g32[wi - 1] : 0u, d0 = wi < gdwords ? g32[wi] : 0u, d1 = wi + 1 < gdwords ? g32[wi + 1] : 0u;
             uint32_t hit = 0, wsel = 0;
 #pragma unroll
@@ -204,7 +210,7 @@ __global__ void __launch_bounds__(64) spec_find_kernel(const uint8_t *__restrict
     // the bytes to scan come through LDS, kScanBytes at a time
     uint32_t *scan = reinterpret_cast<uint32_t *>(L.out);
     const uint4 *g128 = reinterpret_cast<const uint4 *>(in);
-    const uint64_t gvecs = (in_bytes + 15) >> 4; // (the allocation behind `in` is padded: ensure_stage)
+    const uint64_t gvecs = table ? buf_bytes >> 4 : (in_bytes + 15) >> 4; // (the allocation behind `in` is padded: ensure_stage; table: the caller's buffer, whole vectors of it only)
     for (uint64_t blk = lo_bit; blk < hi_bit && result == ~0ull; blk += kScanBytes * 8) {
         wave_sync();
 #pragma unroll
@@ -303,12 +309,17 @@ __device__ inline uint4 lookup8(uint4 q, const uint16_t *prev) // eight symbols;
     }
     return make_uint4(ws[0], ws[1], ws[2], ws[3]);
 }
-__global__ void __launch_bounds__(1024) spec_window_rel_kernel(uint16_t *tails, uint32_t nseg, uint32_t group)
+// ranges (the pieces of MANY streams, zgpu_inflate_batch_pieces.hip): workgroup g composes pieces [ranges[g].x, ranges[g].y), the chained pieces of one item --
+// the composition restarts at every item's first piece, in front of which nothing lies, so an item's relative windows are its windows already and
+// spec_window_abs_kernel, given one entry of zeros for all (group = 0), only turns them into bytes.  spec_window_grp_kernel has nothing to do there.
+// Termination: one step per piece of the range, which the chain kernel bounds by the item's slots.
+__global__ void __launch_bounds__(1024) spec_window_rel_kernel(uint16_t *tails, uint32_t nseg, uint32_t group, const uint2 *__restrict__ ranges = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     uint16_t *win = reinterpret_cast<uint16_t *>(lds_raw); // two windows of kOutRing symbols
-    const uint32_t tid = threadIdx.x, first = blockIdx.x * group, last = first + group < nseg ? first + group : nseg;
-    if (first >= nseg) return;
+    const uint32_t tid = threadIdx.x, first = ranges ? ranges[blockIdx.x].x : blockIdx.x * group;
+    const uint32_t last_raw = ranges ? ranges[blockIdx.x].y : first + group, last = last_raw < nseg ? last_raw : nseg;
+    if (first >= last) return;
     constexpr uint32_t kPer = kOutRing / 8 / 1024;
     uint4 nxt[kPer];
 #pragma unroll
@@ -372,7 +383,7 @@ __global__ void __launch_bounds__(256) spec_window_abs_kernel(const uint16_t *__
 {
     const uint32_t i = blockIdx.x;
     if (i >= nseg) return;
-    const uint8_t *e = entry + (uint64_t)(i / group) * kOutRing;
+    const uint8_t *e = entry + (uint64_t)(group ? i / group : 0u) * kOutRing; // (group 0: one entry for every piece)
     const uint4 *t4 = reinterpret_cast<const uint4 *>(tails + (uint64_t)i * kOutRing);
     for (uint32_t v = threadIdx.x; v < kOutRing / 8; v += 256) {
         const uint4 q = t4[v];
@@ -391,20 +402,32 @@ __global__ void __launch_bounds__(256) spec_window_abs_kernel(const uint16_t *__
 // One workgroup per page of symbols: to its place in the output, markers through the window of the piece in front.
 __global__ void __launch_bounds__(256) spec_resolve_kernel(const uint16_t *__restrict__ mid, const uint64_t *__restrict__ page_owner, uint32_t npages, const SpecEnd *__restrict__ ends,
                                                            uint32_t nseg, const uint8_t *__restrict__ windows, const uint64_t *__restrict__ out_start, uint32_t dict_len,
-                                                           uint8_t *__restrict__ out, uint64_t out_cap, uint32_t *flag)
+                                                           uint8_t *__restrict__ out, uint64_t out_cap, uint32_t *flag, const PieceRow *__restrict__ rows = nullptr,
+                                                           PieceItem *items = nullptr, const uint32_t *npages_dev = nullptr)
 {
+    // rows, items (the pieces of MANY streams, zgpu_inflate_batch_pieces.hip): out_start[seg] counts from the first byte of the piece's item, "not the first
+    // segment" is "not a first piece", the output ends where the item's range ends, and a marker that reaches in front of the item's first byte sets the
+    // item's flag.  Pieces of an item whose chain did not hold, or behind its final block, are left out.  npages_dev: the pages taken, read here.
     const uint32_t pg = blockIdx.x;
+    if (npages_dev) npages = npages_dev[0] < npages ? npages_dev[0] : npages;
     if (pg >= npages) return;
     const uint64_t ow = page_owner[pg];
     const uint32_t seg = (uint32_t)(ow >> 32), k = (uint32_t)ow;
     if (seg >= nseg) return; // a piece behind the end of the stream
+    bool head = seg == 0;
+    uint64_t base = 0;
+    if (rows) {
+        const uint32_t it = rows[seg].item;
+        if (it == kPieceNoItem || !items[it].clean || seg - items[it].slot0 >= items[it].npieces) return;
+        head = rows[seg].first != 0; base = items[it].out_lo; out_cap = items[it].out_hi; flag = &items[it].bad;
+    }
     const uint32_t len = ends[seg].out_bytes, from = k * kOutHalf;
     if (from >= len) return;
     const uint32_t n = len - from < kOutHalf ? len - from : kOutHalf;
-    const uint64_t at = out_start[seg] + from;
-    const uint64_t have_prev = seg == 0 ? 0 : out_start[seg] + dict_len;
+    const uint64_t at = base + out_start[seg] + from;
+    const uint64_t have_prev = head ? 0 : out_start[seg] + dict_len;
     const uint32_t vf_prev = have_prev >= kOutRing ? 0u : kOutRing - (uint32_t)have_prev;
-    const uint8_t *win = seg ? windows + (uint64_t)(seg - 1) * kOutRing : windows;
+    const uint8_t *win = !head ? windows + (uint64_t)(seg - 1) * kOutRing : windows;
     const uint16_t *src = mid + (uint64_t)pg * kOutHalf;
     uint32_t bad = 0;
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
@@ -412,11 +435,38 @@ __global__ void __launch_bounds__(256) spec_resolve_kernel(const uint16_t *__res
         uint32_t byte = sym & 255u;
         if (sym & 0x8000u) {
             const uint32_t idx = sym & 0x7FFFu;
-            if (seg != 0 && idx >= vf_prev) byte = win[idx]; else { byte = 0; bad = 1; }
+            if (!head && idx >= vf_prev) byte = win[idx]; else { byte = 0; bad = 1; }
         }
         if (at + i < out_cap) out[at + i] = (uint8_t)byte;
     }
     if (bad) atomicOr(flag, 1u);
+}
+
+static void spec_opt_in()
+{
+    static bool opt_in = false;
+    if (opt_in) return;
+    hipFuncSetAttribute(reinterpret_cast<const void *>(spec_find_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFind));
+    hipFuncSetAttribute(reinterpret_cast<const void *>(spec_window_rel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kOutRing));
+    opt_in = true;
+}
+
+// The same kernels over the pieces of many streams (zgpu_inflate_batch_pieces.hip): the finders of a table; the windows of every item's chained pieces and
+// every page to its place inside its item's range.  `entry`: kOutRing zeros.
+void launch_spec_find_table(const uint8_t *d_in, uint64_t in_bytes, const PieceTarget *table, uint32_t ntargets, uint64_t *found, hipStream_t st)
+{
+    spec_opt_in();
+    if (ntargets) hipLaunchKernelGGL(spec_find_kernel, dim3(ntargets), dim3(64), sizeof(InflateLdsFind), st, d_in, in_bytes, (uint64_t)0, ntargets, found, table);
+}
+void launch_spec_resolve_items(const SpecArgs &sp, uint32_t nslots, uint32_t nitems, const uint2 *ranges, const uint8_t *entry, uint8_t *windows, const uint64_t *out_start,
+                               PieceItem *items, uint8_t *d_out, hipStream_t st)
+{
+    spec_opt_in();
+    if (!nslots || !nitems) return;
+    hipLaunchKernelGGL(spec_window_rel_kernel, dim3(nitems), dim3(1024), 4 * kOutRing, st, sp.tails, nslots, 0u, ranges);
+    hipLaunchKernelGGL(spec_window_abs_kernel, dim3(nslots), dim3(256), 0, st, sp.tails, nslots, 0u, entry, windows);
+    hipLaunchKernelGGL(spec_resolve_kernel, dim3(sp.page_cap), dim3(256), 0, st, sp.mid, sp.page_owner, sp.page_cap, sp.ends, nslots, windows, out_start, 0u, d_out, (uint64_t)0,
+                       static_cast<uint32_t *>(nullptr), sp.rows, items, sp.page_count);
 }
 
 // 0: decoded (res complete); 1: not this way (the caller uses the one-workgroup decoder); anything else: an error of the engine
@@ -438,12 +488,7 @@ static int inflate_spec_run(zgpu_engine *e, const uint8_t *d_in, const uint8_t *
     if (ntargets < 3 && !force) return 1;
     if (e->inf_status.reserve(e, (size_t)ntargets * 16 + 64)) return ZGPU_MEM_ERROR;
     uint64_t *d_found = reinterpret_cast<uint64_t *>(e->inf_status.p);
-    static bool opt_in = false;
-    if (!opt_in) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(spec_find_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFind));
-        hipFuncSetAttribute(reinterpret_cast<const void *>(spec_window_rel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kOutRing));
-        opt_in = true;
-    }
+    spec_opt_in();
     hipEvent_t ev{};
     prof_span_begin(e, st, &ev);
     if (ntargets) hipLaunchKernelGGL(spec_find_kernel, dim3(ntargets), dim3(64), sizeof(InflateLdsFind), st, d_in, in_bytes, fspacing, ntargets, d_found);
@@ -740,7 +785,7 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
 
 extern "C" {
 #pragma GCC visibility push(default)
-uint64_t zgpu_inflate_spec_count(int which) { return which == 0 ? g_spec_done.load() : which == 1 ? g_whole_done.load() : 0; }
+uint64_t zgpu_inflate_spec_count(int which) { return which == 0 ? g_spec_done.load() : which == 1 ? g_whole_done.load() : (which == 2 || which == 3) ? batch_pieces_count(which - 2) : 0; }
 int zgpu_inflate_find_chunks_host(zgpu_engine *e, const void *in, uint64_t in_bytes, uint32_t chunk_size, uint64_t *offsets, uint64_t max_chunks,
                                   uint64_t *nchunks)
 {

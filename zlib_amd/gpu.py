@@ -770,6 +770,10 @@ class Engine:
     def spec_counts(self):
         return int(self.L.zgpu_inflate_spec_count(0)), int(self.L.zgpu_inflate_spec_count(1))
 
+    def batch_piece_counts(self):
+        """(long items of blocking batch decodes that were decoded in pieces, long items that fell back to the one-workgroup decoder), since the library was loaded"""
+        return int(self.L.zgpu_inflate_spec_count(2)), int(self.L.zgpu_inflate_spec_count(3))
+
     def inflate_device(self, d_in, n, d_offsets, nchunks, d_out, out_cap, chunk_size=CHUNK, stream=None):
         res = InflateResult()
         rc = self.L.zgpu_inflate_device(self.h, d_in, n, d_offsets, nchunks, chunk_size, d_out, out_cap, C.byref(res), stream)
