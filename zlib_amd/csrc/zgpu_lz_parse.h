@@ -85,6 +85,32 @@ __device__ inline uint32_t next_bit(const uint32_t *bits, uint32_t x, uint32_t n
     return (w << 5) + (uint32_t)__builtin_ctz(v);
 }
 
+// Stage 3 of the parse, one lane: the block cuts (deflate.c:1620-1626, 1651-1656: after the 16383rd token of a block) and the stored-block veto, from the
+// token words TOK (a bit per token position), their exclusive prefix counts wbase (nw_done words have one) and the match starts MAT (slide_at, base: ParseCtx's)
+__device__ inline void parse_block_cuts(int slide_at, uint32_t base, const uint32_t *TOK, const uint32_t *MAT, const uint32_t *wbase, uint32_t n, uint32_t nwords, uint32_t nw_done,
+                                        uint32_t ntok, ChunkMeta &out)
+{
+    uint32_t nostore = 0, nblk = 0, block_start = 0;
+    for (uint32_t b = 0;; b++) {
+        const uint32_t e = (b + 1) * kBlockTokens - 1; // index of the token that fills block b
+        if (e >= ntok) break;
+        uint32_t lo_w = 0, hi_w = nw_done; // the word holding token e: wbase[lo_w] <= e < wbase[lo_w + 1]
+        while (hi_w - lo_w > 1) { const uint32_t mid = (lo_w + hi_w) >> 1; if (wbase[mid] <= e) lo_w = mid; else hi_w = mid; }
+        uint32_t v = TOK[lo_w];
+        for (uint32_t s2 = e - wbase[lo_w]; s2; s2--) v &= v - 1;
+        const uint32_t pe = (lo_w << 5) + (uint32_t)__builtin_ctz(v);
+        const bool is_mat = (MAT[pe >> 5] >> (pe & 31u)) & 1u;
+        if (!is_mat && pe == n - 1) { nostore |= kFullFinalBlock; break; } // the last byte's literal is emitted behind the loop (deflate.c:1660-1665): no cut, and the full block is the final one
+        // the token is emitted while the loop stands at pe+1; a match leaves it at the next token position
+        uint32_t ns = pe + 1;
+        if (is_mat) { ns = next_bit(TOK, pe + 1, nwords); if (ns == kNone) ns = n; }
+        if ((int)(pe + 1) >= slide_at && block_start + base < kWSize) nostore |= 1u << nblk; // (ParseCtx::slid)
+        nblk++; block_start = ns;
+    }
+    if ((int)n >= (int)(kWSize + kMaxDist) - (int)base && block_start + base < kWSize) nostore |= 1u << nblk; // the check at p == n slides too
+    out.ntok = ntok; out.nostore = nostore; out.in_bytes = n;
+}
+
 #ifdef ZGPU_P2_TIME // debug build only (scripts/p2_time.py): cycles per phase, summed over workgroups (lane 0's clock)
 // (an includer of the header alone -- walk_kernel with its fused tail -- keeps an array and an accessor of its own and names the array in P2_TIME_ARR
 // before it includes the body: a __device__ variable belongs to one translation unit)

@@ -463,27 +463,7 @@
 
     // ---- 3. block cuts (deflate.c:1620-1626, 1651-1656: after the 16383rd token of a block) and the stored-block veto ----
     if (TILE) { if (tid == 0) { meta[c].ntok = ntok; meta[c].in_bytes = (sh_exit > t_h1 ? sh_exit : t_h1) - t_e; } } // (in_bytes: the bytes the tile's tokens cover)
-    else if (tid == 0) {
-        uint32_t nostore = 0, nblk = 0, block_start = 0;
-        for (uint32_t b = 0;; b++) {
-            const uint32_t e = (b + 1) * kBlockTokens - 1; // index of the token that fills block b
-            if (e >= ntok) break;
-            uint32_t lo_w = 0, hi_w = nw_done; // the word holding token e: wbase[lo_w] <= e < wbase[lo_w + 1]
-            while (hi_w - lo_w > 1) { const uint32_t mid = (lo_w + hi_w) >> 1; if (wbase[mid] <= e) lo_w = mid; else hi_w = mid; }
-            uint32_t v = TOK[lo_w];
-            for (uint32_t s2 = e - wbase[lo_w]; s2; s2--) v &= v - 1;
-            const uint32_t pe = (lo_w << 5) + (uint32_t)__builtin_ctz(v);
-            const bool is_mat = (MAT[pe >> 5] >> (pe & 31u)) & 1u;
-            if (!is_mat && pe == n - 1) { nostore |= kFullFinalBlock; break; } // the last byte's literal is emitted behind the loop (deflate.c:1660-1665): no cut, and the full block is the final one
-            // the token is emitted while the loop stands at pe+1; a match leaves it at the next token position
-            uint32_t ns = pe + 1;
-            if (is_mat) { ns = next_bit(TOK, pe + 1, nwords); if (ns == kNone) ns = n; }
-            if (cx.slid(pe + 1) && block_start + cx.base < kWSize) nostore |= 1u << nblk;
-            nblk++; block_start = ns;
-        }
-        if ((int)n >= (int)(kWSize + kMaxDist) - (int)cx.base && block_start + cx.base < kWSize) nostore |= 1u << nblk; // the check at p == n slides too
-        meta[c].ntok = ntok; meta[c].nostore = nostore; meta[c].in_bytes = n;
-    }
+    else if (tid == 0) parse_block_cuts(cx.slide_at, cx.base, TOK, MAT, wbase, n, nwords, nw_done, ntok, meta[c]);
     P2_T(6);
     P2_TEND();
 }

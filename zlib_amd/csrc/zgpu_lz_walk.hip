@@ -3,6 +3,7 @@
 #include "zgpu_lz_sorted.h"
 #define ZGPU_PARSE_HEADER_ONLY
 #include "zgpu_lz_parse.h"
+#include <cstdlib>
 
 namespace zgpu {
 
@@ -67,7 +68,8 @@ static_assert(kWTaper32 == 0 || kWNeuShift <= (kWTaper16 ? 4 : 5), "a short bloc
 // the block map of a chunk of n positions: blocks of kWBlk below b32, of 32 in [b32, b16), of 16 from b16 on (b32 a multiple of 64, b16 of 32)
 struct WalkTaper {
     uint32_t b32, b16, n64, n32, nblk;
-    __host__ __device__ explicit WalkTaper(uint32_t n)
+    // (forced inline: taken in late, the object stayed on the stack -- 32 bytes of scratch that nothing reads -- once the kernel had grown by the whole-chunk tail)
+    __host__ __device__ __forceinline__ explicit WalkTaper(uint32_t n)
     {
         const bool on = n > kWTaperMin && kWTaper32 != 0;
         b32 = on ? (n - kWTaper32) & ~63u : n;
@@ -75,7 +77,7 @@ struct WalkTaper {
         n64 = on ? b32 / 64 : (n + kWBlk - 1) / kWBlk; n32 = (b16 - b32) / 32;
         nblk = n64 + n32 + (n - b16 + 15) / 16;
     }
-    __host__ __device__ uint32_t start(uint32_t b) const { return b < n64 ? b * kWBlk : b < n64 + n32 ? b32 + (b - n64) * 32 : b16 + (b - n64 - n32) * 16; }
+    __host__ __device__ __forceinline__ uint32_t start(uint32_t b) const { return b < n64 ? b * kWBlk : b < n64 + n32 ? b32 + (b - n64) * 32 : b16 + (b - n64 - n32) * 16; }
 };
 extern "C" __attribute__((visibility("default"))) void zgpu_walk_block_map(uint32_t n, uint32_t *out) // (tests: where a chunk's walkers start) b32, b16, blocks
 {
@@ -100,10 +102,13 @@ extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_stats(uns
 #define W_SOUT0() bool ws_out = false
 #define W_SLIVE() do { W_STAT(ws_out ? 9 : 8, __popcll(__builtin_amdgcn_ballot_w64(st != W_DONE))); W_STAT(ws_out ? 11 : 10, 1); } while (0)
 #define W_SOUT() do { ws_out = ws_out || __builtin_amdgcn_ballot_w64(st == W_DONE) != 0; } while (0) // (W_DONE comes from an empty counter alone)
-__device__ unsigned long long walk_log_stats[2]; // walk_kernel<1> (scripts/walk_log_stats.py): 0 games logged, 1 the fullest log of a window
+__device__ unsigned long long walk_log_stats[6]; // walk_kernel<1> (scripts/walk_log_stats.py): 0 games logged, 1 the fullest log of a window; chunks by the tail they
+                                                 // took: 2 the whole-chunk form, 3 the windowed one for their games (more than the capacity), 4 the windowed one behind
+                                                 // a whole-chunk threading that did not hold; 5 chunks of the whole-chunk form whose game starts were fewer
+                                                 // than their log entries (two games logged at one position: must stay 0, zgpu_lz_tail.h stage 2)
 extern "C" __attribute__((visibility("default"))) void zgpu_debug_walk_log_stats(unsigned long long *out, int reset)
 {
-    unsigned long long z[2] = {};
+    unsigned long long z[6] = {};
     hipMemcpyFromSymbol(out, HIP_SYMBOL(walk_log_stats), sizeof z);
     if (reset) hipMemcpyToSymbol(HIP_SYMBOL(walk_log_stats), z, sizeof z);
 }
@@ -257,12 +262,21 @@ __device__ __forceinline__ void tile_exits(uint8_t *pl, const uint32_t *gm, cons
 // Once the walkers are done the neutral bitmap and the waves' rings and slots are dead as well: the parse's arrays lie over all of the workgroup's LDS
 // but the logs' counts -- J .. sh_entry in the first kP2LdsBytes, END behind them.
 static_assert(kP2LogLdsBytes <= kWOffLcnt, "the parse works in the memory of the chunk bytes, the neutral bitmap and the rings");
+} // namespace zgpu
+#include "zgpu_lz_tail.h"
+namespace zgpu {
+// The tail has two forms.  A chunk whose logs hold at most tail_cap games (a kernel argument, kWTailCap at the most: the room of the table of successors
+// by game, zgpu_lz_tail.h) takes the whole-chunk form; a chunk with more -- zeros, short periods, de Bruijn input: 13 to 31 thousand -- takes the windowed
+// one, and so does a chunk whose whole-chunk threading did not hold.  The choice is the workgroup's (the counts are in LDS), made before either form has
+// written anything; both lie over the same LDS and read the same logs.
+constexpr uint32_t kWTailCap = TailLds<kWThreads>::kCap;
+static_assert(TailLds<kWThreads>::kBytes <= kWOffLcnt && kWTailCap >= 12288, "the whole-chunk tail works in the same memory; every chunk of the bench corpora at levels 4-9 fits it (profiles/r07_walk_log_summary.txt)");
 // MODE 3: MODE 2 with the launch's tiles given row by row (TileRow), each tile a tile of its own stream.
 // MODE 1: a chunk, the rest of the parse behind its walkers (FUSE); 2: a TILE of a continuous stream (zgpu_cont.hip) -- walkers start at every possible
 // entry of the tile and at every 64th position of its range [h0, h1), stop at h1, and the workgroup ends with the tile's exit as a function of its entry.
 template <int MODE>
 __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkGeom g, LevelCfg cfg, const uint16_t *__restrict__ S_all, const uint32_t *__restrict__ ir_all,
-                                                            uint32_t *__restrict__ gm_all, uint32_t *__restrict__ gs_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg)
+                                                            uint32_t *__restrict__ gm_all, uint32_t *__restrict__ gs_all, uint32_t *__restrict__ tokens, ChunkMeta *meta, TileGeom tg, uint32_t tail_cap)
 {
     // (gm_all, gs_all: MODE 2 -- the games by position and their bitmaps; MODE 1 -- the logs' records, lrec, and positions, lpos)
     static_assert(MODE == 1 || MODE == 2 || MODE == 3, "a chunk, a tile, a tile of a launch over many streams");
@@ -658,18 +672,29 @@ __global__ void __launch_bounds__(kWThreads, kWThreads / 128) walk_kernel(ChunkG
 #ifdef ZGPU_WALK_STATS
         if (tid < kP2Wins) { atomicAdd(&walk_log_stats[0], (unsigned long long)lcnt[tid]); atomicMax(&walk_log_stats[1], (unsigned long long)lcnt[tid]); }
 #endif
-        constexpr uint32_t kP2Threads = kWThreads;
-        constexpr bool LITE = true, FUSED = true, TILE = false, ROWS = false, LOG = true;
-        const uint2 *recs = nullptr;
-        const uint32_t *gmv_all = nullptr, *gsv_all = nullptr; // (the position-indexed form: tiles only)
-        uint8_t *pl = reinterpret_cast<uint8_t *>(lds);
-        uint16_t *const J = reinterpret_cast<uint16_t *>(pl + kP2OffJ);
-        uint32_t *const HAS = reinterpret_cast<uint32_t *>(pl + kP2OffHAS), *const MARK = reinterpret_cast<uint32_t *>(pl + kP2OffMARK), *const COV = reinterpret_cast<uint32_t *>(pl + kP2OffCOV),
-                 *const MAT = reinterpret_cast<uint32_t *>(pl + kP2OffMAT), *const wbase = reinterpret_cast<uint32_t *>(pl + kP2OffWbase), *const VIS = reinterpret_cast<uint32_t *>(pl + kP2OffVIS),
-                 *const EXITS = reinterpret_cast<uint32_t *>(pl + kP2OffEXITS), *const wave_tot = reinterpret_cast<uint32_t *>(pl + kP2OffWtot);
-        uint32_t &sh_entry = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry), &sh_exit = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry + 4);
-        uint16_t *const END = reinterpret_cast<uint16_t *>(pl + kP2OffEND);
+        uint32_t nlog = 0; // (uniform) games in the chunk's logs
+#pragma unroll
+        for (uint32_t a = 0; a < kP2Wins; a++) nlog += (uint32_t)__builtin_amdgcn_readfirstlane((int)lcnt[a]);
+        const bool whole = tail_cap != 0 && nlog <= tail_cap; // (tail_cap 0: every chunk through the windowed tail)
+        bool done = false;
+        if (whole) done = tail_chunk<kWThreads>(reinterpret_cast<uint8_t *>(lds), lcnt, lpos, lrec, src, n, base, slide_at, tokens + (size_t)c * kChunkMax, meta[c], tid);
+#ifdef ZGPU_WALK_STATS
+        if (tid == 0) atomicAdd(&walk_log_stats[done ? 2 : whole ? 4 : 3], 1ull);
+#endif
+        if (!done) { // the windowed tail (zgpu_lz_parse_body.inc with LOG), from its start
+            constexpr uint32_t kP2Threads = kWThreads;
+            constexpr bool LITE = true, FUSED = true, TILE = false, ROWS = false, LOG = true;
+            const uint2 *recs = nullptr;
+            const uint32_t *gmv_all = nullptr, *gsv_all = nullptr; // (the position-indexed form: tiles only)
+            uint8_t *pl = reinterpret_cast<uint8_t *>(lds);
+            uint16_t *const J = reinterpret_cast<uint16_t *>(pl + kP2OffJ);
+            uint32_t *const HAS = reinterpret_cast<uint32_t *>(pl + kP2OffHAS), *const MARK = reinterpret_cast<uint32_t *>(pl + kP2OffMARK), *const COV = reinterpret_cast<uint32_t *>(pl + kP2OffCOV),
+                     *const MAT = reinterpret_cast<uint32_t *>(pl + kP2OffMAT), *const wbase = reinterpret_cast<uint32_t *>(pl + kP2OffWbase), *const VIS = reinterpret_cast<uint32_t *>(pl + kP2OffVIS),
+                     *const EXITS = reinterpret_cast<uint32_t *>(pl + kP2OffEXITS), *const wave_tot = reinterpret_cast<uint32_t *>(pl + kP2OffWtot);
+            uint32_t &sh_entry = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry), &sh_exit = *reinterpret_cast<uint32_t *>(pl + kP2OffEntry + 4);
+            uint16_t *const END = reinterpret_cast<uint16_t *>(pl + kP2OffEND);
 #include "zgpu_lz_parse_body.inc"
+        }
     }
 }
 
@@ -678,7 +703,9 @@ template <int MODE> static void launch_walk(const ChunkGeom &g, LevelCfg cfg, co
     static bool opt_in = false; // (one per MODE)
     if (!opt_in) { hipFuncSetAttribute(reinterpret_cast<const void *>(walk_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWLds); opt_in = true; }
     uint32_t *games = MODE == 1 ? ws.lrec() : ws.gm(), *starts = MODE == 1 ? reinterpret_cast<uint32_t *>(ws.lpos()) : ws.gs();
-    hipLaunchKernelGGL(walk_kernel<MODE>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, ws.S, ws.ir, games, starts, tokens, meta, tg);
+    uint32_t tail_cap = kWTailCap; // ZGPU_WALK_TAIL_CAP (tests; read per launch): the games a chunk may have to take the whole-chunk tail, 0: none does
+    if (MODE == 1) { const char *v = getenv("ZGPU_WALK_TAIL_CAP"); char *end = nullptr; const unsigned long x = v ? strtoul(v, &end, 10) : 0; if (v && end != v) tail_cap = x < kWTailCap ? (uint32_t)x : kWTailCap; } // (a value without digits is ignored)
+    hipLaunchKernelGGL(walk_kernel<MODE>, dim3(g.nchunks), dim3(kWThreads), kWLds, st, g, cfg, ws.S, ws.ir, games, starts, tokens, meta, tg, tail_cap);
 }
 void launch_walk_chunks(const ChunkGeom &g, LevelCfg cfg, const SortedWs &ws, uint32_t *tokens, ChunkMeta *meta, hipStream_t st) { launch_walk<1>(g, cfg, ws, tokens, meta, TileGeom{}, st); }
 void launch_walk_tiles(const ChunkGeom &g, const TileGeom &tg, LevelCfg cfg, const SortedWs &ws, ChunkMeta *meta, hipStream_t st)
