@@ -311,10 +311,12 @@ def _dynamic(bits, blk):
     _put_tokens(bits, t, canonical_codes(lpad), lpad, canonical_codes(dpad), dpad, blk["eob"])
 
 
-def stream(blocks):
-    """Pack the blocks (in order) into bytes; the last byte is filled up with zeros."""
+def _emit(blocks):
+    """The blocks as fields, and the bit at which each block starts"""
     bits = _Bits()
+    starts = []
     for blk in blocks:
+        starts.append(bits.nbits)
         ty = blk["t"]
         if ty == "bits":
             bits.put(blk["v"], blk["n"])
@@ -337,4 +339,16 @@ def stream(blocks):
             _dynamic(bits, blk)
         else:
             raise ValueError(ty)
-    return bits.pack()
+    return bits, starts
+
+
+def stream(blocks):
+    """Pack the blocks (in order) into bytes; the last byte is filled up with zeros."""
+    return _emit(blocks)[0].pack()
+
+
+def block_starts(blocks):
+    """The bit of `stream(blocks)` at which every block starts (a stored block: its three header bits, the padding and LEN follow), and behind them
+    the bit at which the last block ends."""
+    bits, starts = _emit(blocks)
+    return starts + [bits.nbits]

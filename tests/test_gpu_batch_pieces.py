@@ -2,7 +2,9 @@
 block starts found by search and the pieces of all long items of a call share their launches (zgpu_inflate_batch_pieces.hip); short items, and long ones
 that fall back, go to the one-workgroup decoder as before.  Streams come from Python's zlib.  Bytes, in_used and both checks must be Python's; verdicts on
 damaged, cut and too-large items must be the one-workgroup decoder's, which the same process produces with the feature switched off; Engine.batch_piece_counts()
-says which way the long items went.  Sizes are the smallest that reach the piece path: 150-600 KiB of compressed data per long item."""
+says which way the long items went.  Sizes are the smallest that reach the piece path at its default threshold: 150-600 KiB of compressed data per
+long item.  Smaller ones -- hand-built items of 49-140 KiB behind a lowered threshold, shaped as zlib's encoder never shapes them -- are
+tests/test_gpu_batch_pieces_built.py's."""
 import ctypes as C
 import os
 import struct
