@@ -455,7 +455,9 @@ int zgpu_inflate_stream_host3(zgpu_engine *e, const void *in, uint64_t in_bytes,
 void zgpu_debug_inject_sort_fault(void);
 uint64_t zgpu_inflate_spec_count(int which); /* 0: decoded in pieces, 1: one-workgroup decodes (both: zgpu_inflate_stream_host*);
                                               * 2: long items of blocking batch decodes decoded in pieces, 3: long items of them that fell back
-                                              * to the one-workgroup decoder (zgpu_inflate_batch_*, see there) */
+                                              * to the one-workgroup decoder (zgpu_inflate_batch_*, see there); 4: long items of sizing passes
+                                              * sized in pieces, 5: long items of them that fell back to the one-wave sizing kernel
+                                              * (zgpu_inflate_batch_sizes_*, the sizing half of zgpu_inflate_batch_packed_*) */
 const char *zgpu_inflate_message(uint32_t index);
 /* Preset dictionary of the inflate calls that follow (inflateSetDictionary, qcsrc/inflate.c:1200-1236): the first segment of a
  * call may reach back into its last min(len, 32768) bytes.  Stays set until replaced; len 0 clears it. */
@@ -488,9 +490,10 @@ int zgpu_inflate_set_checks(zgpu_engine *e, uint32_t mask);
  * search, the pieces of all long items of the call in shared launches (zlib_amd/csrc/zgpu_inflate_batch_pieces.hip).  Records and bytes are those of the
  * one-workgroup decoder: a long item whose pieces do not chain cleanly into its room (damage, truncation, a room too small) is decoded again by it,
  * once.  ZGPU_BATCH_PIECES_ROUND_BYTES (default 512 MiB) caps the output room one round of the piece path serves; scratch the engine cannot reserve
- * sends a round's items to the one-workgroup decoder and is no error.  This covers the blocking decode only (these two calls, the decode half of
- * zgpu_inflate_batch_packed_*, zgpu_bgzf_*, the final decode of zgpu_gzip_inflate_*): the *_enqueue calls, the sizing pass and the integrity test
- * give every item to one workgroup (one wave) as before.  zgpu_inflate_spec_count(2) / (3) count the long items decoded in pieces / fallen back. */
+ * sends a round's items to the one-workgroup decoder and is no error.  This covers the blocking decode (these two calls, the decode half of
+ * zgpu_inflate_batch_packed_*, zgpu_bgzf_*, the final decode of zgpu_gzip_inflate_*) and, in a form of its own, the blocking sizing pass (see
+ * zgpu_inflate_batch_sizes_* below): the *_enqueue calls and the integrity test give every item to one workgroup as before.
+ * zgpu_inflate_spec_count(2) / (3) count the long items decoded in pieces / fallen back -- the decode only, also inside a packed call. */
 #define ZGPU_WRAP_RAW 0
 #define ZGPU_WRAP_ZLIB 1
 #define ZGPU_WRAP_GZIP 2
@@ -519,7 +522,15 @@ int zgpu_inflate_batch_host(zgpu_engine *e, const void *in, uint64_t in_bytes, c
  * What it cannot say: it computes no Adler-32 or CRC-32 and compares no ISIZE -- its verdict is the decoder's minus the trailer checks.  An item
  * whose check value or length field is wrong is ZGPU_OK here and ZGPU_DATA_ERROR ("incorrect data check" / "incorrect length check") in a decode.
  * Arguments, limits (< 512 MiB compressed, < 4 GiB decoded per item, no preset dictionary), ZGPU_STREAM_ERROR for offsets that run backwards or
- * leave the buffer and *nfailed are zgpu_inflate_batch_*'s.  One read-back, at the end; the device entry blocks until the records are in d_items. */
+ * leave the buffer and *nfailed are zgpu_inflate_batch_*'s.  One read-back, at the end; the device entry blocks until the records are in d_items.
+ * Long items are sized in pieces too (these two calls and the sizing half of zgpu_inflate_batch_packed_*; not zgpu_inflate_batch_sizes_enqueue): a
+ * piece that starts at a block boundary is counted by one wave with no knowledge of what lies in front of it, and a chain over the item's pieces
+ * settles what a piece cannot -- that each ended where the next starts, the total, and that no match of a later piece reaches in front of the item's
+ * first byte.  An item that does not come out clean is sized again by the one-wave kernel, once: every record is the one-wave kernel's.  The threshold
+ * is ZGPU_BATCH_PIECES_SIZES_MIN_BYTES, read at every call; not set, it follows ZGPU_BATCH_PIECES_MIN_BYTES (131072; 0: no item is long).
+ * ZGPU_BATCH_PIECES_SIZES_ROUND_SLOTS caps the piece slots of one round (not set: no cap; the tests' switch); ZGPU_BATCH_PIECES_ROUND_BYTES has no
+ * meaning here, sizing has no rooms.  A call without long items pays 104 bytes more of the read-back it makes anyway, nothing else; one with long
+ * items a second read-back.  zgpu_inflate_spec_count(4) / (5) count the long items sized in pieces / fallen back. */
 int zgpu_inflate_batch_sizes_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
                                     zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream);
 int zgpu_inflate_batch_sizes_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,

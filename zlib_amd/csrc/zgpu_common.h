@@ -76,6 +76,7 @@ struct SpecArgs {
     uint16_t *tails;      // per segment: the ring when it ended, oldest symbol first = the last 32 KiB of the segment's output
     SpecEnd *ends;
     const struct PieceRow *rows = nullptr; // the pieces of MANY streams (zgpu_inflate_batch_pieces.hip): segment gc is rows[gc], the offsets table is not read
+    uint32_t *need = nullptr; // the sizing form of the piece path only (kInfPieceSizes): per segment, how far its matches reach in front of its own first byte
 };
 // The piece path of the batch decode (zgpu_inflate_batch_pieces.hip; the numbers behind it: zgpu_inflate_pieces_plan.h).  Positions are those of the call's
 // input buffer: bits for starts, bytes for ends.

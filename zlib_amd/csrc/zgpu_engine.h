@@ -280,9 +280,10 @@ struct InfLaunch {
 // kInfPieces: always the 32 KiB ring of 16-bit symbols; kInfSizes: no ring at all; kInfVerify: the 32 KiB ring and no destination -- `out` is not
 // used, `out_cap` carries the checks to compute (bit 0 Adler-32, bit 1 CRC-32) and `meta` takes one record per item: out_bytes, adler_a, adler_b, crc;
 // kInfBatchFold: kInfBatch that also folds what it stores (ring_kb counts, as for kInfBatch) -- `out` and `out_cap` are the destination's, `checks`
-// says what to fold, `meta` takes one record per item as for kInfVerify
-enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify, kInfBatchFold };
-constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes, kInfPieces or kInfVerify launch: the kind fixes the ring, the launcher does not look at the value
+// says what to fold, `meta` takes one record per item as for kInfVerify; kInfPieceSizes: kInfPieces' rows (sp.rows) counted as kInfSizes counts, one wave per
+// slot and no ring -- `out` and the page pool are not used, sp.ends and sp.need take one record per slot
+enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify, kInfBatchFold, kInfPieceSizes };
+constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes, kInfPieces, kInfPieceSizes or kInfVerify launch: the kind fixes the ring, the launcher does not look at the value
 int inflate_ring_kb(); // ZGPU_INF_RING_KB, read at EVERY call (the tests run the same streams through all three): 8, 16, anything else 32; not set: the build's default
 void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const SpecArgs &sp, hipStream_t st);
 int output_checksums(zgpu_engine *e, const uint8_t *d_out, uint64_t nbytes, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st);
@@ -306,6 +307,14 @@ PieceItem *batch_pieces_items(uint8_t *scr);           // ... and where the list
 // merge has put the empty segment's verdict there), so that the caller's second merge takes the record.  Ends with a read-back of the counters
 int batch_pieces_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint8_t *d_out, uint64_t out_cap, uint64_t max_long, uint8_t *scr, unsigned long long *d_hdr,
                      const unsigned long long *hdr, BatchItemState *states, InfStatus *status, uint64_t round_bytes, int ring_kb, hipStream_t st);
+// The sizing form (the sizing pass of zgpu_inflate_batch_sizes_* / _packed_*): the same list, finders and selection; the pieces are COUNTED (kInfPieceSizes),
+// pieces_sizes_chain (zgpu_inflate_pieces_plan.h) is the verdict, a clean item's record is the one kInfSizes writes for it and every other item goes
+// through one kInfSizes launch.  No destination, no pages, no windows, no resolve pass.
+struct BatchPiecesSizesKnobs { uint64_t min_bytes, round_slots; }; // round_slots 0: no cap
+BatchPiecesSizesKnobs batch_pieces_sizes_knobs(); // ZGPU_BATCH_PIECES_SIZES_MIN_BYTES (not set: ZGPU_BATCH_PIECES_MIN_BYTES), ZGPU_BATCH_PIECES_SIZES_ROUND_SLOTS, read at EVERY call
+uint64_t batch_pieces_sizes_count(int which); // 0: long items sized in pieces, 1: long items of a sizing pass that fell back to the one-wave sizing kernel
+int batch_pieces_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint64_t max_long, uint8_t *scr, unsigned long long *d_hdr, const unsigned long long *hdr,
+                           BatchItemState *states, InfStatus *status, uint64_t round_slots, hipStream_t st);
 
 // ---- zgpu_inflate_batch.hip ----
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,

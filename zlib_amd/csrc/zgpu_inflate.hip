@@ -107,6 +107,17 @@ __device__ inline void block_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0
 // CRC-32 and compares no ISIZE, so its verdict is the decoder's verdict minus the trailer checks.
 // Termination: SIZES adds no loop.  The block loop and the token loop are the reader's, and every iteration of either consumes input bits or ends with
 // an error (or with `stop`, which the counting sets together with its error); the counting itself is straight-line code.
+// SPEC with SIZES (kInfPieceSizes, sp.rows only: the sizing pass over the pieces of many streams, batch_pieces_sizes_run): the reader of the rowed SPEC decode --
+// start and stop bits, a start at a stored block's LEN, in_end and `first` from the row, a slot with kPieceNoItem returns at the top -- that counts as SIZES
+// counts, from its start to the first block boundary at or behind its stop, or to the final block.  One wave per slot, InflateLdsSizes, no token ring,
+// no output ring, no barrier; `out`, the page pool and the tails are never touched.  It writes one SpecEnd per slot (end_bit, out_bytes, bit 0 = the
+// final block, bits 8.. the error, as the SPEC decode sets them) and sp.need[slot].  Two things differ from SIZES.  Reach: a first piece keeps SIZES' rule
+// (reach 0: a distance beyond the bytes counted so far is its error); every other piece cannot know what lies in front of it, never fails for reach and
+// records need = the largest (distance - bytes counted in front of that token) over its matches, floored at 0, which pieces_sizes_chain holds against
+// what the pieces in front of it counted.  Overflow: the count stops at the item limit 0xFFFF0000 with kMsgOutput instead of wrapping (a piece whose
+// finders found nothing can be a body of 2^29 bytes, and deflate expands 1032 to 1): SIZES' own `over` rule, chunk_size being that limit here.
+// Occupancy: compiled for ZGPU_INF_SIZES_WAVES like SIZES, the same LDS: twenty-four slots a CU, six waves a SIMD (registers: profiles/sizes_pieces_isa.txt).
+// Termination: it adds no loop to the reader's; `need` is straight-line code (a maximum over the lanes, six steps) in the hand-overs of a piece's first 32 KiB.
 // VERIFY (zgpu_inflate_batch_verify_*, BATCH only, the 32 KiB ring): the integrity test.  The reader is the decoder's, and so is everything the writer does
 // inside the ring -- literals, match copies, stored blocks half by half; every match finds its source there.  What it does not have is a destination: where
 // the decoder would flush ring bytes [flushed, upto) to memory (half a ring, or the tail at the end, never wrapping) the writer wave folds them into the
@@ -138,7 +149,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
 {
     typedef typename std::conditional<SPEC, uint16_t, uint8_t>::type ring_t;
     typedef typename std::conditional<SIZES, InflateLdsSizes, typename std::conditional<VERIFY, InflateLdsVerify, typename std::conditional<FOLD, InflateLdsFoldT<RING>, InflateLdsT<ring_t, RING>>::type>::type>::type Lds;
-    static_assert(!SIZES || (BATCH && !SPEC), "the sizing pass serves batch items");
+    static_assert(!SIZES || (BATCH != SPEC), "the sizing pass serves batch items, whole (BATCH) or by the rows of their pieces (SPEC)");
     static_assert(!VERIFY || (BATCH && !SPEC && !SIZES && !FOLD && RING == 32768), "the integrity test serves batch items, every match from the ring");
     static_assert(!FOLD || (BATCH && !SPEC && !SIZES && !VERIFY), "the fused decode serves batch items");
     constexpr uint32_t kOutRing = RING, kOutHalf = RING / 2; // (this kernel's ring, not the file's default)
@@ -156,6 +167,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     // its row; a slot that is not in use ends here, before the first barrier
     const bool rowed = SPEC && sp.rows != nullptr;
     if (rowed && sp.rows[gc].item == kPieceNoItem) return;
+    if (SPEC && SIZES && !rowed) return; // (the sizing form has rows only)
     uint64_t seg_lo = rowed ? sp.rows[gc].start : BATCH ? offsets[4 * gc] : offsets[gc], seg_hi = rowed ? sp.rows[gc].stop : BATCH ? offsets[4 * gc + 1] : offsets[gc + 1];
     const uint64_t spec_end = rowed ? sp.rows[gc].in_end : in_bytes; // SPEC: the byte behind the stream the segment belongs to
     const bool spec_first = rowed ? sp.rows[gc].first != 0 : gc == 0; // SPEC: the stream's first segment
@@ -198,6 +210,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
         uint32_t wr = 0;   // tokens put into the ring so far
         bool stop = false; // the writer gave up (its error comes first in stream order)
         uint32_t size_o = 0, size_err = kMsgNone; // SIZES: bytes the tokens so far stand for; the error of the first token that breaks a limit of the output position
+        uint32_t size_need = 0;                   // SIZES of a piece that is not its item's first: how far its matches reach in front of its first byte
         auto publish = [&]() { // the current half is complete: hand it over, the other half is free from here on
             INF_T(9);
             block_sync();
@@ -209,7 +222,17 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
             if constexpr (SIZES) { // what the writer does with a run of tokens, minus the bytes (the marked lanes are in stream order)
                 const uint32_t k2 = sel_mask(marks, word & 3u, 0u), len = (word >> 2) & 511u, ol = k2 == 1 ? 1u : k2 == 2 ? len : 0u;
                 const uint32_t incl = wave_prefix_sum(ol), offv = size_o + incl - ol;
-                const bool far = k2 == 2 && (word >> 11) >= offv + reach, over = offv + ol > chunk_size; // (size_o <= 0xFFFF0000 and a run adds 64 * 258 at most: no wrap)
+                // (SPEC: only a first piece knows what lies in front of it -- nothing; the others record how far they reach instead)
+                const bool far = k2 == 2 && (!SPEC || spec_first) && (word >> 11) >= offv + reach, over = offv + ol > chunk_size; // (size_o <= 0xFFFF0000 and a run adds 64 * 258 at most: no wrap)
+                if constexpr (SPEC) {
+                    if (!spec_first && !stop && size_o < 32768u) { // (behind 32 KiB of its own no distance reaches in front of the piece)
+                        uint32_t nd = (k2 == 2 && (word >> 11) >= offv) ? (word >> 11) + 1 - offv : 0u;
+#pragma unroll
+                        for (int sh = 32; sh >= 1; sh >>= 1) { const uint32_t o2 = (uint32_t)__shfl_xor((int)nd, sh); nd = o2 > nd ? o2 : nd; }
+                        nd = uni(nd);
+                        size_need = nd > size_need ? nd : size_need;
+                    }
+                }
                 const uint64_t bad = __ballot(far || over);
                 if (stop) { } // (the second window of a step whose first one broke a limit: the first error stands, as the writer takes no token behind its error)
                 else if (bad) { size_err = ((__ballot(far) >> (uint32_t)__builtin_ctzll(bad)) & 1) ? kMsgTooFar : kMsgOutput; stop = true; }
@@ -460,6 +483,10 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
                 status[c].code = err ? ZGPU_DATA_ERROR : ZGPU_OK;
                 status[c].msg = err ? err : ((L.end_bits & 7u) << 24); status[c].out_bytes = err ? 0 : size_o;
                 status[c].used = err ? 0u : (((L.end_bits + 7u) >> 3) | (L.end_final << 31));
+                if constexpr (SPEC) { // the piece's end record, as the SPEC decode's writer forms it (no page pool: bit 1 stays clear), and its reach
+                    sp.ends[gc].end_bit = seg_lo * 8 + L.end_bits; sp.ends[gc].out_bytes = err ? 0 : size_o; sp.ends[gc].flags = err ? (err << 8) : L.end_final;
+                    sp.need[gc] = size_need;
+                }
             }
         }
 #ifdef ZGPU_INF_TIME
@@ -793,6 +820,7 @@ void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const 
     };
     if (kind == kInfPieces) go(inflate_kernel_t<true>, 128, sizeof(InflateLdsSpec));
     else if (kind == kInfSizes) go(inflate_kernel_t<false, ZGPU_INF_RING, true, true>, 64, sizeof(InflateLdsSizes));
+    else if (kind == kInfPieceSizes) go(inflate_kernel_t<true, ZGPU_INF_RING, false, true>, 64, sizeof(InflateLdsSizes));
     else if (kind == kInfVerify) go(inflate_kernel_t<false, 32768, true, false, true>, 128, sizeof(InflateLdsVerify));
     else if (kind == kInfBatchFold) {
         if (ring_kb == 8) go(inflate_kernel_t<false, 8192, true, false, false, true>, 128, sizeof(InflateLdsFoldT<8192>));

@@ -3,7 +3,8 @@
 // in BATCH mode (one workgroup per item, straight into the item's range), the decoded bytes are checked in 64 KiB pieces by adler_kernel / crc_kernel, and
 // the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.  Items of 128 KiB of deflate data or more are decoded in
 // pieces instead (zgpu_inflate_batch_pieces.hip), blocking decode only, and rejoin the chain at the merge kernel.  The sizing pass and the integrity test (further down) run
-// the same header kernel and the decoder in its SIZES / VERIFY mode: neither has a destination, the second still has its trailers compared.
+// the same header kernel and the decoder in its SIZES / VERIFY mode: neither has a destination, the second still has its trailers compared.  The blocking
+// sizing pass has its long items counted in pieces, the sizing form of the same file's piece path, behind its read-back (batch_sizes_long).
 // The stream-ordered calls (zgpu_inflate_batch_*_enqueue, at the end) put the same chains on the caller's stream with the caller's workspace in place of
 // the engine's scratch and read nothing back; their decode runs the decoder in its FOLD mode, which checks the bytes while it stores them.
 #include "zgpu_common.h"
@@ -320,18 +321,27 @@ __global__ void __launch_bounds__(256) batch_packed_merge_kernel(const zgpu_infl
     if (items[k].code != ZGPU_OK) atomicAdd(nfailed, 1ull);
 }
 
-// The sizing pass over items in[d_in_off[k], d_in_off[k + 1]): records into d_items.  The counters stay in the engine's scratch (*cnt_out: [1] failed
-// items, [2] bad offsets) and nothing is read back here: the caller's one read-back fetches them.
-static int inflate_batch_sizes_launch(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items,
-                                      unsigned long long **cnt_out, hipStream_t st)
+// The sizing pass over items in[d_in_off[k], d_in_off[k + 1]): records into d_items.  The counters stay in the engine's scratch (c->s.cnt: [1] failed
+// items, [2] bad offsets, [8..15] the long items' eight) and nothing is read back here: the caller's one read-back fetches them (batch_sizes_readback).
+// Long items (a deflate body of ZGPU_BATCH_PIECES_SIZES_MIN_BYTES or more; not set: ZGPU_BATCH_PIECES_MIN_BYTES, 128 KiB; 0: none) leave the segment table for
+// the list, as in inflate_batch_run_ranges, and the one-wave launch skips them: batch_sizes_long, behind the caller's read-back, counts them in pieces.
+struct SizesCall { BatchScratch s; bool pieces; uint64_t max_long, round_slots; };
+static int inflate_batch_sizes_launch(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, zgpu_inflate_item *d_items, SizesCall *c,
+                                      hipStream_t st)
 {
-    BatchScratch s;
-    if (int rc = batch_scratch(e, n, kScratchSizes, 0, &s)) return rc;
+    // long items in pieces: only a call whose input can hold one (the block finder reads the input in 16-byte vectors: an input that is not aligned goes the old way)
+    const BatchPiecesSizesKnobs kn = batch_pieces_sizes_knobs();
+    c->pieces = kn.min_bytes && in_bytes >= kn.min_bytes && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
+    c->max_long = c->pieces ? (in_bytes / kn.min_bytes < n ? in_bytes / kn.min_bytes : n) : 0;
+    c->round_slots = kn.round_slots;
+    BatchScratch &s = c->s;
+    if (int rc = batch_scratch(e, n, kScratchSizes, 0, &s, c->pieces ? batch_pieces_scratch_bytes(c->max_long) : 0)) return rc;
     ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
     const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    const PiecesList pl = c->pieces ? PiecesList{s.cnt + 8, batch_pieces_items(s.long_items), kn.min_bytes, c->max_long} : PiecesList{};
     // (there is no destination: the header kernel is given the input tables a second time in its place, so that its range check passes what the first passes)
     hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, d_in_off + 1, n, (uint32_t)wrap, in_bytes, d_in_off, d_in_off + 1, s.seg, s.items,
-                       reinterpret_cast<uint32_t *>(s.cnt + 2));
+                       reinterpret_cast<uint32_t *>(s.cnt + 2), pl);
     hipEvent_t ev{};
     prof_span_begin(e, st, &ev);
     for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
@@ -341,7 +351,36 @@ static int inflate_batch_sizes_launch(zgpu_engine *e, const uint8_t *d_in, uint6
     prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
     hipLaunchKernelGGL(batch_sizes_finish_kernel, dim3(ngrid), dim3(256), 0, st, s.items, s.status, n, d_items, s.cnt + 1);
     ZGPU_HIP_CHECK(hipGetLastError());
-    *cnt_out = s.cnt;
+    return ZGPU_OK;
+}
+
+// the caller's one read-back: h[0..2] as ever, and -- only where a long item was possible -- the long items' counters behind them, h[8..15] (104 bytes
+// more of the same copy: all a call without long items pays)
+static int batch_sizes_readback(zgpu_engine *e, const SizesCall &c, unsigned long long (&h)[16], hipStream_t st)
+{
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, c.s.cnt, c.pieces ? sizeof h : 3 * sizeof h[0], hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    return ZGPU_OK;
+}
+
+// Behind the read-back: *again = false and nothing is enqueued when the call has no long items (or its offsets are bad).  Otherwise the long items are
+// counted in pieces (batch_pieces_sizes_run), their records replace the empty ones the one-wave launch left, and the finish kernel runs again over all
+// items with the failed counter cleared first -- the first pass has counted the long items' empty records --; the caller takes its layout and its
+// read-back again.
+static int batch_sizes_long(zgpu_engine *e, const SizesCall &c, const unsigned long long (&h)[16], const uint8_t *d_in, uint64_t in_bytes, uint64_t n, zgpu_inflate_item *d_items,
+                            bool *again, hipStream_t st)
+{
+    *again = false;
+    if (!c.pieces || h[2] || h[8 + kHdrLong] == 0) return ZGPU_OK;
+    hipEvent_t ev{};
+    prof_span_begin(e, st, &ev);
+    const int rc = batch_pieces_sizes_run(e, d_in, in_bytes, c.max_long, c.s.long_items, c.s.cnt + 8, h + 8, c.s.items, c.s.status, c.round_slots, st);
+    prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+    if (rc) return rc;
+    ZGPU_HIP_CHECK(hipMemsetAsync(c.s.cnt + 1, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(batch_sizes_finish_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c.s.items, c.s.status, n, d_items, c.s.cnt + 1);
+    ZGPU_HIP_CHECK(hipGetLastError());
+    *again = true;
     return ZGPU_OK;
 }
 
@@ -360,10 +399,13 @@ int inflate_batch_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_byt
     if (int rc = batch_sizes_args(e, d_in, in_bytes, d_in_off, n, wrap, d_items)) return rc;
     if (n == 0) return ZGPU_OK;
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
-    unsigned long long *cnt = nullptr, h[3] = {0, 0, 0};
-    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &cnt, st)) return rc;
-    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
-    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    unsigned long long h[16] = {};
+    SizesCall c{};
+    bool again = false;
+    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &c, st)) return rc;
+    if (int rc = batch_sizes_readback(e, c, h, st)) return rc;
+    if (int rc = batch_sizes_long(e, c, h, d_in, in_bytes, n, d_items, &again, st)) return rc;
+    if (again) { if (int rc = batch_sizes_readback(e, c, h, st)) return rc; }
     collect_spans(e);
     if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
     if (nfailed) *nfailed = h[1];
@@ -444,12 +486,17 @@ int inflate_batch_packed_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     if (n == 0) return ZGPU_OK;
     ZGPU_HIP_CHECK(hipSetDevice(e->device));
     if (e->pk_hi.reserve(e, n + 1) || e->pk_items.reserve(e, n)) return ZGPU_MEM_ERROR;
-    unsigned long long *cnt = nullptr, h[3] = {0, 0, 0};
-    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &cnt, st)) return rc;
-    hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(1024), 0, st, d_items, n, (uint64_t)align, d_out_off, e->pk_hi.p, cnt);
-    ZGPU_HIP_CHECK(hipGetLastError());
-    ZGPU_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
-    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    unsigned long long h[16] = {};
+    SizesCall c{};
+    if (int rc = inflate_batch_sizes_launch(e, d_in, in_bytes, d_in_off, n, wrap, d_items, &c, st)) return rc;
+    for (int pass = 0; pass < 2; pass++) { // (the second pass: a call with long items, their records in place)
+        hipLaunchKernelGGL(batch_layout_kernel, dim3(1), dim3(1024), 0, st, d_items, n, (uint64_t)align, d_out_off, e->pk_hi.p, c.s.cnt);
+        ZGPU_HIP_CHECK(hipGetLastError());
+        if (int rc = batch_sizes_readback(e, c, h, st)) return rc;
+        bool again = false;
+        if (pass == 0) { if (int rc = batch_sizes_long(e, c, h, d_in, in_bytes, n, d_items, &again, st)) return rc; }
+        if (!again) break;
+    }
     collect_spans(e);
     if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
     *total = h[0];

@@ -24,6 +24,7 @@
 #include <vector>
 
 static std::atomic<uint64_t> g_pieces_done{0}, g_pieces_fell{0};
+static std::atomic<uint64_t> g_sizes_done{0}, g_sizes_fell{0}; // the sizing form (batch_pieces_sizes_run): counted apart, also inside a packed call
 
 namespace zgpu {
 static_assert(kPiecesRing == kOutRing && kPiecesHalf == kOutHalf && kPiecesStoredFlag == (1ull << 62), "zgpu_inflate_pieces_plan.h states the decoder's ring as numbers");
@@ -101,20 +102,13 @@ __global__ void __launch_bounds__(64) pieces_select_kernel(PieceItem *items, uin
 // one lane per item: the chain (what inflate_spec_run checks on the host, the input read here).  ostart[slot]: where the piece's output starts inside its
 // item.  Clean: every piece up to the one that saw the final block ended where the next one starts, the total is within the item's room, no piece went
 // without a page and the final block ends inside the item.  Anything else -- an error in any piece, a false start, a broken chain -- is "fall back".
-// Termination: one step per piece in use (npieces <= piece_cap); links() looks at ten bits at most.
+// Termination: one step per piece in use (npieces <= piece_cap); pieces_links looks at ten bits at most.
 __global__ void __launch_bounds__(64) pieces_chain_kernel(PieceItem *items, uint32_t nitems, const uint8_t *__restrict__ in, const PieceRow *__restrict__ rows,
                                                           const SpecEnd *__restrict__ ends, uint64_t *ostart, uint2 *ranges)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nitems) return;
     const PieceItem it = items[j];
-    auto links = [&](uint64_t eb, uint64_t start) -> bool { // does a piece that ended at bit eb hand over to this start?
-        if (!(start & kPiecesStoredFlag)) return eb == start;
-        const uint64_t s = start & ~kPiecesStoredFlag;
-        if (eb + 3 > s || eb + 10 < s) return false;
-        for (uint64_t q = eb; q < s; q++) if ((in[q >> 3] >> (q & 7)) & 1u) return false; // BFINAL 0, stored, padding of zeros
-        return true;
-    };
     uint64_t total = 0, end_bit = 0;
     uint32_t used = 0;
     bool ended = false, dry = false;
@@ -124,7 +118,7 @@ __global__ void __launch_bounds__(64) pieces_chain_kernel(PieceItem *items, uint
         ostart[it.slot0 + i] = total;
         total += e.out_bytes; used = i + 1; dry = dry || (e.flags & 2u);
         if (e.flags & 1u) { ended = true; end_bit = e.end_bit; break; }
-        if (i + 1 == it.npieces || !links(e.end_bit, rows[it.slot0 + i + 1].start)) break;
+        if (i + 1 == it.npieces || !pieces_links(in, e.end_bit, rows[it.slot0 + i + 1].start)) break;
     }
     const bool clean = ended && !dry && total <= it.out_hi - it.out_lo && end_bit >= it.body_lo * 8 && end_bit <= it.in_hi * 8;
     items[j].total = total; items[j].end_bit = end_bit; items[j].npieces = clean ? used : 0u; items[j].clean = clean ? 1u : 0u; items[j].bad = 0;
@@ -253,6 +247,108 @@ int batch_pieces_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uin
     ZGPU_HIP_CHECK(hipMemcpyAsync(h, d_hdr, sizeof h, hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
     g_pieces_done += h[kHdrClean]; g_pieces_fell += h[kHdrFell];
+    return ZGPU_OK;
+}
+
+// ---- the sizing form: the long items of a sizing pass (inflate_batch_sizes_launch, zgpu_inflate_batch.hip), counted in pieces ----
+// classify, round, targets, find and select are the decode's, kernel for kernel; then
+//   count     inflate_kernel_t<SPEC, SIZES> over the rows: one wave per slot, an end record and a need per slot
+//   chain     (a lane / item)      pieces_sizes_chain (zgpu_inflate_pieces_plan.h): clean, or fall back
+//   status    pieces_status_kernel: a clean item gets the record the one-wave sizing kernel would write, the others are gathered
+//   fallback  ONE kInfSizes launch over the gathered items, their records scattered back: the verdict of anything that is not clean (damage, a cut item, a
+//             false start, a reach in front of the item, an item over the limit) is the one-wave sizing kernel's by construction
+// No pages, no windows, no resolve pass, no destination; no repair rounds, no retry, no kernel that waits on another workgroup: the stream orders the stages.
+
+// one lane per item: the verdict.  Termination: pieces_sizes_chain's, one step per piece in use.
+__global__ void __launch_bounds__(64) pieces_sizes_chain_kernel(PieceItem *items, uint32_t nitems, const uint8_t *__restrict__ in, const PieceRow *__restrict__ rows,
+                                                                const SpecEnd *__restrict__ ends, const uint32_t *__restrict__ need)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nitems) return;
+    const PieceItem it = items[j];
+    const PiecesSizesVerdict v = pieces_sizes_chain(ends + it.slot0, need + it.slot0, rows + it.slot0, it.npieces, in, it.body_lo, it.in_hi);
+    items[j].total = v.total; items[j].end_bit = v.end_bit; items[j].npieces = v.clean ? v.used : 0u; items[j].clean = v.clean; items[j].bad = 0;
+}
+
+BatchPiecesSizesKnobs batch_pieces_sizes_knobs()
+{
+    BatchPiecesSizesKnobs k{batch_pieces_knobs().min_bytes, 0};
+    if (const char *v = getenv("ZGPU_BATCH_PIECES_SIZES_MIN_BYTES")) k.min_bytes = strtoull(v, nullptr, 10);
+    if (const char *v = getenv("ZGPU_BATCH_PIECES_SIZES_ROUND_SLOTS")) k.round_slots = strtoull(v, nullptr, 10);
+    return k;
+}
+uint64_t batch_pieces_sizes_count(int which) { return which == 0 ? g_sizes_done.load() : which == 1 ? g_sizes_fell.load() : 0; }
+
+int batch_pieces_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint64_t max_long, uint8_t *scr, unsigned long long *d_hdr, const unsigned long long *hdr,
+                           BatchItemState *states, InfStatus *status, uint64_t round_slots, hipStream_t st)
+{
+    const PiecesCall c = pieces_call(scr, max_long, nullptr);
+    unsigned long long h[8] = {};
+    for (int i = 0; i < 8; i++) h[i] = hdr[i];
+    const uint64_t nlong = h[kHdrLong];
+    if (nlong == 0) return ZGPU_OK;
+    // one round serves everything, or the list of long items comes home and pieces_sizes_round_end cuts it
+    std::vector<PiecesItemCost> cost;
+    const bool one = nlong < 0xFFFFFFFFull && h[kHdrTargets] < 0xFFFFFFFFull && h[kHdrSlots] < 0xFFFFFFFFull && (round_slots == 0 || h[kHdrSlots] <= round_slots) &&
+                     pieces_sizes_round_plan(nlong, h[kHdrTargets], h[kHdrSlots]).total <= kPiecesScratchCap;
+    if (!one) {
+        std::vector<PieceItem> list(nlong);
+        ZGPU_HIP_CHECK(hipMemcpyAsync(list.data(), c.items, nlong * sizeof(PieceItem), hipMemcpyDeviceToHost, st));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+        cost.resize(nlong);
+        for (uint64_t j = 0; j < nlong; j++) cost[j] = PiecesItemCost{0, list[j].ntargets, list[j].piece_cap};
+    }
+    for (uint64_t j0 = 0; j0 < nlong;) {
+        uint64_t j1 = nlong, targets = h[kHdrTargets], slots = h[kHdrSlots];
+        if (!one) {
+            j1 = pieces_sizes_round_end(cost.data(), nlong, j0, round_slots);
+            targets = slots = 0;
+            for (uint64_t j = j0; j < j1; j++) { targets += cost[j].ntargets; slots += cost[j].piece_cap; }
+        }
+        const uint32_t ni = (uint32_t)(j1 - j0), igrid = (ni + 255) / 256;
+        PieceItem *items = c.items + j0;
+        const PiecesSizesRoundPlan p = pieces_sizes_round_plan(ni, targets, slots);
+        // declining is no error, as in batch_pieces_run: the round's items go to the one-wave sizing kernel (ZGPU_BATCH_PIECES_NO_SCRATCH=1: every round)
+        uint8_t *base = nullptr;
+        if (p.total != 0 && p.total <= kPiecesScratchCap && !getenv("ZGPU_BATCH_PIECES_NO_SCRATCH")) {
+            if (e->inf_slots.reserve(nullptr, p.total)) (void)hipGetLastError();
+            else base = e->inf_slots.p;
+        }
+        ZGPU_HIP_CHECK(hipMemsetAsync(d_hdr + kHdrGathered, 0, 8, st));
+        ZGPU_HIP_CHECK(hipMemsetAsync(c.fbseg + 4 * j0, 0, (size_t)ni * 32, st));
+        if (base) {
+            const uint32_t nt = (uint32_t)targets, ns = (uint32_t)slots;
+            PieceTarget *table = reinterpret_cast<PieceTarget *>(base + p.targets.off);
+            uint64_t *found = reinterpret_cast<uint64_t *>(base + p.found.off), *ostart = reinterpret_cast<uint64_t *>(base + p.ostart.off);
+            PieceRow *rows = reinterpret_cast<PieceRow *>(base + p.rows.off);
+            SpecArgs sp{};
+            sp.ends = reinterpret_cast<SpecEnd *>(base + p.ends.off); sp.rows = rows; sp.need = reinterpret_cast<uint32_t *>(base + p.need.off);
+            ZGPU_HIP_CHECK(hipMemsetAsync(sp.ends, 0xFF, (size_t)ns * sizeof(SpecEnd), st));
+            ZGPU_HIP_CHECK(hipMemsetAsync(sp.need, 0, (size_t)ns * 4, st));
+            hipLaunchKernelGGL(pieces_round_kernel, dim3(1), dim3(1024), 0, st, items, ni);
+            hipLaunchKernelGGL(pieces_targets_kernel, dim3(ni), dim3(256), 0, st, items, ni, table);
+            launch_spec_find_table(d_in, in_bytes, table, nt, found, st);
+            hipLaunchKernelGGL(pieces_select_kernel, dim3((ni + 63) / 64), dim3(64), 0, st, items, ni, d_in, found, nt, rows, ostart);
+            for (uint32_t c0 = 0; c0 < ns; c0 += 65536) {
+                const uint32_t nb = ns - c0 < 65536 ? ns - c0 : 65536;
+                InfLaunch a{d_in, in_bytes, nullptr, c0, nb, nullptr, 0, reinterpret_cast<InfStatus *>(base + p.status.off) + c0};
+                launch_inflate_decode(kInfPieceSizes, kInfNoRing, a, sp, st);
+            }
+            hipLaunchKernelGGL(pieces_sizes_chain_kernel, dim3((ni + 63) / 64), dim3(64), 0, st, items, ni, d_in, rows, sp.ends, sp.need);
+        }
+        // (a round that got no scratch: the items' clean fields are the zeros the header kernel wrote)
+        hipLaunchKernelGGL(pieces_status_kernel, dim3(igrid), dim3(256), 0, st, items, ni, states, status, c.fbseg + 4 * j0, c.fbmap + j0, d_hdr);
+        for (uint32_t c0 = 0; c0 < ni; c0 += 65536) {
+            const uint32_t nb = ni - c0 < 65536 ? ni - c0 : 65536;
+            launch_inflate_decode(kInfSizes, kInfNoRing, InfLaunch{d_in, in_bytes, c.fbseg + 4 * j0, c0, nb, nullptr, 0, c.fbstatus + j0 + c0}, SpecArgs{}, st);
+        }
+        hipLaunchKernelGGL(pieces_scatter_kernel, dim3(igrid), dim3(256), 0, st, c.fbstatus + j0, c.fbmap + j0, d_hdr, ni, status);
+        ZGPU_HIP_CHECK(hipGetLastError());
+        j0 = j1;
+    }
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, d_hdr, sizeof h, hipMemcpyDeviceToHost, st));
+    ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    g_sizes_done += h[kHdrClean]; g_sizes_fell += h[kHdrFell];
     return ZGPU_OK;
 }
 } // namespace zgpu

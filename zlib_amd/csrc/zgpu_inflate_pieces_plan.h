@@ -1,7 +1,8 @@
 // zgpu_inflate_pieces_plan.h -- internal (not installed): what the piece path of the blocking batch decode (zgpu_inflate_batch_pieces.hip) decides from
 // plain numbers: which items are long, how far apart their pieces and their block finders stand, which of the finders' hits become piece starts,
-// how a call's long items are split into rounds and how a round's scratch is laid out.  No HIP type and no include but <cstdint>: tests/tools/
-// inflate_pieces_plan_model.cpp runs the same code on a machine without a GPU.  The functions the device runs too carry ZGPU_PIECES_HD, which is
+// how a call's long items are split into rounds and how a round's scratch is laid out; and, for the sizing form of the path (at the end), the verdict
+// over an item's counted pieces and the sizing round's plan.  No HIP type and no include but <cstdint>: tests/tools/inflate_pieces_plan_model.cpp and
+// tests/tools/inflate_sizes_pieces_model.cpp run the same code on a machine without a GPU.  The functions the device runs too carry ZGPU_PIECES_HD, which is
 // `__host__ __device__` under hipcc and nothing elsewhere.
 // The spacing formulas are those of inflate_spec_run (zgpu_inflate_stream.hip) for one stream of the same length.
 #pragma once
@@ -16,7 +17,7 @@
 namespace zgpu {
 
 constexpr uint64_t kPiecesMinBytesDefault = 131072;       // ZGPU_BATCH_PIECES_MIN_BYTES: a deflate body of at least this many bytes is a long item (0: none is)
-constexpr uint64_t kPiecesRoundBytesDefault = 512ull << 20; // ZGPU_BATCH_PIECES_ROUND_BYTES: bytes of output room one round serves
+constexpr uint64_t kPiecesRoundBytesDefault = 512ull << 20; // ZGPU_BATCH_PIECES_ROUND_BYTES: bytes of output room one round of the DECODE serves (no meaning for sizing, which has no rooms)
 constexpr uint64_t kPiecesScratchCap = (2ull << 30) - 1;  // ... and a round ends before its scratch would pass this, whatever the knob says
 constexpr uint64_t kPiecesBodyMax = 1ull << 29;           // the one-workgroup decoder's own limit of an item: a longer body is its to refuse
 constexpr uint64_t kPiecesStoredFlag = 1ull << 62;        // a start that is the (byte-aligned) LEN of a stored block (inflate_kernel_t<SPEC>)
@@ -160,6 +161,104 @@ inline PiecesRoundPlan pieces_round_plan(uint64_t nitems, uint64_t ntargets, uin
     p.page_cap = pages;
     p.total = off;
     return p;
+}
+
+// ---- the sizing form (the sizing pass of the sizes and the packed call, batch_pieces_sizes_run) ----
+// The decoded size of a stream is a function of its symbols alone: a piece that starts at a block boundary is COUNTED with no knowledge of the 32 KiB in
+// front of it.  What a piece cannot settle alone is settled by the chain below from plain numbers per piece: where it ended, how many bytes it counted,
+// whether it saw the final block, and `need` -- how far its matches reach in front of its own first byte.
+constexpr uint64_t kPiecesItemLimit = 0xFFFF0000ull; // the one-workgroup decoder's limit of an item's decoded size (a piece's count stops there too)
+
+// does a piece that ended at bit eb hand over to this start?  A plain start: exactly there.  A stored start (the LEN of a stored block): 3 header bits and
+// up to 7 of padding lie between, all zeros -- BFINAL 0, type stored, padding.  Termination: ten bits at most.
+ZGPU_PIECES_HD inline bool pieces_links(const uint8_t *in, uint64_t eb, uint64_t start)
+{
+    if (!(start & kPiecesStoredFlag)) return eb == start;
+    const uint64_t s = start & ~kPiecesStoredFlag;
+    if (eb + 3 > s || eb + 10 < s) return false;
+    for (uint64_t q = eb; q < s; q++) if ((in[q >> 3] >> (q & 7)) & 1u) return false;
+    return true;
+}
+
+// The verdict over one item's pieces.  ends[i]: .end_bit, .out_bytes, .flags (bit 0 the final block, bits 8.. an error; all ones: never written);
+// need[i]: the largest (distance - bytes the piece had counted in front of that token) over piece i's matches, floored at 0 (piece 0's reach is its own
+// error); rows[i].start: the piece's start as selected; the item's body begins at byte body_lo and the item ends in front of byte in_hi of `in`.
+// Clean: every piece up to the one that saw the final block ended without error and linked to the next start, the final block ends inside the item, the
+// total is within the item limit, and no piece i > 0 needs more than pieces 0 .. i - 1 counted -- the sizing form of "no back-reference reaches in
+// front of the item's first byte", which the decode learns in its resolve pass.  `used`: pieces up to the final one (meaningful when clean).
+// Termination: one step per piece, pieces_links in each.
+struct PiecesSizesVerdict { uint64_t total, end_bit; uint32_t used, clean; };
+template <class End, class Row>
+ZGPU_PIECES_HD inline PiecesSizesVerdict pieces_sizes_chain(const End *ends, const uint32_t *need, const Row *rows, uint32_t npieces, const uint8_t *in, uint64_t body_lo,
+                                                            uint64_t in_hi)
+{
+    PiecesSizesVerdict v{};
+    bool ended = false, reach = false;
+    for (uint32_t i = 0; i < npieces; i++) {
+        if (ends[i].flags >> 8) break; // an error (a count that would pass the item limit is one), or never written
+        if (i > 0 && need[i] > v.total) { reach = true; break; }
+        v.total += ends[i].out_bytes; v.used = i + 1;
+        if (ends[i].flags & 1u) { ended = true; v.end_bit = ends[i].end_bit; break; }
+        if (i + 1 == npieces || !pieces_links(in, ends[i].end_bit, rows[i + 1].start)) break;
+    }
+    v.clean = (ended && !reach && v.total <= kPiecesItemLimit && v.end_bit >= body_lo * 8 && v.end_bit <= in_hi * 8) ? 1u : 0u;
+    return v;
+}
+
+// A sizing round's scratch: per finder its row and its two results, per piece slot its row, end record, status, output start (the selection's list of
+// starts stands there first) and need.  There is no term in the room: there is no room.
+constexpr uint64_t kPiecesSizesPerPieceBytes = 32 + 16 + 16 + 8 + 4;
+struct PiecesSizesRoundPlan {
+    PiecesRegion targets, found, rows, ends, status, ostart, need; // in this order
+    uint64_t total; // 0: the round cannot be had (2^32 - 1 items, finders or slots, or more)
+};
+constexpr int kPiecesSizesRegions = 7;
+inline const PiecesRegion &pieces_sizes_region(const PiecesSizesRoundPlan &p, int i)
+{
+    const PiecesRegion *r[kPiecesSizesRegions] = {&p.targets, &p.found, &p.rows, &p.ends, &p.status, &p.ostart, &p.need};
+    return *r[i];
+}
+inline const char *pieces_sizes_region_name(int i)
+{
+    static const char *const names[kPiecesSizesRegions] = {"targets", "found", "rows", "ends", "status", "ostart", "need"};
+    return i >= 0 && i < kPiecesSizesRegions ? names[i] : "";
+}
+inline PiecesSizesRoundPlan pieces_sizes_round_plan(uint64_t nitems, uint64_t ntargets, uint64_t npieces)
+{
+    PiecesSizesRoundPlan p{};
+    if (nitems >= 0xFFFFFFFFull || ntargets >= 0xFFFFFFFFull || npieces >= 0xFFFFFFFFull) return p;
+    uint64_t off = 0;
+    auto carve = [&](uint64_t bytes) { PiecesRegion r{off, bytes}; off = (off + bytes + kPiecesAlign - 1) & ~(kPiecesAlign - 1); return r; };
+    p.targets = carve(ntargets * 24);
+    p.found = carve(ntargets * 16);
+    p.rows = carve(npieces * 32);
+    p.ends = carve(npieces * 16);
+    p.status = carve(npieces * 16);
+    p.ostart = carve(npieces * 8);
+    p.need = carve(npieces * 4);
+    p.total = off;
+    return p;
+}
+// what a long item adds to a sizing round's scratch (its room does not count)
+ZGPU_PIECES_HD inline uint64_t pieces_sizes_item_scratch(const PiecesItemCost &c)
+{
+    return (uint64_t)c.piece_cap * kPiecesSizesPerPieceBytes + (uint64_t)c.ntargets * kPiecesPerTargetBytes;
+}
+// The sizing round that begins with long item `first` of `nlong`: it ends behind item (return value) - 1.  Items are taken in order while their scratch
+// (with the regions' alignment) stays within kPiecesScratchCap, their slots and finders below 2^32 - 1, and -- slot_cap, ZGPU_BATCH_PIECES_SIZES_ROUND_SLOTS,
+// 0: no cap -- their slots within the cap; an item that alone passes a limit makes a round of its own.  ZGPU_BATCH_PIECES_ROUND_BYTES has no meaning
+// here.  Every long item is in exactly one round.  Termination: k grows by one per step and stops at nlong.
+inline uint64_t pieces_sizes_round_end(const PiecesItemCost *c, uint64_t nlong, uint64_t first, uint64_t slot_cap)
+{
+    uint64_t scratch = kPiecesSizesRegions * kPiecesAlign, slots = 0, targets = 0, k = first;
+    while (k < nlong) {
+        const uint64_t s = pieces_sizes_item_scratch(c[k]);
+        if (k > first && (scratch + s > kPiecesScratchCap || slots + c[k].piece_cap >= 0xFFFFFFFFull || targets + c[k].ntargets >= 0xFFFFFFFFull || k - first + 1 >= 0xFFFFFFFFull ||
+                          (slot_cap && slots + c[k].piece_cap > slot_cap)))
+            break;
+        scratch += s; slots += c[k].piece_cap; targets += c[k].ntargets; k++;
+    }
+    return k;
 }
 
 } // namespace zgpu

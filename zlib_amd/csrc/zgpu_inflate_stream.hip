@@ -785,7 +785,7 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
 
 extern "C" {
 #pragma GCC visibility push(default)
-uint64_t zgpu_inflate_spec_count(int which) { return which == 0 ? g_spec_done.load() : which == 1 ? g_whole_done.load() : (which == 2 || which == 3) ? batch_pieces_count(which - 2) : 0; }
+uint64_t zgpu_inflate_spec_count(int which) { return which == 0 ? g_spec_done.load() : which == 1 ? g_whole_done.load() : (which == 2 || which == 3) ? batch_pieces_count(which - 2) : (which == 4 || which == 5) ? batch_pieces_sizes_count(which - 4) : 0; }
 int zgpu_inflate_find_chunks_host(zgpu_engine *e, const void *in, uint64_t in_bytes, uint32_t chunk_size, uint64_t *offsets, uint64_t max_chunks,
                                   uint64_t *nchunks)
 {

@@ -774,6 +774,11 @@ class Engine:
         """(long items of blocking batch decodes that were decoded in pieces, long items that fell back to the one-workgroup decoder), since the library was loaded"""
         return int(self.L.zgpu_inflate_spec_count(2)), int(self.L.zgpu_inflate_spec_count(3))
 
+    def batch_size_piece_counts(self):
+        """(long items of sizing passes -- the sizes call, the sizing half of the packed call -- that were sized in pieces, long items of a sizing pass that
+        fell back to the one-wave sizing kernel), since the library was loaded.  batch_piece_counts() goes on counting the decode alone."""
+        return int(self.L.zgpu_inflate_spec_count(4)), int(self.L.zgpu_inflate_spec_count(5))
+
     def inflate_device(self, d_in, n, d_offsets, nchunks, d_out, out_cap, chunk_size=CHUNK, stream=None):
         res = InflateResult()
         rc = self.L.zgpu_inflate_device(self.h, d_in, n, d_offsets, nchunks, chunk_size, d_out, out_cap, C.byref(res), stream)
