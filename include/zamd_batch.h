@@ -30,7 +30,8 @@ unsigned long long zamd_compress2_batch_count(int which);
  * that needs a preset dictionary.  Items of 512 MiB of input or more are served one by one.  Items of any size below that share the one engine
  * call: one workgroup decodes an item of less than 128 KiB of deflate data, a longer one is decoded in pieces, the pieces of all long items in shared
  * launches (zgpu_inflate_batch_host in zamd_gpu.h; zamd_uncompress_batch_packed's decode and the ZIP batch read likewise).  The sizing pass and the
- * integrity test below still give every item to one workgroup. */
+ * integrity test below take their long items in pieces too, each in a form of its own (the integrity test from 20,000,000 bytes of deflate data): the sizing pass counts the pieces, the integrity test decodes
+ * them inside the workgroups' local memory and joins their check values. */
 int zamd_uncompress_batch(Bytef *const *dest, uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits,
                           int *status);
 
@@ -56,7 +57,9 @@ int zamd_uncompress_batch_packed(Bytef *dest, uLongf *destCap, uLong *destOffset
  * status[k] = what zamd_uncompress_batch gives item k with enough room: Z_OK, or Z_DATA_ERROR (damaged, truncated, in need of a dictionary, a wrong
  * Adler-32, CRC-32 or ISIZE -- the trailers ARE checked here).  destLen (optional, may be NULL): destLen[k] = the decoded size, 0 for a failed item.
  * Every item is decoded in full on the device, inside the workgroup's local memory, and its check values are taken there
- * (zgpu_inflate_batch_verify_host): no room for any decoded byte is allocated anywhere.  Items of 512 MiB of input or more go one by one through
+ * (zgpu_inflate_batch_verify_host): no room for any decoded byte is allocated anywhere.  An item of 20,000,000 bytes of deflate data or more is checked in
+ * pieces, the pieces of all long items in shared launches; that costs scratch per piece slot, bounded by a slot cap (about 96 MiB) whatever the items
+ * decode to and however many there are.  Items of 512 MiB of input or more go one by one through
  * inflate(), their output discarded.  The return value is the first failing item's code; Z_STREAM_ERROR for bad arguments touches nothing; n == 0
  * is Z_OK and creates no engine. */
 int zamd_uncompress_verify_batch(uLongf *destLen, const Bytef *const *source, const uLong *sourceLen, size_t n, int windowBits, int *status);

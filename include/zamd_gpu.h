@@ -457,7 +457,9 @@ uint64_t zgpu_inflate_spec_count(int which); /* 0: decoded in pieces, 1: one-wor
                                               * 2: long items of blocking batch decodes decoded in pieces, 3: long items of them that fell back
                                               * to the one-workgroup decoder (zgpu_inflate_batch_*, see there); 4: long items of sizing passes
                                               * sized in pieces, 5: long items of them that fell back to the one-wave sizing kernel
-                                              * (zgpu_inflate_batch_sizes_*, the sizing half of zgpu_inflate_batch_packed_*) */
+                                              * (zgpu_inflate_batch_sizes_*, the sizing half of zgpu_inflate_batch_packed_*); 6: long items of
+                                              * blocking integrity tests verified in pieces, 7: long items of them that fell back to the
+                                              * one-workgroup verifier (zgpu_inflate_batch_verify_host / _device) */
 const char *zgpu_inflate_message(uint32_t index);
 /* Preset dictionary of the inflate calls that follow (inflateSetDictionary, qcsrc/inflate.c:1200-1236): the first segment of a
  * call may reach back into its last min(len, 32768) bytes.  Stays set until replaced; len 0 clears it. */
@@ -492,7 +494,8 @@ int zgpu_inflate_set_checks(zgpu_engine *e, uint32_t mask);
  * once.  ZGPU_BATCH_PIECES_ROUND_BYTES (default 512 MiB) caps the output room one round of the piece path serves; scratch the engine cannot reserve
  * sends a round's items to the one-workgroup decoder and is no error.  This covers the blocking decode (these two calls, the decode half of
  * zgpu_inflate_batch_packed_*, zgpu_bgzf_*, the final decode of zgpu_gzip_inflate_*) and, in a form of its own, the blocking sizing pass (see
- * zgpu_inflate_batch_sizes_* below): the *_enqueue calls and the integrity test give every item to one workgroup as before.
+ * zgpu_inflate_batch_sizes_* below) and the blocking integrity test (zgpu_inflate_batch_verify_* further down): the *_enqueue calls give every item to
+ * one workgroup as before.
  * zgpu_inflate_spec_count(2) / (3) count the long items decoded in pieces / fallen back -- the decode only, also inside a packed call. */
 #define ZGPU_WRAP_RAW 0
 #define ZGPU_WRAP_ZLIB 1
@@ -552,7 +555,7 @@ int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_b
  * Every item is decoded in full -- the same wrapper rules, the same deflate decoder, every match copied -- inside a 32 KiB ring in the workgroup's
  * LDS, and where the decoder would flush a half of the ring to memory the bytes go into the item's running Adler-32 / CRC-32 instead.  The trailer is
  * then compared as zgpu_inflate_batch_* compares it.  No decoded byte is written to device memory or read from it: the call needs the input, 144 bytes
- * of scratch per item and nothing else, whatever the items decode to (gzip -t, unzip -t, bgzip -t, a scrubber, a pack-file fsck).
+ * of scratch per item and -- where items are long, see below -- a piece scratch bounded by a slot cap, whatever the items decode to (gzip -t, unzip -t, bgzip -t, a scrubber, a pack-file fsck).
  * Record k equals, field for field, the record zgpu_inflate_batch_* gives the same item with the same `checks` and an output range of exactly the
  * right size: code (ZGPU_OK, ZGPU_DATA_ERROR or 2 for FDICT; ZGPU_BUF_ERROR cannot occur), msg ("incorrect data check", "incorrect length check", a
  * trailer that does not fit as "segment ends inside a block", every decoder message), out_bytes, in_used, adler32 and crc32 (the check the wrapper
@@ -560,7 +563,25 @@ int zgpu_inflate_batch_packed_host(zgpu_engine *e, const void *in, uint64_t in_b
  * What it does not promise: speed over a decode -- it does all the decoder's work but the stores; its claim is memory.  Arguments, limits (< 512 MiB
  * compressed, < 4 GiB decoded per item, no preset dictionary, a multi-member gzip item is its first member), ZGPU_STREAM_ERROR for offsets that run
  * backwards or leave the buffer, *nfailed and n == 0 are zgpu_inflate_batch_sizes_*'s.  One read-back, at the end; the device entry blocks until the
- * records are in d_items. */
+ * records are in d_items.
+ * Long items are checked in pieces (these two calls and what stands on them: zamd_uncompress_verify_batch, zamd_unzip_test_batch; not
+ * zgpu_inflate_batch_verify_enqueue, where no host sees the items' sizes, and not zgpu_bgzf_verify_*, whose blocks are never long).  Check values need
+ * every byte, in order, with the real 32 KiB in front of every piece, and the call has no room for a decoded byte: the pieces are decoded twice, both
+ * times inside LDS.  A first pass leaves per piece slot its tail -- the last 32 Ki symbols, as the decode in pieces keeps them -- and where it ended; a chain
+ * over the item's pieces and the window kernels turn the tails into the real 32 KiB behind every piece; a second pass decodes every piece again behind
+ * the window of the piece in front, folds its bytes as the one-workgroup verifier does, and finds a distance that reaches in front of the item exactly.
+ * The pieces' Adler-32 / CRC-32 are joined in order into the item's, and the trailer is compared by the code that compares every trailer: a long item
+ * with a wrong Adler-32, CRC-32 or ISIZE stays in pieces.  An item that does not come out clean (damage, a cut item, a false start, a reach in front of
+ * the item, more than 4 GiB) is verified again by one workgroup, once: every record is the one-workgroup verifier's.  Memory: a slot costs its tail
+ * (64 KiB), its window (32 KiB) and under 128 bytes of records, and rounds are cut under ZGPU_BATCH_PIECES_VERIFY_ROUND_SLOTS slots (default 1024: one
+ * residency of the second pass, about 96 MiB of scratch) -- an item with more slots makes a round of its own --, so the scratch depends neither on what
+ * the items decode to nor on their number.  The threshold is ZGPU_BATCH_PIECES_VERIFY_MIN_BYTES, read at every call; not set, it follows
+ * ZGPU_BATCH_PIECES_MIN_BYTES where that is set; neither set, it is 20000000 -- measured (profiles/r14_batch_verify_long_table.txt): two passes over every
+ * piece lose to one workgroup per item on 256 items of 1 MiB and win 2.59 times on 16 items of 64 MiB, whose bodies are that long; 0: every item to one
+ * workgroup.  An input that is not 16-byte aligned or shorter than the threshold never enters
+ * the path; scratch the engine cannot reserve sends a round's items to the one-workgroup verifier and is no error.  A call without long items pays 104
+ * bytes more of the read-back it makes anyway, nothing else; one with long items a second read-back.  zgpu_inflate_spec_count(6) / (7) count the long
+ * items verified in pieces / fallen back; the decode's and the sizing pass's counters do not move in a verify call. */
 int zgpu_inflate_batch_verify_device(zgpu_engine *e, const void *d_in, uint64_t in_bytes, const uint64_t *d_in_offsets, uint64_t n, int wrap,
                                      uint32_t checks, zgpu_inflate_item *d_items, uint64_t *nfailed, void *hip_stream);
 int zgpu_inflate_batch_verify_host(zgpu_engine *e, const void *in, uint64_t in_bytes, const uint64_t *in_offsets, uint64_t n, int wrap,

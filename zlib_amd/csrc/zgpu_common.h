@@ -77,7 +77,15 @@ struct SpecArgs {
     SpecEnd *ends;
     const struct PieceRow *rows = nullptr; // the pieces of MANY streams (zgpu_inflate_batch_pieces.hip): segment gc is rows[gc], the offsets table is not read
     uint32_t *need = nullptr; // the sizing form of the piece path only (kInfPieceSizes): per segment, how far its matches reach in front of its own first byte
+    // the verify form of the piece path only (kInfPieceVerify): per segment the byte window at the end of the segment (the check of segment gc preloads
+    // windows[gc - 1]), where its output starts inside its item, and the record its check leaves
+    const uint8_t *windows = nullptr;
+    const uint64_t *ostart = nullptr;
+    struct PieceCheck *checks = nullptr;
 };
+// what the check of one piece slot leaves (kInfPieceVerify): its end as SpecEnd says it (flags: bit 0 the final block, bits 8.. an error; all ones: never
+// written) and the Adler-32 halves and CRC-32 of the piece's own bytes, started from (1, 0) and 0
+struct PieceCheck { uint64_t end_bit; uint32_t out_bytes, flags, adler_a, adler_b, crc, pad; };
 // The piece path of the batch decode (zgpu_inflate_batch_pieces.hip; the numbers behind it: zgpu_inflate_pieces_plan.h).  Positions are those of the call's
 // input buffer: bits for starts, bytes for ends.
 struct PieceTarget { uint64_t lo_bit, hi_bit, limit; }; // one block finder: the bits it scans, the byte behind its item (nothing is read behind it)
@@ -381,6 +389,23 @@ __host__ __device__ inline void adler_join(uint32_t &ax, uint32_t &bx, uint32_t 
     uint64_t a = ((uint64_t)ax + ay + kAdlerBase - 1) % kAdlerBase;
     uint64_t b = ((uint64_t)bx + by + rem * ((ax + kAdlerBase - 1) % kAdlerBase)) % kAdlerBase;
     ax = (uint32_t)a; bx = (uint32_t)b;
+}
+// The verify form of the piece path (batch_pieces_verify_run, zgpu_inflate_batch_pieces.hip): confirm and join.  The check of each of an item's `used`
+// chained pieces must have ended without error where the tails pass ended -- the same end bit, byte count and final-block bit -- ; then the pieces' check
+// values, each started from (1, 0) and 0, are joined in order into those of the item (a piece can be far longer than kFoldMax: the general power).
+// Returns false, the values undefined, when a check disagrees.  Termination: one step per piece, crc_xpow8n's 64 squarings in each.
+struct PiecesJoined { uint32_t a, b, crc; };
+template <class End, class Check>
+__host__ __device__ inline bool pieces_verify_confirm(const End *ends, const Check *checks, uint32_t used, uint32_t do_adler, uint32_t do_crc, PiecesJoined *out)
+{
+    PiecesJoined j{1, 0, 0};
+    for (uint32_t i = 0; i < used; i++) {
+        if ((checks[i].flags >> 8) || checks[i].end_bit != ends[i].end_bit || checks[i].out_bytes != ends[i].out_bytes || ((checks[i].flags ^ ends[i].flags) & 1u)) return false;
+        if (do_adler) adler_join(j.a, j.b, checks[i].adler_a, checks[i].adler_b, checks[i].out_bytes);
+        if (do_crc) j.crc = crc_join(j.crc, checks[i].crc, crc_xpow8n(checks[i].out_bytes));
+    }
+    *out = j;
+    return true;
 }
 
 // ---- the fold of the verifying decoder (inflate_kernel_t<..., VERIFY>, zgpu_inflate.hip): the check values of a stream taken piece by piece, a piece

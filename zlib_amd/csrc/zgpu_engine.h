@@ -281,9 +281,11 @@ struct InfLaunch {
 // used, `out_cap` carries the checks to compute (bit 0 Adler-32, bit 1 CRC-32) and `meta` takes one record per item: out_bytes, adler_a, adler_b, crc;
 // kInfBatchFold: kInfBatch that also folds what it stores (ring_kb counts, as for kInfBatch) -- `out` and `out_cap` are the destination's, `checks`
 // says what to fold, `meta` takes one record per item as for kInfVerify; kInfPieceSizes: kInfPieces' rows (sp.rows) counted as kInfSizes counts, one wave per
-// slot and no ring -- `out` and the page pool are not used, sp.ends and sp.need take one record per slot
-enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify, kInfBatchFold, kInfPieceSizes };
-constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes, kInfPieces, kInfPieceSizes or kInfVerify launch: the kind fixes the ring, the launcher does not look at the value
+// slot and no ring -- `out` and the page pool are not used, sp.ends and sp.need take one record per slot; kInfPieces with sp.mid == nullptr: no pages, the
+// tails and the end records alone; kInfPieceVerify: kInfPieces' rows read as kInfPieces reads them and written as kInfVerify writes -- the byte ring
+// preloaded from sp.windows, reach from sp.ostart, `out_cap` the checks to compute, one PieceCheck per slot to sp.checks, `out` and `meta` not used
+enum InfKind { kInfChunks, kInfBatch, kInfSizes, kInfPieces, kInfVerify, kInfBatchFold, kInfPieceSizes, kInfPieceVerify };
+constexpr int kInfNoRing = 0; // ring_kb of a kInfSizes, kInfPieces, kInfPieceSizes, kInfPieceVerify or kInfVerify launch: the kind fixes the ring, the launcher does not look at the value
 int inflate_ring_kb(); // ZGPU_INF_RING_KB, read at EVERY call (the tests run the same streams through all three): 8, 16, anything else 32; not set: the build's default
 void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const SpecArgs &sp, hipStream_t st);
 int output_checksums(zgpu_engine *e, const uint8_t *d_out, uint64_t nbytes, uint64_t out_cap, zgpu_inflate_result *res, hipStream_t st);
@@ -294,6 +296,7 @@ int inflate_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const ui
 void launch_spec_find_table(const uint8_t *d_in, uint64_t in_bytes, const PieceTarget *table, uint32_t ntargets, uint64_t *found, hipStream_t st);
 void launch_spec_resolve_items(const SpecArgs &sp, uint32_t nslots, uint32_t nitems, const uint2 *ranges, const uint8_t *entry, uint8_t *windows, const uint64_t *out_start,
                                PieceItem *items, uint8_t *d_out, hipStream_t st);
+void launch_spec_windows_items(uint16_t *tails, uint32_t nslots, uint32_t nitems, const uint2 *ranges, const uint8_t *entry, uint8_t *windows, hipStream_t st); // the windows of the same, nothing resolved
 
 // ---- zgpu_inflate_batch_pieces.hip: the long items of a blocking batch decode, in pieces ----
 struct BatchPiecesKnobs { uint64_t min_bytes, round_bytes; };
@@ -315,6 +318,16 @@ BatchPiecesSizesKnobs batch_pieces_sizes_knobs(); // ZGPU_BATCH_PIECES_SIZES_MIN
 uint64_t batch_pieces_sizes_count(int which); // 0: long items sized in pieces, 1: long items of a sizing pass that fell back to the one-wave sizing kernel
 int batch_pieces_sizes_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint64_t max_long, uint8_t *scr, unsigned long long *d_hdr, const unsigned long long *hdr,
                            BatchItemState *states, InfStatus *status, uint64_t round_slots, hipStream_t st);
+// The verify form (the blocking integrity test, inflate_batch_verify_run): the same list, finders and selection; the pieces are decoded twice inside LDS --
+// the tails pass (kInfPieces without pages), pieces_verify_chain, the window kernels, the check pass (kInfPieceVerify) -- and pieces_verify_confirm
+// (zgpu_common.h) joins a clean item's check values into meta[k], its record into status[k] as kInfVerify writes them; every other item goes through one
+// kInfVerify launch.  No destination, no pages, no resolve pass: a round's scratch is pieces_verify_round_plan's, bounded by the slot cap.
+struct BatchPiecesVerifyKnobs { uint64_t min_bytes, round_slots; }; // round_slots: pieces_verify_slot_cap of the knob
+BatchPiecesVerifyKnobs batch_pieces_verify_knobs(); // ZGPU_BATCH_PIECES_VERIFY_MIN_BYTES (not set: ZGPU_BATCH_PIECES_MIN_BYTES where set, else kPiecesVerifyMinBytesDefault), ZGPU_BATCH_PIECES_VERIFY_ROUND_SLOTS, read at EVERY call
+uint64_t batch_pieces_verify_count(int which); // 0: long items verified in pieces, 1: long items of an integrity test that fell back to the one-workgroup verifier
+size_t batch_pieces_verify_scratch_bytes(uint64_t max_long); // batch_pieces_scratch_bytes and the fallback's compact check records (the list lies where batch_pieces_items says)
+int batch_pieces_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, uint32_t checks, uint64_t max_long, uint8_t *scr, unsigned long long *d_hdr,
+                            const unsigned long long *hdr, BatchItemState *states, InfStatus *status, ChunkMeta *meta, uint64_t round_slots, hipStream_t st);
 
 // ---- zgpu_inflate_batch.hip ----
 int inflate_batch_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, uint8_t *d_out, uint64_t out_cap,

@@ -130,6 +130,19 @@ __device__ inline void block_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0
 // a bank.  The alternatives -- a table in lane registers read by cross-lane shuffles, a 1 KiB byte table (three workgroups a CU), the 4 KiB
 // slicing-by-4 table of zgpu_checksum.hip (three as well) -- have not been measured against it.
 // Termination: VERIFY adds the fold's loops, each bounded by the bytes of one flush (16 KiB), and a table build of two words per lane.
+// SPEC with sp.rows and NOPAGES (the launcher picks it where sp.mid == nullptr: the tails pass of the verify form of the piece path, batch_pieces_verify_run): the rowed SPEC decode whose
+// flushes go nowhere.  The same reader, the same 16-bit ring with markers; no page is taken from a pool and nothing goes to `mid`.  It leaves what the window
+// kernels read -- the slot's tail and its SpecEnd.  A deflate distance reaches 32 KiB at most, so the ring alone carries the decode.
+// SPEC with VERIFY (kInfPieceVerify, sp.rows only: the check pass of the same path): the rowed reader paired with VERIFY's writer.  Start bit, stop bit, a start at
+// a stored block's LEN, in_end and `first` come from the row as in the rowed SPEC decode; a slot with kPieceNoItem returns at the top.  The writer keeps
+// VERIFY's byte ring of 32 KiB (InflateLdsVerify, the CRC nibble tables behind it: four workgroups a CU, as VERIFY) and folds where the decoder would flush.
+// Before its first token the ring is preloaded with the window of the slot in front (sp.windows[gc - 1], bytes), as the dictionary preload does: its last
+// `reach` = min(32768, sp.ostart[gc]) bytes, the bytes of the item in front of this piece; an item's first piece preloads nothing and has reach 0.  A distance
+// beyond reach is the decoder's own "invalid distance too far back" -- exact here, where the tails pass could not know it.  Each slot writes one record
+// (sp.checks[gc]): end bit, bytes produced, the final-block bit or the error, and the Adler-32 halves and CRC-32 of its own bytes started from (1, 0) and 0,
+// whichever `out_cap` asks for.  It touches neither `out` nor a destination, takes no page and writes no tail; `meta` is not used.
+// Termination: the mode adds no loop beyond the preload (2048 vectors over 64 lanes at most); the reader's loops are the rowed SPEC decode's, the fold's VERIFY's.
+// Registers, LDS and scratch of the instantiation: profiles/verify_pieces_isa.txt.
 // FOLD (zgpu_inflate_batch_*_enqueue, BATCH only, the rings BATCH has): the fused decode.  BATCH as it stands -- the same destination, the same dst_room / nofit
 // rules, the same status[] -- whose writer wave, in flush_to, first folds ring bytes [flushed, upto) into the running check values as VERIFY does and then
 // stores them as BATCH does.  The bytes are folded out of LDS in the flush that carries them to memory, so the output is never read again: no piece table, no
@@ -141,17 +154,18 @@ __device__ inline void block_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0
 // layout (InflateLdsFoldT): 512 bytes that leave the workgroups per CU of every ring as they are -- four, six, ten.
 // Termination: FOLD adds to BATCH exactly what VERIFY adds -- the fold's loops, each bounded by the bytes of one flush (half a ring, 16 KiB at most), and the table build --
 // and the flush's store loops stay BATCH's, bounded by the same bytes.
-template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false, bool VERIFY = false, bool FOLD = false>
+template <bool SPEC, uint32_t RING = ZGPU_INF_RING, bool BATCH = false, bool SIZES = false, bool VERIFY = false, bool FOLD = false, bool NOPAGES = false>
 __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES : (!SPEC && RING <= 8192) ? 5 : 4) inflate_kernel_t(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint64_t *__restrict__ offsets,
                                                         uint64_t chunk0, uint32_t nchunks, uint64_t last_chunk, uint32_t chunk_size_arg,
                                                         uint8_t *__restrict__ out, uint64_t out_cap, InfStatus *status, ChunkMeta *meta,
                                                         const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t stream_mode, SpecArgs sp, uint32_t fold_checks)
 {
-    typedef typename std::conditional<SPEC, uint16_t, uint8_t>::type ring_t;
+    typedef typename std::conditional<SPEC && !VERIFY, uint16_t, uint8_t>::type ring_t; // (the check pass knows the window in front: bytes, no markers)
     typedef typename std::conditional<SIZES, InflateLdsSizes, typename std::conditional<VERIFY, InflateLdsVerify, typename std::conditional<FOLD, InflateLdsFoldT<RING>, InflateLdsT<ring_t, RING>>::type>::type>::type Lds;
     static_assert(!SIZES || (BATCH != SPEC), "the sizing pass serves batch items, whole (BATCH) or by the rows of their pieces (SPEC)");
-    static_assert(!VERIFY || (BATCH && !SPEC && !SIZES && !FOLD && RING == 32768), "the integrity test serves batch items, every match from the ring");
+    static_assert(!VERIFY || ((BATCH != SPEC) && !SIZES && !FOLD && RING == 32768), "the integrity test serves batch items, whole (BATCH) or by the rows of their pieces (SPEC), every match from the ring");
     static_assert(!FOLD || (BATCH && !SPEC && !SIZES && !VERIFY), "the fused decode serves batch items");
+    static_assert(!NOPAGES || (SPEC && !BATCH && !SIZES && !VERIFY && !FOLD), "the no-pages form is the 16-bit decode in pieces, its flushes dropped");
     constexpr uint32_t kOutRing = RING, kOutHalf = RING / 2; // (this kernel's ring, not the file's default)
     constexpr bool FAR = RING < 32768;
     static_assert(!(SPEC && FAR) && RING >= 4096 && (RING & (RING - 1)) == 0, "ring size");
@@ -167,7 +181,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     // its row; a slot that is not in use ends here, before the first barrier
     const bool rowed = SPEC && sp.rows != nullptr;
     if (rowed && sp.rows[gc].item == kPieceNoItem) return;
-    if (SPEC && SIZES && !rowed) return; // (the sizing form has rows only)
+    if (SPEC && (SIZES || VERIFY) && !rowed) return; // (the sizing form and the verify form have rows only)
     uint64_t seg_lo = rowed ? sp.rows[gc].start : BATCH ? offsets[4 * gc] : offsets[gc], seg_hi = rowed ? sp.rows[gc].stop : BATCH ? offsets[4 * gc + 1] : offsets[gc + 1];
     const uint64_t spec_end = rowed ? sp.rows[gc].in_end : in_bytes; // SPEC: the byte behind the stream the segment belongs to
     const bool spec_first = rowed ? sp.rows[gc].first != 0 : gc == 0; // SPEC: the stream's first segment
@@ -200,7 +214,9 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     const uint32_t chunk_size = compact ? kChunkMax : whole ? 0xFFFF0000u : chunk_size_arg;
     // a preset dictionary (inflateSetDictionary, inflate.c:1200-1236) is what the window holds before the first byte: in the ring it
     // sits right below position 0, and the first segment may reach that much farther back
-    const uint32_t reach = BATCH ? 0u : (SPEC ? spec_first : gc == 0) ? dict_len : SPEC ? kOutRing : 0u;
+    // (the check pass of the verify form knows where its piece starts inside its item: what lies in front of it, 32 KiB at most, is all a distance may reach)
+    const uint32_t reach = (SPEC && VERIFY) ? (spec_first ? 0u : (uint32_t)(sp.ostart[gc] < kOutRing ? sp.ostart[gc] : kOutRing))
+                                            : BATCH ? 0u : (SPEC ? spec_first : gc == 0) ? dict_len : SPEC ? kOutRing : 0u;
     if (threadIdx.x == 0) { L.abort_flag = 0; L.end_bits = 0; L.end_final = 0; }
     INF_T0();
 
@@ -499,7 +515,14 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     if constexpr (!SIZES) {
     uint32_t err = kMsgNone;
     uint32_t o = 0;       // bytes produced
-    if (SPEC) {
+    if constexpr (SPEC && VERIFY) {
+        // the window of the slot in front, as bytes: its last `reach` bytes lie right below position 0 of the ring (whole 16-byte vectors: what a vector
+        // brings in front of them is never read -- a distance beyond reach is an error).  A piece that is not its item's first has a slot in front: gc >= 1.
+        if (reach) {
+            const uint4 *w = reinterpret_cast<const uint4 *>(sp.windows + (gc - 1) * kOutRing);
+            for (uint32_t i = ((kOutRing - reach) >> 4) + lane; i < kOutRing / 16; i += 64) reinterpret_cast<uint4 *>(L.out)[i] = w[i];
+        }
+    } else if (SPEC) {
         for (uint32_t i = lane; i < kOutRing; i += 64) L.out[i] = (ring_t)(0x8000u | i); // slot i, never written, is byte i of the window in front
         if (spec_first) for (uint32_t i = lane; i < dict_len; i += 64) L.out[(kOutRing - dict_len + i) & (kOutRing - 1)] = dict[i];
     } else
@@ -548,6 +571,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
             return;
         }
         if (SPEC) { // the next page of the pool (flushed is a multiple of kOutHalf: the page's index within the segment)
+            if constexpr (NOPAGES) { flushed = upto; return; } // (no pages: the tails pass of the verify form keeps the ring and nothing else)
             uint32_t page = 0;
             if (lane == 0) page = atomicAdd(sp.page_count, 1u);
             page = uni(page);
@@ -723,7 +747,7 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
     if (!err && !compact && !SPEC && !must_be_final && o != chunk_size) err = kMsgShort; // direct placement assumes full chunks
     // the rest of the chunk (an error leaves what was flushed before it was found; the status says the chunk is void)
     if (!err && (!SPEC || o != flushed)) flush_to(o);
-    if (SPEC && !err) // the ring is the last 32 KiB of what this segment knows: slots it never wrote still name the window in front
+    if (SPEC && !VERIFY && !err) // the ring is the last 32 KiB of what this segment knows: slots it never wrote still name the window in front
         for (uint32_t j = lane; j < kOutRing; j += 64) sp.tails[gc * kOutRing + j] = L.out[(o + j) & (kOutRing - 1)];
     const bool fits = !nofit;
     INF_T(4);
@@ -731,12 +755,17 @@ __global__ void __launch_bounds__(SIZES ? 64 : 128, SIZES ? ZGPU_INF_SIZES_WAVES
         status[c].code = err ? ZGPU_DATA_ERROR : (fits ? ZGPU_OK : ZGPU_BUF_ERROR);
         status[c].msg = err ? err : ((L.end_bits & 7u) << 24); status[c].out_bytes = err ? 0 : o; // (a segment that decoded: the bits of its last byte that are its own, for a stream taken up at a bit offset)
         status[c].used = err ? 0u : (((L.end_bits + 7u) >> 3) | (L.end_final << 31));
-        if (SPEC) { sp.ends[gc].end_bit = seg_lo * 8 + L.end_bits; sp.ends[gc].out_bytes = err ? 0 : o; sp.ends[gc].flags = err ? (err << 8) : (L.end_final | (nofit ? 2u : 0u)); }
+        if constexpr (SPEC && VERIFY) { // the check's record: the end as the tails pass forms it, and the piece's own check values
+            PieceCheck r{};
+            r.end_bit = seg_lo * 8 + L.end_bits; r.out_bytes = err ? 0 : o; r.flags = err ? (err << 8) : L.end_final; r.adler_a = run.a; r.adler_b = run.b; r.crc = run.crc;
+            sp.checks[gc] = r;
+        } else if (SPEC) { sp.ends[gc].end_bit = seg_lo * 8 + L.end_bits; sp.ends[gc].out_bytes = err ? 0 : o; sp.ends[gc].flags = err ? (err << 8) : (L.end_final | (nofit ? 2u : 0u)); }
 #ifdef ZGPU_INF_TIME
         t_acc[6] = n_mat;
         for (int i_ = 0; i_ < 16; i_++) if (t_acc[i_]) atomicAdd(&inf_time[i_], t_acc[i_]);
 #endif
-        if constexpr (VERIFY || FOLD) { meta[c].out_bytes = err ? 0 : o; meta[c].adler_a = run.a; meta[c].adler_b = run.b; meta[c].crc = run.crc; }
+        if constexpr (SPEC && VERIFY) { } // (the check pass: its values stand in the record above)
+        else if constexpr (VERIFY || FOLD) { meta[c].out_bytes = err ? 0 : o; meta[c].adler_a = run.a; meta[c].adler_b = run.b; meta[c].crc = run.crc; }
         else if (meta) { meta[c].out_bytes = err ? 0 : o; meta[c].ntok = 0; meta[c].adler_a = 1; meta[c].adler_b = 0; meta[c].in_bytes = 0; meta[c].data_type = 2; }
     }
     } // !SIZES
@@ -807,7 +836,9 @@ void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const 
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 16384>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds16);
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 8192>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds8);
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsSpec));
+        hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<true, ZGPU_INF_RING, false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsSpec));
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 32768, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsVerify));
+        hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<true, 32768, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsVerify));
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 32768, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFoldT<32768>));
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 16384, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFoldT<16384>));
         hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel_t<false, 8192, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(InflateLdsFoldT<8192>));
@@ -818,9 +849,11 @@ void launch_inflate_decode(InfKind kind, int ring_kb, const InfLaunch &a, const 
         hipLaunchKernelGGL(kern, dim3(a.nchunks), dim3(threads), lds, st, a.in, a.in_bytes, a.offsets, a.chunk0, a.nchunks, a.last_chunk, a.chunk_size, a.out, a.out_cap,
                            a.status, a.meta, a.dict, a.dict_len, a.stream_mode, sp, a.checks);
     };
-    if (kind == kInfPieces) go(inflate_kernel_t<true>, 128, sizeof(InflateLdsSpec));
+    if (kind == kInfPieces && sp.mid == nullptr) go(inflate_kernel_t<true, ZGPU_INF_RING, false, false, false, false, true>, 128, sizeof(InflateLdsSpec)); // (the no-pages form: an instantiation of its own, so the decode in pieces is the code it was)
+    else if (kind == kInfPieces) go(inflate_kernel_t<true>, 128, sizeof(InflateLdsSpec));
     else if (kind == kInfSizes) go(inflate_kernel_t<false, ZGPU_INF_RING, true, true>, 64, sizeof(InflateLdsSizes));
     else if (kind == kInfPieceSizes) go(inflate_kernel_t<true, ZGPU_INF_RING, false, true>, 64, sizeof(InflateLdsSizes));
+    else if (kind == kInfPieceVerify) go(inflate_kernel_t<true, 32768, false, false, true>, 128, sizeof(InflateLdsVerify));
     else if (kind == kInfVerify) go(inflate_kernel_t<false, 32768, true, false, true>, 128, sizeof(InflateLdsVerify));
     else if (kind == kInfBatchFold) {
         if (ring_kb == 8) go(inflate_kernel_t<false, 8192, true, false, false, true>, 128, sizeof(InflateLdsFoldT<8192>));

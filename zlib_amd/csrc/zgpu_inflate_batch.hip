@@ -4,7 +4,8 @@
 // the finish kernel (zgpu_stitch.hip) joins the pieces of each item and compares its trailer.  Items of 128 KiB of deflate data or more are decoded in
 // pieces instead (zgpu_inflate_batch_pieces.hip), blocking decode only, and rejoin the chain at the merge kernel.  The sizing pass and the integrity test (further down) run
 // the same header kernel and the decoder in its SIZES / VERIFY mode: neither has a destination, the second still has its trailers compared.  The blocking
-// sizing pass has its long items counted in pieces, the sizing form of the same file's piece path, behind its read-back (batch_sizes_long).
+// sizing pass has its long items counted in pieces, the sizing form of the same file's piece path, behind its read-back (batch_sizes_long); the blocking
+// integrity test has them checked in pieces, the verify form, behind its read-back (batch_pieces_verify_run).
 // The stream-ordered calls (zgpu_inflate_batch_*_enqueue, at the end) put the same chains on the caller's stream with the caller's workspace in place of
 // the engine's scratch and read nothing back; their decode runs the decoder in its FOLD mode, which checks the bytes while it stores them.
 #include "zgpu_common.h"
@@ -430,6 +431,8 @@ __global__ void __launch_bounds__(256) batch_verify_merge_kernel(const InfStatus
 
 // header kernel, the verifying decoder in rounds of 65,536 items, the finish kernel of the batch decoder (the trailer is compared by the very code that
 // compares it there), one read-back.  No destination, no piece table, no checksum kernels.  *states: as inflate_batch_run_ranges
+// Long items: classified by the header kernel, checked in pieces behind the read-back (zgpu_inflate_batch_pieces.hip, the verify form), then merge and finish again.
+// zgpu_inflate_batch_verify_enqueue does not have this: no host sees its items' sizes.
 int inflate_batch_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_bytes, const uint64_t *d_in_off, uint64_t n, int wrap, uint32_t checks, zgpu_inflate_item *d_items,
                              uint64_t *nfailed, const BatchItemState **states, hipStream_t st)
 {
@@ -443,13 +446,20 @@ int inflate_batch_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     // the check each item's wrapper needs is always computed (AUTO: both), the others when asked for
     const uint32_t do_adler = (checks & 1u) || wrap == (int)kWrapZlib || wrap == (int)kWrapAuto;
     const uint32_t do_crc = (checks & 2u) || wrap == (int)kWrapGzip || wrap == (int)kWrapAuto;
+    // long items in pieces (a deflate body of ZGPU_BATCH_PIECES_VERIFY_MIN_BYTES or more; not set: ZGPU_BATCH_PIECES_MIN_BYTES where set, else 20,000,000; 0: none): only a call whose
+    // input can hold one (the block finder reads the input in 16-byte vectors: an input that is not aligned goes the old way).  They leave the segment table
+    // for the list, as in inflate_batch_run_ranges, and the verifier's launch skips them: batch_pieces_verify_run, behind the read-back, checks them in pieces.
+    const BatchPiecesVerifyKnobs kn = batch_pieces_verify_knobs();
+    const bool pieces = kn.min_bytes && in_bytes >= kn.min_bytes && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0;
+    const uint64_t max_long = pieces ? (in_bytes / kn.min_bytes < n ? in_bytes / kn.min_bytes : n) : 0;
     BatchScratch s;
-    if (int rc = batch_scratch(e, n, kScratchVerify, 0, &s)) return rc;
+    if (int rc = batch_scratch(e, n, kScratchVerify, 0, &s, pieces ? batch_pieces_verify_scratch_bytes(max_long) : 0)) return rc;
     ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt, 0, 256, st));
     const uint32_t ngrid = (uint32_t)((n + 255) / 256);
+    const PiecesList pl = pieces ? PiecesList{s.cnt + 8, batch_pieces_items(s.long_items), kn.min_bytes, max_long} : PiecesList{};
     // (no destination: the input tables stand in for it, as in the sizing pass)
     hipLaunchKernelGGL(batch_header_kernel, dim3(ngrid), dim3(256), 0, st, d_in, in_bytes, d_in_off, d_in_off + 1, n, (uint32_t)wrap, in_bytes, d_in_off, d_in_off + 1, s.seg, s.items,
-                       reinterpret_cast<uint32_t *>(s.cnt + 2));
+                       reinterpret_cast<uint32_t *>(s.cnt + 2), pl);
     hipEvent_t ev{};
     prof_span_begin(e, st, &ev);
     for (uint64_t c0 = 0; c0 < n; c0 += 65536) {
@@ -462,9 +472,24 @@ int inflate_batch_verify_run(zgpu_engine *e, const uint8_t *d_in, uint64_t in_by
     hipLaunchKernelGGL(batch_verify_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
     launch_batch_finish(s.items, n, s.meta, d_in, do_adler, do_crc, d_items, s.cnt + 1, st);
     ZGPU_HIP_CHECK(hipGetLastError());
-    unsigned long long h[3] = {0, 0, 0};
-    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    // The call's one read-back.  With long items possible it also fetches their counters (104 bytes more of this copy: all a call without long items pays);
+    // when there are some, the piece path runs now, the long items' records and check values replace the empty ones the verifier's launch left, and the merge,
+    // the finish kernel -- the failed counter cleared first: the first pass has counted the long items' empty records -- and the read-back are taken again.
+    unsigned long long h[16] = {};
+    ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, pieces ? sizeof h : 3 * sizeof h[0], hipMemcpyDeviceToHost, st));
     ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    if (pieces && !h[2] && h[8 + kHdrLong] != 0) {
+        prof_span_begin(e, st, &ev);
+        const int prc = batch_pieces_verify_run(e, d_in, in_bytes, do_adler | (do_crc << 1), max_long, s.long_items, s.cnt + 8, h + 8, s.items, s.status, s.meta, kn.round_slots, st);
+        prof_span_end(e, st, ZGPU_STAGE_INFLATE, ev);
+        if (prc) return prc;
+        ZGPU_HIP_CHECK(hipMemsetAsync(s.cnt + 1, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(batch_verify_merge_kernel, dim3(ngrid), dim3(256), 0, st, s.status, n, do_adler | do_crc, s.items);
+        launch_batch_finish(s.items, n, s.meta, d_in, do_adler, do_crc, d_items, s.cnt + 1, st);
+        ZGPU_HIP_CHECK(hipGetLastError());
+        ZGPU_HIP_CHECK(hipMemcpyAsync(h, s.cnt, 3 * sizeof h[0], hipMemcpyDeviceToHost, st));
+        ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+    }
     collect_spans(e);
     if (h[2]) return fail(e, ZGPU_STREAM_ERROR, "inflate batch offsets out of range");
     if (nfailed) *nfailed = h[1];

@@ -1,8 +1,9 @@
 // zgpu_inflate_pieces_plan.h -- internal (not installed): what the piece path of the blocking batch decode (zgpu_inflate_batch_pieces.hip) decides from
 // plain numbers: which items are long, how far apart their pieces and their block finders stand, which of the finders' hits become piece starts,
 // how a call's long items are split into rounds and how a round's scratch is laid out; and, for the sizing form of the path (at the end), the verdict
-// over an item's counted pieces and the sizing round's plan.  No HIP type and no include but <cstdint>: tests/tools/inflate_pieces_plan_model.cpp and
-// tests/tools/inflate_sizes_pieces_model.cpp run the same code on a machine without a GPU.  The functions the device runs too carry ZGPU_PIECES_HD, which is
+// over an item's counted pieces and the sizing round's plan; and, for the verify form (behind that), the verdict over an item's tails records, the slot
+// cap and the verify round's plan.  No HIP type and no include but <cstdint>: tests/tools/inflate_pieces_plan_model.cpp,
+// tests/tools/inflate_sizes_pieces_model.cpp and tests/tools/inflate_verify_pieces_model.cpp run the same code on a machine without a GPU.  The functions the device runs too carry ZGPU_PIECES_HD, which is
 // `__host__ __device__` under hipcc and nothing elsewhere.
 // The spacing formulas are those of inflate_spec_run (zgpu_inflate_stream.hip) for one stream of the same length.
 #pragma once
@@ -260,5 +261,89 @@ inline uint64_t pieces_sizes_round_end(const PiecesItemCost *c, uint64_t nlong, 
     }
     return k;
 }
+
+// ---- the verify form (the blocking integrity test, batch_pieces_verify_run) ----
+// Check values need every byte, in order, with the real 32 KiB in front of every piece -- and the integrity test allocates no room for a decoded byte.  So
+// the pieces are decoded twice, both times into LDS alone: the tails pass (the rowed SPEC decode with no pages) leaves per slot its tail -- the last
+// 32 Ki symbols, markers included -- and its end record; the chain below and the window kernels turn the tails into per-slot byte windows; the check pass
+// decodes every chained piece again behind the window of the slot in front and folds its bytes.  A slot costs its tail, its window and its records:
+// nothing is proportional to an item's decoded size or to the number of items.
+// ZGPU_BATCH_PIECES_VERIFY_MIN_BYTES when neither it nor ZGPU_BATCH_PIECES_MIN_BYTES is set: decided by profiles/r14_batch_verify_long_table.txt.  Two passes
+// over every piece lose to the one-workgroup verifier on 256 items with bodies of 318 KB (46.6 ms against 18.9 ms) and win on 16 items with bodies of
+// 20,481,854 bytes (381 ms against 986 ms): the smallest measured body at which the path wins, rounded down.  Nothing between the two has been measured.
+constexpr uint64_t kPiecesVerifyMinBytesDefault = 20000000;
+constexpr uint64_t kPiecesVerifyRoundSlotsDefault = 1024; // ZGPU_BATCH_PIECES_VERIFY_ROUND_SLOTS: one residency of the check kernel, four workgroups on each of 256 CUs
+// per piece slot: its tail (16-bit symbols), its window (bytes), its row, end record, status, output start and check record
+constexpr uint64_t kPiecesVerifyPerPieceBytes = 2ull * kPiecesRing + kPiecesRing + 32 + 16 + 16 + 8 + 32;
+// the slot cap rounds are made under: the knob (0: the default), and never so many slots that a round of items within the cap would pass kPiecesScratchCap
+ZGPU_PIECES_HD inline uint64_t pieces_verify_slot_cap(uint64_t knob)
+{
+    const uint64_t most = (kPiecesScratchCap / 2) / kPiecesVerifyPerPieceBytes, cap = knob ? knob : kPiecesVerifyRoundSlotsDefault;
+    return cap < most ? cap : most;
+}
+
+// The verdict over one item's tails records: pieces_sizes_chain without its `need` term (a reach in front of the item is the check pass's to find, exactly:
+// it knows where every piece starts).  ostart[i] receives where piece i's output starts inside its item, for every piece up to the final one.
+// Termination: one step per piece, pieces_links in each.
+template <class End, class Row>
+ZGPU_PIECES_HD inline PiecesSizesVerdict pieces_verify_chain(const End *ends, const Row *rows, uint32_t npieces, const uint8_t *in, uint64_t body_lo, uint64_t in_hi, uint64_t *ostart)
+{
+    PiecesSizesVerdict v{};
+    bool ended = false;
+    for (uint32_t i = 0; i < npieces; i++) {
+        if (ends[i].flags >> 8) break; // an error, or never written
+        ostart[i] = v.total;
+        v.total += ends[i].out_bytes; v.used = i + 1;
+        if (ends[i].flags & 1u) { ended = true; v.end_bit = ends[i].end_bit; break; }
+        if (i + 1 == npieces || !pieces_links(in, ends[i].end_bit, rows[i + 1].start)) break;
+    }
+    v.clean = (ended && v.total <= kPiecesItemLimit && v.end_bit >= body_lo * 8 && v.end_bit <= in_hi * 8) ? 1u : 0u;
+    return v;
+}
+
+// A verify round's scratch.  The small records first, then one entry of zeros (what lies in front of an item's first piece, for the window composition),
+// the windows and the tails.  There is no term in an item's decoded size: there is no room and there are no pages.
+struct PiecesVerifyRoundPlan {
+    PiecesRegion targets, found, rows, ends, status, ostart, checks, ranges, entry, windows, tails; // in this order
+    uint64_t total; // 0: the round cannot be had (2^32 - 1 items, finders or slots, or more)
+};
+constexpr int kPiecesVerifyRegions = 11;
+inline const PiecesRegion &pieces_verify_region(const PiecesVerifyRoundPlan &p, int i)
+{
+    const PiecesRegion *r[kPiecesVerifyRegions] = {&p.targets, &p.found, &p.rows, &p.ends, &p.status, &p.ostart, &p.checks, &p.ranges, &p.entry, &p.windows, &p.tails};
+    return *r[i];
+}
+inline const char *pieces_verify_region_name(int i)
+{
+    static const char *const names[kPiecesVerifyRegions] = {"targets", "found", "rows", "ends", "status", "ostart", "checks", "ranges", "entry", "windows", "tails"};
+    return i >= 0 && i < kPiecesVerifyRegions ? names[i] : "";
+}
+inline PiecesVerifyRoundPlan pieces_verify_round_plan(uint64_t nitems, uint64_t ntargets, uint64_t npieces)
+{
+    PiecesVerifyRoundPlan p{};
+    if (nitems >= 0xFFFFFFFFull || ntargets >= 0xFFFFFFFFull || npieces >= 0xFFFFFFFFull) return p;
+    uint64_t off = 0;
+    auto carve = [&](uint64_t bytes) { PiecesRegion r{off, bytes}; off = (off + bytes + kPiecesAlign - 1) & ~(kPiecesAlign - 1); return r; };
+    p.targets = carve(ntargets * 24);
+    p.found = carve(ntargets * 16);
+    p.rows = carve(npieces * 32);
+    p.ends = carve(npieces * 16);
+    p.status = carve(npieces * 16);
+    p.ostart = carve(npieces * 8);
+    p.checks = carve(npieces * 32);          // PieceCheck
+    p.ranges = carve(nitems * 8);            // the chained pieces of every item, for the window composition
+    p.entry = carve(kPiecesRing);            // zeros
+    p.windows = carve(npieces * kPiecesRing);
+    p.tails = carve(npieces * kPiecesRing * 2);
+    p.total = off;
+    return p;
+}
+// what a long item adds to a verify round's scratch (its room and its decoded size do not count)
+ZGPU_PIECES_HD inline uint64_t pieces_verify_item_scratch(const PiecesItemCost &c)
+{
+    return (uint64_t)c.piece_cap * kPiecesVerifyPerPieceBytes + (uint64_t)c.ntargets * kPiecesPerTargetBytes + 8;
+}
+// Rounds are made by pieces_sizes_round_end under pieces_verify_slot_cap: a round of more than one item has `cap` slots at most, so its piece scratch is
+// bounded by max(cap, the largest item's piece_cap) * kPiecesVerifyPerPieceBytes whatever the call holds.
 
 } // namespace zgpu

@@ -468,6 +468,14 @@ void launch_spec_resolve_items(const SpecArgs &sp, uint32_t nslots, uint32_t nit
     hipLaunchKernelGGL(spec_resolve_kernel, dim3(sp.page_cap), dim3(256), 0, st, sp.mid, sp.page_owner, sp.page_cap, sp.ends, nslots, windows, out_start, 0u, d_out, (uint64_t)0,
                        static_cast<uint32_t *>(nullptr), sp.rows, items, sp.page_count);
 }
+// the windows alone (the verify form of the piece path: there is nothing to resolve into)
+void launch_spec_windows_items(uint16_t *tails, uint32_t nslots, uint32_t nitems, const uint2 *ranges, const uint8_t *entry, uint8_t *windows, hipStream_t st)
+{
+    spec_opt_in();
+    if (!nslots || !nitems) return;
+    hipLaunchKernelGGL(spec_window_rel_kernel, dim3(nitems), dim3(1024), 4 * kOutRing, st, tails, nslots, 0u, ranges);
+    hipLaunchKernelGGL(spec_window_abs_kernel, dim3(nslots), dim3(256), 0, st, tails, nslots, 0u, entry, windows);
+}
 
 // 0: decoded (res complete); 1: not this way (the caller uses the one-workgroup decoder); anything else: an error of the engine
 // start_bit (0..7): the deflate data begins at that bit of the first byte (a stream taken up again where an earlier call's last whole piece ended)
@@ -785,7 +793,7 @@ static int inflate_stream_host(zgpu_engine *e, const void *in, uint64_t in_bytes
 
 extern "C" {
 #pragma GCC visibility push(default)
-uint64_t zgpu_inflate_spec_count(int which) { return which == 0 ? g_spec_done.load() : which == 1 ? g_whole_done.load() : (which == 2 || which == 3) ? batch_pieces_count(which - 2) : (which == 4 || which == 5) ? batch_pieces_sizes_count(which - 4) : 0; }
+uint64_t zgpu_inflate_spec_count(int which) { return which == 0 ? g_spec_done.load() : which == 1 ? g_whole_done.load() : (which == 2 || which == 3) ? batch_pieces_count(which - 2) : (which == 4 || which == 5) ? batch_pieces_sizes_count(which - 4) : (which == 6 || which == 7) ? batch_pieces_verify_count(which - 6) : 0; }
 int zgpu_inflate_find_chunks_host(zgpu_engine *e, const void *in, uint64_t in_bytes, uint32_t chunk_size, uint64_t *offsets, uint64_t max_chunks,
                                   uint64_t *nchunks)
 {

@@ -779,6 +779,12 @@ class Engine:
         fell back to the one-wave sizing kernel), since the library was loaded.  batch_piece_counts() goes on counting the decode alone."""
         return int(self.L.zgpu_inflate_spec_count(4)), int(self.L.zgpu_inflate_spec_count(5))
 
+    def batch_verify_piece_counts(self):
+        """(long items of blocking integrity tests -- inflate_batch_verify_host / _device and what stands on them -- that were verified in pieces, long items of
+        an integrity test that fell back to the one-workgroup verifier), since the library was loaded.  The decode's and the sizing pass's counters do not move
+        in a verify call."""
+        return int(self.L.zgpu_inflate_spec_count(6)), int(self.L.zgpu_inflate_spec_count(7))
+
     def inflate_device(self, d_in, n, d_offsets, nchunks, d_out, out_cap, chunk_size=CHUNK, stream=None):
         res = InflateResult()
         rc = self.L.zgpu_inflate_device(self.h, d_in, n, d_offsets, nchunks, chunk_size, d_out, out_cap, C.byref(res), stream)
