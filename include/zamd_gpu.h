@@ -727,6 +727,24 @@ void zgpu_profile_reset(zgpu_engine *e);
 int zgpu_profile_get(zgpu_engine *e, int stage, double *ms, uint64_t *launches);
 const char *zgpu_stage_name(int stage);
 
+/* Levels 1-3, one continuous stream: what the rounds of the tile parse did since the engine was made (diagnostic).  Rounds and tile
+ * parses are always counted on the host.  The other six are the kernel's own counters of the tiles that were parsed AGAIN, summed over the rounds of
+ * every call made while the environment variable ZGPU_FAST_STATS is set (read per call; without it they stay 0 and the kernel counts nothing; the phases
+ * of a round 0 parse no tile again and add nothing): with it
+ * the 32 bytes come back with the read-back each round already makes.  0 for a null engine or an unknown counter. */
+enum {
+    ZGPU_FAST_ROUNDS = 0,       /* rounds, over all batches */
+    ZGPU_FAST_TILE_PARSES,      /* tiles launched, over all rounds */
+    ZGPU_FAST_SAME_ENTRY,       /* parsed again and entered where it had entered last time */
+    ZGPU_FAST_STOPPED_EARLY,    /* ... and stopped early: its old results stand */
+    ZGPU_FAST_DIFFERENT_TOKEN,  /* ... and met a token that differs from last time's */
+    ZGPU_FAST_REACH_TO_END,     /* ... with changed history within reach up to the tile's end */
+    ZGPU_FAST_WINDOWS_TO_DIFF,  /* 64-position windows in front of the first different token, summed */
+    ZGPU_FAST_WINDOWS_OF_DIFF,  /* windows of the tiles that met one, summed */
+    ZGPU_FAST_COUNT_N
+};
+uint64_t zgpu_deflate_fast_count(zgpu_engine *e, int which);
+
 /* Seeded synthetic corpora of SURVEY.md 8(d), generated in HBM (zlib_amd/csrc/corpus.h).
  * kind 0 silesia-mix, 1 log-text; d_out receives nchunks * 65536 bytes. */
 int zgpu_corpus_fill_device(zgpu_engine *e, uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks,

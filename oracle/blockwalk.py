@@ -112,8 +112,9 @@ def _code_lengths(z, pos):
     return lens[:hlit], lens[hlit:], pos
 
 
-def _coded(z, pos, out, ltab, lbits, dtab, dbits):
-    """The tokens of a coded block from bit `pos` on, appended to `out`: (tokens, length of the last one, bit offset behind the end-of-block)."""
+def _coded(z, pos, out, ltab, lbits, dtab, dbits, toks=None):
+    """The tokens of a coded block from bit `pos` on, appended to `out`: (tokens, length of the last one, bit offset behind the end-of-block).
+    toks: a list that receives every token as (position, dist, length), a literal as (position, 0, 1)."""
     lmask, dmask = (1 << lbits) - 1, (1 << dbits) - 1
     lbase, lext, dbase, dext = W.LEN_BASE, W.LEN_EXTRA, W.DIST_BASE, W.DIST_EXTRA
     from_bytes = int.from_bytes
@@ -127,6 +128,8 @@ def _coded(z, pos, out, ltab, lbits, dtab, dbits):
         if n == 0 or pos + n > nz:
             raise ValueError("no literal/length code at bit %d" % pos)
         if s < 256:
+            if toks is not None:
+                toks.append((len(out), 0, 1))
             out.append(s)
             pos += n
             ntok += 1
@@ -151,6 +154,8 @@ def _coded(z, pos, out, ltab, lbits, dtab, dbits):
         pos += used + n + x
         if dist > len(out):
             raise ValueError("distance %d with %d bytes in front, at bit %d" % (dist, len(out), pos))
+        if toks is not None:
+            toks.append((len(out), dist, length))
         if dist >= length:
             o = len(out) - dist
             out += out[o: o + length]
@@ -163,8 +168,9 @@ def _coded(z, pos, out, ltab, lbits, dtab, dbits):
             raise ValueError("the stream ends inside a token")
 
 
-def walk(z, max_blocks=None):
-    """(blocks, data, bytes of z used) -- see the module's text.  Raises ValueError on a stream that is not valid or ends before a final block."""
+def walk(z, max_blocks=None, toks=None):
+    """(blocks, data, bytes of z used) -- see the module's text.  Raises ValueError on a stream that is not valid or ends before a final block.
+    toks: a list that receives the tokens of the coded blocks, (position, dist, length) each."""
     z = bytes(z)
     out = bytearray()
     blocks = []
@@ -199,7 +205,7 @@ def walk(z, max_blocks=None):
                     raise ValueError("no end-of-block code in the block at bit %d" % pos)
                 ltab, lbits = _table(ll)
                 dtab, dbits = _table(dl)
-            ntok, last, pos = _coded(z, p, out, ltab, lbits, dtab, dbits)
+            ntok, last, pos = _coded(z, p, out, ltab, lbits, dtab, dbits, toks)
             blocks.append(Block(at, final, btype, ntok, len(out) - start, last, pos, start))
         if final or (max_blocks is not None and len(blocks) >= max_blocks):
             return blocks, bytes(out), (pos + 7) >> 3
@@ -214,3 +220,19 @@ def first_difference(got, want):
     for i, b in enumerate(blocks):
         if bit < b.end_bit or i + 1 == len(blocks):
             return "%d bytes for %d, first differing bit %d, in block %d of %d: %s" % (len(got), len(want), bit, i, len(blocks), b)
+
+
+def first_token_difference(got, want_tokens):
+    """For a report: the first token of `got` (a raw stream, valid or not) that is not the one of want_tokens (a list of (position, dist, length)), as text."""
+    toks = []
+    try:
+        walk(got, toks=toks)
+        err = ""
+    except ValueError as e:
+        err = " (then: %s)" % e
+    for i, w in enumerate(want_tokens):
+        if i >= len(toks):
+            return "%d tokens for %d, the first %d agree%s" % (len(toks), len(want_tokens), i, err)
+        if tuple(toks[i]) != tuple(w):
+            return "token %d at position %d: (dist %d, len %d), the reference has (dist %d, len %d) at %d%s" % ((i, toks[i][0], toks[i][1], toks[i][2], w[1], w[2], w[0], err))
+    return "the first %d tokens agree, %d follow%s" % (len(want_tokens), len(toks) - len(want_tokens), err)

@@ -61,28 +61,35 @@ static ContKnobs read_cont_knobs()
     { const char *v = getenv("ZGPU_CONT_PIPE"); if (v && *v) kn.pipe = atoi(v); }
     kn.fast_run = env_u32("ZGPU_FAST_RUN", 0);
     kn.trace = getenv("ZGPU_FAST_TRACE") != nullptr;
+    kn.stats = getenv("ZGPU_FAST_STATS") != nullptr;
     return kn;
 }
 
 // Everything of lz_tiles_fast that is there for ZGPU_FAST_TRACE (what every round did, to stderr) and ZGPU_FAST_FORCE_ROUNDS=n (debug: every tile is
-// parsed again in each of the first n rounds); with neither set no member does anything
+// parsed again in each of the first n rounds) and ZGPU_FAST_STATS (the trace's six counters summed into the engine, zgpu_deflate_fast_count); with none set
+// no member does anything
 struct FastDebug {
     zgpu_engine *e; uint32_t nb; hipStream_t st;
-    bool trace = false; int force = 0;
-    int init(zgpu_engine *e_, uint32_t nb_, bool trace_, hipStream_t st_)
+    bool trace = false, stats = false; int force = 0;
+    int init(zgpu_engine *e_, uint32_t nb_, bool trace_, bool stats_, hipStream_t st_)
     {
-        e = e_; nb = nb_; st = st_; trace = trace_;
+        e = e_; nb = nb_; st = st_; trace = trace_; stats = stats_;
         static int force_env = -1; // (read once a process)
         if (force_env < 0) { const char *v = getenv("ZGPU_FAST_FORCE_ROUNDS"); force_env = v ? atoi(v) : 0; }
         force = force_env;
-        if (trace && (e->cf_dbg.reserve(e, 65536 * 8) || e->cf_dstat.reserve(e, 8))) return ZGPU_MEM_ERROR;
+        if (trace && e->cf_dbg.reserve(e, 65536 * 8)) return ZGPU_MEM_ERROR;
+        if ((trace || stats) && e->cf_dstat.reserve(e, 8)) return ZGPU_MEM_ERROR;
         return ZGPU_OK;
     }
     void arm(FastTiles &ft) const // the kernel's records of a launch: eight words per tile, eight counters
     {
         ft.dbg = trace && nb <= 65536 ? static_cast<uint32_t *>(e->cf_dbg) : nullptr;
-        if (trace) { hipMemsetAsync(e->cf_dstat, 0, 32, st); ft.stat = e->cf_dstat; }
+        if (trace || stats) { hipMemsetAsync(e->cf_dstat, 0, 32, st); ft.stat = e->cf_dstat; }
     }
+    // ZGPU_FAST_STATS: the round's counters come back with the round's own read-back (queued in front of its synchronise) and are summed behind it.  They count
+    // tiles that are parsed AGAIN: the launches of round 0 in phases (fast_round0_phases) clear them and nobody reads them, no tile has old results there
+    int read_stats(uint32_t *hs) const { if (stats) ZGPU_HIP_CHECK(hipMemcpyAsync(hs, e->cf_dstat, 32, hipMemcpyDeviceToHost, st)); return ZGPU_OK; }
+    void add_stats(const uint32_t *hs) const { if (stats) for (int i = 0; i < 6; i++) e->cf_stat[i] += hs[i]; }
     void phases_done(uint32_t K, size_t nheads) const { if (trace) fprintf(stderr, "fast tiles: round 0 in %u phases, %zu run heads to parse again\n", K, nheads); }
     void before_round(const FastTiles &ft) const { if (ft.dbg) hipMemsetAsync(e->cf_dbg, 0xff, (size_t)nb * 32, st); }
     void after_launch(const FastTiles &ft) const
@@ -183,7 +190,7 @@ static int lz_tiles_fast(zgpu_engine *e, const ChunkGeom &g, const TileGeom &tg,
     StageTimer t(e, st, ZGPU_STAGE_MATCH);
     launch_fast_init(e->cf_cur, e->cf_act_a, e->cf_exit_a, nb, st);
     uint32_t *list = nullptr, *list_next = e->cf_list_a, ngrid = nb;
-    int rc = r.dbg.init(e, nb, kn.trace, st);
+    int rc = r.dbg.init(e, nb, kn.trace, kn.stats, st);
     if (rc) return rc;
     const uint32_t K = plan_fast_phases(nb, kn.fast_run);
     if (K > 1) {
@@ -199,9 +206,11 @@ static int lz_tiles_fast(zgpu_engine *e, const ChunkGeom &g, const TileGeom &tg,
         r.launch(ft, ngrid);
         r.dbg.after_launch(ft);
         launch_fast_flip(e->cf_cur, r.act, r.act_next, e->cf_changed, e->cf_exit_a, e->cf_exit_b, nb, round, e->cf_count, list_next, ft.kept, st);
-        uint32_t active = 0;
+        uint32_t active = 0, hs[8] = {};
         ZGPU_HIP_CHECK(hipMemcpyAsync(&active, e->cf_count, 4, hipMemcpyDeviceToHost, st));
+        if ((rc = r.dbg.read_stats(hs))) return rc;
         ZGPU_HIP_CHECK(hipStreamSynchronize(st));
+        r.dbg.add_stats(hs);
         e->cf_rounds++; e->cf_tile_parses += round == 0 ? nb : 0;
         if ((rc = r.dbg.force_round(round, r.act_next, list_next, &active))) return rc;
         r.dbg.round_done(round, active);

@@ -270,6 +270,7 @@ struct ContKnobs {
     int pipe = 0;            // ZGPU_CONT_PIPE
     uint32_t fast_run = 0;   // ZGPU_FAST_RUN
     bool trace = false;      // ZGPU_FAST_TRACE
+    bool stats = false;      // ZGPU_FAST_STATS
 };
 
 struct ContPlan {

@@ -102,9 +102,10 @@ struct zgpu_engine {
     // ... levels 1-3: the rounds of fastwin_tile_kernel (the per-batch ones are one group)
     DevBuf<uint16_t> cf_exit_a, cf_exit_b; DevBuf<uint32_t> cf_ins0, cf_ins1, cf_prev, cf_prev2, cf_hist, cf_count;
     DevBuf<uint8_t> cf_cur, cf_act_a, cf_act_b, cf_changed, cf_kept; DevBuf<uint32_t> cf_list_a, cf_list_b, cf_used; DevBuf<uint16_t> cf_entry_used;
-    DevBuf<uint32_t> cf_dbg, cf_dstat; // (ZGPU_FAST_TRACE only)
+    DevBuf<uint32_t> cf_dbg, cf_dstat; // (ZGPU_FAST_TRACE; cf_dstat ZGPU_FAST_STATS as well)
     hipStream_t ct_stream = nullptr; hipEvent_t ct_ev_a[2] = {nullptr, nullptr}, ct_ev_b[2] = {nullptr, nullptr}; // levels 4-9: a batch's blocks are made on a second stream under the next batch's walkers
     uint64_t cf_rounds = 0, cf_tile_parses = 0; // (diagnostic: rounds and tile parses since the engine was made)
+    uint64_t cf_stat[6] = {};                   // (ZGPU_FAST_STATS: FastTiles::stat summed over the rounds since the engine was made)
     // BGZF block finder (zgpu_bgzf.hip): per 4096 positions (bz_cnt, bz_base), per candidate (the others), one result record
     DevBuf<uint32_t> bz_cnt, bz_isize, bz_jump_a, bz_jump_b, bz_reach, bz_res;
     DevBuf<uint64_t> bz_base, bz_pos, bz_next, bz_in_off, bz_out_off;

@@ -184,6 +184,12 @@ const char *zgpu_stage_name(int stage)
     return stage >= 0 && stage < ZGPU_STAGE_COUNT ? names[stage] : "?";
 }
 
+uint64_t zgpu_deflate_fast_count(zgpu_engine *e, int which)
+{
+    if (!e || which < 0 || which >= ZGPU_FAST_COUNT_N) return 0;
+    return which == ZGPU_FAST_ROUNDS ? e->cf_rounds : which == ZGPU_FAST_TILE_PARSES ? e->cf_tile_parses : e->cf_stat[which - ZGPU_FAST_SAME_ENTRY];
+}
+
 int zgpu_corpus_fill_device(zgpu_engine *e, uint32_t kind, uint64_t seed, uint64_t first_chunk, uint64_t nchunks, void *d_out, void *hip_stream)
 {
     if (!e || !d_out) return fail(e, ZGPU_STREAM_ERROR, "null argument");

@@ -200,6 +200,8 @@ def load_library():
     L.zgpu_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64)]
     L.zgpu_stage_name.argtypes = [C.c_int]
     L.zgpu_stage_name.restype = C.c_char_p
+    L.zgpu_deflate_fast_count.argtypes = [vp, C.c_int]
+    L.zgpu_deflate_fast_count.restype = u64
     L.zgpu_corpus_fill_device.argtypes = [vp, u32, u64, u64, u64, vp, vp]
     _lib = L
     return L
@@ -302,6 +304,13 @@ class Engine:
         """deflateInit2's windowBits (9..15) and memLevel (1..9) for the deflate calls that follow; 15 / 8 is the default."""
         self._check(self.L.zgpu_deflate_set_geometry(self.h, window_bits, mem_level))
         self.geometry = (window_bits, mem_level)
+
+    FAST_COUNTS = ("rounds", "tile_parses", "same_entry", "stopped_early", "different_token", "reach_to_end", "windows_to_diff", "windows_of_diff")
+
+    def fast_round_counts(self):
+        """Levels 1-3, one continuous stream: what the rounds of the tile parse did since the engine was made (zgpu_deflate_fast_count), as a dict.  Rounds and
+        tile parses always count; the other six only over calls made while ZGPU_FAST_STATS is set in the environment."""
+        return {k: int(self.L.zgpu_deflate_fast_count(self.h, i)) for i, k in enumerate(self.FAST_COUNTS)}
 
     def set_tuning(self, tune=None):
         """deflateTune for the deflate calls that follow: tune = (good_length, max_lazy, nice_length, max_chain) instead of the level's row; None: the level's row again."""
